@@ -6,7 +6,7 @@ batch of 256 nbody-2 designs through TemporalUnet1D(dim=64, horizon=24) (BASELIN
 synthetic generator-defined weights (cindm_amd.synthetic), x_T and per-step noise from the in-kernel counter-based generator.
 Inputs (weights, state) are resident in HBM when the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W [--workload W]
+    python bench.py --gpus N --steps K --warmup W [--workload W] [--dump-outputs DIR] [--full]
         cfg2 (default)  BASELINE configs[1]: the metric's configuration
         cfg3            configs[2]: time composition, three 24-step windows -> 56 steps, batch 256
         cfg4            configs[3]: 4-body composition (6 pair + 4 single-body evaluations, 400 steps), 128 designs per GPU
@@ -15,12 +15,14 @@ Inputs (weights, state) are resident in HBM when the timed region starts.
                         (cfg5g: --steps 1 --warmup 1, ~35-55 s per chain)
 N > 1: launched by torch.distributed.run, one rank per GPU; every rank samples its own designs
 (weak scaling, no communication inside the loop) and the final designs are all-gathered over RCCL.
-Prints ONE JSON line on rank 0, with `roofline`, `cpu_baseline` and `rel_err` for every workload.
+Prints ONE JSON line on rank 0.
 
-The default run (cfg2, one GPU) also times EVERY other BASELINE configuration after the headline's timed region -- a few chains
-each of cfg3, cfg4, cfg2-ddim250 and cfg5 and a step-bounded sample of cfg5g, each with its own rel_err against the oracle, its
-roofline fraction and a bounded CPU baseline -- and nests the compact records under "workloads" in the same line
-(--no-extra-workloads skips them; they add about a minute).
+A plain run sets up, warms up, times the K chains and prints the line; nothing else.  --dump-outputs DIR then writes the designs
+the last timed chain returned as DIR/designs.npy (float32; same arguments, same inputs), so two builds can be compared output for
+output.  --full adds everything that is not the headline figure: `roofline` (a profiled forward), `cpu_baseline` and `rel_err`
+against the oracle, and for cfg2 on one GPU every other BASELINE configuration after the headline's timed region -- a few chains
+each of cfg3, cfg4, cfg2-ddim250 and cfg5 and a step-bounded sample of cfg5g, each with its own rel_err, roofline fraction and a
+bounded CPU baseline -- nested under "workloads" in the same line (--no-cpu-baseline / --no-extra-workloads skip parts of it).
 """
 import argparse
 import json
@@ -378,7 +380,8 @@ def cpu_baseline_2d(sd, budget_s=20.0, threads_hint=None, guided_sd=None, Bc=4):
 def measure_2d(args, wl, steps, warmup, cpu_budget_s, threads_hint=None, t_stop=0):
     """BASELINE configs[4]: airfoil 2-D, Unet(dim=64, dim_mults=(1,2), channels=21) on 64x64, 2-boundary composition,
     batch 64 designs per GPU (128 images per reverse step), 1000 DDPM steps per design (t_stop > 0: a step-bounded sample of
-    the chain, 1000 - t_stop steps, extrapolated -- every reverse step costs the same).  Returns the bench line (rank 0)."""
+    the chain, 1000 - t_stop steps, extrapolated -- every reverse step costs the same).  Returns (the bench line on rank 0, None
+    elsewhere; the designs of the last timed chain)."""
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -430,7 +433,7 @@ def measure_2d(args, wl, steps, warmup, cpu_budget_s, threads_hint=None, t_stop=
             elapsed = float(tmax.item())
         assert tuple(out.shape) == (total, nb, 21, 64, 64) and bool(torch.isfinite(out).all())
         roof = None
-        if rank == 0:
+        if rank == 0 and args.full:
             x = torch.randn((B * nb, 64 * 64, model.padded_channels), device=dev)
             x[:, :, 21:] = 0
             model.profile(x, 500)
@@ -500,9 +503,9 @@ def measure_2d(args, wl, steps, warmup, cpu_budget_s, threads_hint=None, t_stop=
             if t_stop:
                 line["config"]["sampled"] = (f"step-bounded sample: {steps} x the first {nsteps} reverse steps of the chain (t = 999 .. {t_stop}); "
                                              f"value and ms_per_step are extrapolated x{TIMESTEPS / nsteps:g} (every reverse step is the same work)")
-            if guided:
+            if guided and roof is not None:
                 line["roofline"]["note"] = "per_kind_us / launches are the diffusion U-Net's; the surrogate's kernel table is profiles/r06_kernel_stats_force.txt"
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 # cpu_baseline + rel_err: the oracle's reverse steps on a few designs, then the same steps, inputs and explicit noise
                 # through the HIP path.  Guided: 1 design (the surrogate's autograd on the CPU is ~4 s per design and step).
                 from cindm_amd.diffusion2d import NoiseTape2D        # noqa: F401  (the explicit-noise convention of p_sample)
@@ -521,7 +524,7 @@ def measure_2d(args, wl, steps, warmup, cpu_budget_s, threads_hint=None, t_stop=
                 line["rel_err"] = float((xg.cpu() - xc).abs().max() / xc.abs().max())
                 line["rel_err_note"] = (f"max-abs / max-abs of the state after the cpu_baseline leg's {len(tape)} reverse steps of {Bc} designs x {nb} "
                                         "boundaries (same weights, inputs and explicit noise on both sides, free-running); tolerance 1e-4")
-    return line
+    return line, out
 
 
 def main_cfg5(args):
@@ -535,9 +538,11 @@ def main_cfg5(args):
             dist.init_process_group("gloo")
         else:
             dist.init_process_group("nccl", device_id=dev)
-    line = measure_2d(args, args.workload, args.steps, args.warmup, 20.0)
+    line, out = measure_2d(args, args.workload, args.steps, args.warmup, 20.0)
     if line is not None and shared:
         line["shared_gpus"] = f"{world} ranks on {torch.cuda.device_count()} GPU(s), gloo rendezvous: code-path run, not a benchmark"
+    if line is not None and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
     if line is not None:
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -685,8 +690,8 @@ def bench_line_1d(world, B, steps, warmup, elapsed, text, S, evals, roof, recove
 
 
 def measure_1d(args, wl, steps, warmup, cpu_budget_s, threads_hint=None):
-    """One 1-D workload: warm-up chains, `steps` timed chains between barriers, the roofline leg, the CPU leg.  Returns the
-    bench line on rank 0 (None elsewhere)."""
+    """One 1-D workload: warm-up chains, `steps` timed chains between barriers and, with --full, the roofline leg and the CPU leg.
+    Returns (the bench line on rank 0, None elsewhere; the designs of the last timed chain)."""
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -724,7 +729,6 @@ def measure_1d(args, wl, steps, warmup, cpu_budget_s, threads_hint=None):
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
         assert tuple(out.shape) == (total,) + w["out_shape"] and bool(torch.isfinite(out).all())
-        step_launches, step_fused = diffusion.last_step_info()
 
         # ---- roofline leg (rank 0): per-dispatch begin / end timestamps of one forward in launch order ----
         # (hipExtLaunchKernelGGL start / stop events: the kernel's own duration, what rocprofv3 --kernel-trace reports;
@@ -732,7 +736,8 @@ def measure_1d(args, wl, steps, warmup, cpu_budget_s, threads_hint=None):
         # pair model sees in this workload
         roof = None
         S = w["steps_per_design"]
-        if rank == 0:
+        if rank == 0 and args.full:
+            step_launches, step_fused = diffusion.last_step_info()
             rows = w["rows"][0]
             x = torch.randn((rows, 24, 8), device=dev)
             model.profile(x, 500)
@@ -798,12 +803,12 @@ def measure_1d(args, wl, steps, warmup, cpu_budget_s, threads_hint=None):
             # the exact fp32-MFMA kernels (a weight tensor / an activation left the window)
             line["range_fallback"] = int(model.get_option("range_fallback"))
             line["mfma_f32"] = int(model.get_option("mfma_f32"))
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 line["cpu_baseline"], line["rel_err"], extra = cpu_baseline_1d(wl, w, B, dev, budget_s=cpu_budget_s, threads_hint=threads_hint)
                 line.update(extra)
                 line["rel_err_note"] = "max-abs / max-abs of the state after the cpu_baseline leg's reverse steps (same weights, inputs and explicit " \
                                        "noise on both sides, free-running); tolerance 1e-4"
-    return line
+    return line, out
 
 
 def compact(line):
@@ -828,7 +833,22 @@ def compact(line):
     return out
 
 
-# what the default run measures after the headline: (workload, timed chains, warm-up chains, CPU-leg budget in seconds, t_stop)
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out, outdir):
+    """--dump-outputs: the designs the last timed chain returned, as <outdir>/designs.npy (float32, shape of the chain's output).
+    Above DUMP_BYTES only a fixed, seeded sample of whole designs is written (ascending indices, the same on every run)."""
+    import numpy as np
+    x = out.detach().to("cpu", torch.float32)
+    if x.numel() * 4 > DUMP_BYTES:
+        keep = DUMP_BYTES // (x[0].numel() * 4)
+        x = x[torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "designs.npy"), x.numpy())
+
+
+# what the --full run of cfg2 measures after the headline: (workload, timed chains, warm-up chains, CPU-leg budget in seconds, t_stop)
 EXTRA_WORKLOADS = (("cfg3", 2, 1, 4.0, 0), ("cfg4", 3, 1, 4.0, 0), ("cfg2-ddim250", 3, 1, 3.0, 0), ("cfg5", 1, 1, 4.0, 0),
                    ("cfg5g", 1, 1, 8.0, 980), ("cfg2-b1024", 1, 1, 3.0, 0), ("cfg1-gpu", 3, 1, 2.0, 0), ("cfg2-f32mfma", 2, 1, 3.0, 0))
 
@@ -847,11 +867,18 @@ def main():
                          "scripts' default 250 DDIM steps; cfg5 = configs[4] (2-D airfoil); cfg5g = cfg5 under the ForceUnet design objective; "
                          "cfg2-b1024 = cfg2 at 1024 designs per GPU; cfg1-gpu = configs[0] (batch 4) on the GPU; cfg2-f32mfma = cfg2 on the "
                          "exact fp32-MFMA kernels (the range rule's fallback)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline, cpu_baseline and rel_err, and (cfg2, one GPU) "
+                         "every other workload nested under \"workloads\"")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline / rel_err")
     ap.add_argument("--no-extra-workloads", action="store_true",
-                    help="the default run (cfg2, one GPU) also times cfg3, cfg4, cfg2-ddim250, cfg5 and a step-bounded cfg5g after the headline "
-                         "and nests them under \"workloads\"; this skips them")
+                    help="with --full: the cfg2 run on one GPU also times cfg3, cfg4, cfg2-ddim250, cfg5 and a step-bounded cfg5g after the "
+                         "headline and nests them under \"workloads\"; this skips them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the designs of the last timed chain as DIR/designs.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     spawn_ranks_if_needed(args)
     if args.workload in ("cfg5", "cfg5g"):
         return main_cfg5(args)
@@ -866,17 +893,19 @@ def main():
             dist.init_process_group("gloo")
         else:
             dist.init_process_group("nccl", device_id=dev)
-    line = measure_1d(args, wl, args.steps, args.warmup, 20.0)
+    line, out = measure_1d(args, wl, args.steps, args.warmup, 20.0)
     if line is not None and shared:
         line["shared_gpus"] = f"{world} ranks on {torch.cuda.device_count()} GPU(s), gloo rendezvous: code-path run, not a benchmark"
-    if line is not None and wl == "cfg2" and world == 1 and not args.no_extra_workloads and not args.batch:
+    if line is not None and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
+    if line is not None and args.full and wl == "cfg2" and world == 1 and not args.no_extra_workloads and not args.batch:
         # every other BASELINE configuration, driver-timed in the same run; each builds its own models and frees them
         hint = (line.get("cpu_baseline") or {}).get("cores")
         extra = {}
         t_extra = time.time()
         for name, st, wu, budget, t_stop in EXTRA_WORKLOADS:
             try:
-                sub = measure_2d(args, name, st, wu, budget, threads_hint=hint, t_stop=t_stop) if name.startswith("cfg5") else \
+                sub, _ = measure_2d(args, name, st, wu, budget, threads_hint=hint, t_stop=t_stop) if name.startswith("cfg5") else \
                     measure_1d(args, name, st, wu, budget, threads_hint=hint)
                 extra[name] = compact(sub)
             except Exception as e:      # a failing extra workload must not take the headline down: it is reported, not hidden

@@ -795,3 +795,28 @@ def test_checkpoint_to_eval_simu_on_the_device(device, tmp_path):
     steps = {t: (t2.step_state[t], t2.step_boundary[t]) for t in range(1, 1000)}
     ref2 = O.p_sample_loop_2d(od2, (1, 2, 21, 64, 64), t2.init, steps, t_stop=996)
     assert out2.is_cuda and rel(out2, ref2) < TOL_CHAIN
+
+
+def test_bench_plain_run_dumps_the_last_timed_chain(device, tmp_path):
+    """`bench.py` without --full prints the headline line only (no roofline leg, CPU leg or nested workloads), and --dump-outputs
+    writes the designs of the LAST timed chain: the chain of that index (seed 1234 + warm-up + steps - 1), run here, reproduces them."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "32",
+                        "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=900, cwd=root, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+    assert abs(line["value"] - 32 / (line["ms_per_step"] / 1000.0)) < 1e-2 * line["value"]
+    assert line["roofline"] is None and not any(k in line for k in ("cpu_baseline", "rel_err", "workloads"))
+    got = np.load(tmp_path / "dump" / "designs.npy")
+    assert got.dtype == np.float32 and got.shape == (32, 24, 8) and np.isfinite(got).all()
+    sys.path.insert(0, root)
+    import bench
+    want = bench.build_1d("cfg2", 32, device)["chain"](1 + 2 - 1, 0)
+    assert rel(torch.from_numpy(got), want) < TOL_CHAIN

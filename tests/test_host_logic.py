@@ -499,6 +499,25 @@ def test_bench_line_of_an_eight_rank_world():
     assert cfg4["config"]["designs_per_step"] == 1024 and cfg4["config"]["unet_evals_per_design"] == 4000
 
 
+def test_bench_dump_outputs_is_float32_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs writes the designs as float32; above its byte limit it keeps a seeded sample of whole designs, the
+    same rows on every call, in ascending order."""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    x = torch.arange(10 * 3 * 4, dtype=torch.float64).reshape(10, 3, 4)
+    bench.dump_outputs(x, str(tmp_path / "a"))
+    a = np.load(tmp_path / "a" / "designs.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, x.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 3 * 4 * 4 + 5)        # room for 4 designs
+    bench.dump_outputs(x, str(tmp_path / "b"))
+    bench.dump_outputs(x, str(tmp_path / "c"))
+    b, c = np.load(tmp_path / "b" / "designs.npy"), np.load(tmp_path / "c" / "designs.npy")
+    idx = (b[:, 0, 0] / 12).astype(int)
+    assert b.shape == (4, 3, 4) and np.array_equal(b, c) and (np.diff(idx) > 0).all()
+    assert np.array_equal(b, x.float().numpy()[idx])
+
+
 def test_cpu_leg_is_self_consistent():
     """bench.py's CPU leg (round 4: the timed leg was 2.1 x slower than the sweep's value at the same thread count, three times
     over): every thread count of the sweep and the timed leg run in their own child process with the count fixed in the

@@ -27,18 +27,18 @@ if [ "$what" = 1d ] || [ "$what" = all ]; then
     ktrace cfg3 python3 /root/repo/tools/prof_wl.py cfg3 50
     ktrace cfg4 python3 /root/repo/tools/prof_wl.py cfg4 50
     for w in cfg2 cfg3 cfg4 cfg2-ddim250; do
-        python bench.py --workload $w > $out/bench_$w.json 2> $out/bench_$w.err; cut -c1-200 $out/bench_$w.json
+        python bench.py --full --workload $w > $out/bench_$w.json 2> $out/bench_$w.err; cut -c1-200 $out/bench_$w.json
     done
 fi
 if [ "$what" = 2d ] || [ "$what" = all ]; then
     pmc cfg5 7 python3 /root/repo/tools/prof2d.py 64 2 5
     cp $out/pmc_traffic_cfg5.json profiles/r03_pmc_traffic_cfg5.json
     ktrace cfg5 python3 /root/repo/tools/prof2d.py 64 2 10
-    python bench.py --workload cfg5 > $out/bench_cfg5.json 2> $out/bench_cfg5.err; cut -c1-200 $out/bench_cfg5.json
+    python bench.py --full --workload cfg5 > $out/bench_cfg5.json 2> $out/bench_cfg5.err; cut -c1-200 $out/bench_cfg5.json
 fi
 if [ "$what" = force ] || [ "$what" = all ]; then
     pmc force 0 python3 /root/repo/tools/bench_force.py 64 2 3
     cp $out/pmc_traffic_force.json profiles/r03_pmc_traffic_force.json        # the guided bench line adds the surrogate's bytes (hash-checked)
     ktrace force python3 /root/repo/tools/bench_force.py 64 2 10
-    python bench.py --workload cfg5g --steps 1 --warmup 1 > $out/bench_cfg5g.json 2> $out/bench_cfg5g.err; cut -c1-200 $out/bench_cfg5g.json
+    python bench.py --full --workload cfg5g --steps 1 --warmup 1 > $out/bench_cfg5g.json 2> $out/bench_cfg5g.err; cut -c1-200 $out/bench_cfg5g.json
 fi

@@ -42,7 +42,7 @@ if [ "$what" = phases ] || [ "$what" = all ]; then
     done
 fi
 if [ "$what" = bench ] || [ "$what" = all ]; then
-    python bench.py > $out/r05_bench_default.json 2> $out/bench_default.err; cut -c1-400 $out/r05_bench_default.json
+    python bench.py --full > $out/r05_bench_default.json 2> $out/bench_default.err; cut -c1-400 $out/r05_bench_default.json
     python - <<'PY'
 import json
 l = json.load(open("/root/repo/gpurun_out/meas5/r05_bench_default.json"))
