@@ -61,30 +61,21 @@ static std::atomic<int> g_generation{0};
 
 // ============================================================================ TemporalUnet1D
 
-struct Param {
-    std::string name;
-    std::vector<int64_t> shape;
-    size_t numel = 0;
-    std::vector<float> host;
-    bool set = false;
-};
+#include "handle_core.inc"
 
 struct Packed { size_t off = 0; size_t sz = 0; int T = 0, CinP = 0, Npad = 0, N = 0, KC = 32; size_t bias_off = 0; bool has_bias = false; bool h3 = false; };
 
 struct RtbDesc { std::string p; int cin, cout; int tb_off; };
 
-struct cindm_unet1d {
+struct cindm_unet1d : ModelCore {
     const cindm::ComposeArgs* fuse_upd = nullptr;   // set by run_step around one forward: ups_last_kernel also runs this update
     bool fused_done = false;                          // ... and reports here that it did
     int issued = 0;                                   // kernels the last cindm_unet1d_forward actually launched (the plan's `launches` counts the epoch
                                                       // launch of a bare forward, which a sample loop's step does not issue: its predecessor advanced the epoch)
     int gatherB = 0, gather_cs = 0, gather_Ltot = 0;  // set by run_step around one forward: x is the sampler's state, level0_down_kernel reads its windows in place
     cindm_unet1d_desc d;
-    std::vector<Param> params;
-    std::unordered_map<std::string, int> index;
     std::vector<int> dims;                 // [F, dim*m0, ...]
     int n_plain = 1;                       // number of trailing levels without down-sampling (:550-555)
-    std::vector<float> sinus;              // [T, dim]
     // device
     float* blob = nullptr;                 // packed weights / biases / norm vectors
     size_t blob_floats = 0;
@@ -93,17 +84,11 @@ struct cindm_unet1d {
     float* ttable = nullptr;               // [T, tb_ld] per-timestep, per-RTB bias (Mish->Linear of temb)
     int tb_ld = 0;
     std::unordered_map<std::string, int> tb_off;        // RTB prefix -> column offset
-    bool finalized = false;
     bool use_h3 = true;                    // k=5 convolutions on the fp16 matrix cores (3-term split); CINDM_MFMA=f32 disables
-    bool use_local_gn = true;              // producer-side GroupNorm + Mish where groups are tile-local (CINDM_LOCAL_GN=0 disables)
-    bool use_wide_qkv = true;              // shallow-level qkv projections on conv1x1_wide_kernel (CINDM_WIDE_QKV=0 disables)
-    bool use_attn_site = true;             // one launch per attention site, attn1d_site_kernel (CINDM_ATTN_SITE=0 disables)
     bool level0_ok = false;                // level0_down_kernel operands packed (dim 64, F <= 32, attention, down-sampling)
     bool level1_ok = false;                // level1_down_kernel operands packed (64 -> 128)
     bool ups_last_ok = false;              // ups_last_kernel operands packed
     bool ups_tail_ok = false;              // ups_tail128_kernel operands packed
-    bool use_level0 = true;                // the finest down level in one launch, level0_down_kernel (CINDM_LEVEL0=0 disables)
-    bool use_h3_resample = true;           // stride-2 / transposed resampling convolutions on the split-fp16 kernel (CINDM_H3_RESAMPLE=0 disables)
     int launches = 0;
     struct WReg { size_t off[PF_REGIONS]; unsigned bytes[PF_REGIONS]; unsigned stride[PF_REGIONS]; };      // byte offsets into blob
     std::vector<WReg> pf_table;            // per launch of one forward: the weights it streams (L2 warm-up of its predecessor)
@@ -128,21 +113,11 @@ struct cindm_unet1d {
     // phase clocks (profiling builds): [slot][PH_MAXWG][PH_MAXWAVE][PH_NST] uint64, armed by cindm_unet1d_phase_prof_enable
     unsigned long long* ph_buf = nullptr; int ph_on = 0;
     std::vector<std::string> ph_names;     // kernel of each launch slot of the last emitted forward
-    // kernel-path options (cindm_unet1d_set_option; defaults = the fast path, overridable by CINDM_* at create)
-    std::map<std::string, int> opt;
-    int O(const char* k) const { auto it = opt.find(k); return it == opt.end() ? 0 : it->second; }
     // taps of the last forward
     struct Tap { size_t off; int L, C, ld; };
     std::unordered_map<std::string, Tap> taps;
     int64_t taps_rows = 0;
 };
-
-static void add_param(cindm_unet1d* h, const std::string& n, std::vector<int64_t> s) {
-    Param p; p.name = n; p.shape = s; p.numel = 1;
-    for (auto v : s) p.numel *= (size_t)v;
-    h->index[n] = (int)h->params.size();
-    h->params.push_back(std::move(p));
-}
 
 // State-dict manifest in the reference's registration order (time_mlp, downs, ups, mid_*, final_conv).
 static int build_manifest(cindm_unet1d* h) {
@@ -156,11 +131,11 @@ static int build_manifest(cindm_unet1d* h) {
     else if (d.horizon % 4 == 0) h->n_plain = 2;
     else if (d.horizon % 2 == 0) h->n_plain = 3;
     else return fail("horizon must be even (model/diffusion_1d.py:550-555)");
-    auto lin = [&](const std::string& p, int i, int o) { add_param(h, p + ".weight", {o, i}); add_param(h, p + ".bias", {o}); };
-    auto conv = [&](const std::string& p, int i, int o, int k) { add_param(h, p + ".weight", {o, i, k}); add_param(h, p + ".bias", {o}); };
+    auto lin = [&](const std::string& p, int i, int o) { h->add_param(p + ".weight", {o, i}); h->add_param(p + ".bias", {o}); };
+    auto conv = [&](const std::string& p, int i, int o, int k) { h->add_param(p + ".weight", {o, i, k}); h->add_param(p + ".bias", {o}); };
     auto cblock = [&](const std::string& p, int i, int o) {
         conv(p + ".block.0", i, o, 5);
-        add_param(h, p + ".block.2.weight", {o}); add_param(h, p + ".block.2.bias", {o});
+        h->add_param(p + ".block.2.weight", {o}); h->add_param(p + ".block.2.bias", {o});
     };
     auto rtb = [&](const std::string& p, int i, int o) {
         cblock(p + ".blocks.0", i, o); cblock(p + ".blocks.1", o, o);
@@ -168,9 +143,9 @@ static int build_manifest(cindm_unet1d* h) {
         if (i != o) conv(p + ".residual_conv", i, o, 1);
     };
     auto attn = [&](const std::string& p, int c) {
-        add_param(h, p + ".fn.fn.to_qkv.weight", {384, c, 1});
+        h->add_param(p + ".fn.fn.to_qkv.weight", {384, c, 1});
         conv(p + ".fn.fn.to_out", 128, c, 1);
-        add_param(h, p + ".fn.norm.g", {1, c, 1});
+        h->add_param(p + ".fn.norm.g", {1, c, 1});
     };
     lin("time_mlp.1", dim, dim * 4);
     lin("time_mlp.3", dim * 4, dim);
@@ -187,7 +162,7 @@ static int build_manifest(cindm_unet1d* h) {
         const std::string p = "ups." + std::to_string(ind);
         rtb(p + ".0", co * 2, co); rtb(p + ".1", co, ci);
         if (d.attention) attn(p + ".2", ci);
-        if (ind >= h->n_plain - 1) { add_param(h, p + ".3.conv.weight", {ci, ci, 4}); add_param(h, p + ".3.conv.bias", {ci}); }
+        if (ind >= h->n_plain - 1) { h->add_param(p + ".3.conv.weight", {ci, ci, 4}); h->add_param(p + ".3.conv.bias", {ci}); }
     }
     const int mid = h->dims[nres];
     rtb("mid_block1", mid, mid);
@@ -198,69 +173,46 @@ static int build_manifest(cindm_unet1d* h) {
     return 0;
 }
 
-// Option keys, defaults and the environment variables that override the defaults at create (ablation scripts):
-// every alternative kernel path is selectable per handle so the parity suite can run each of them in one process.
-struct OptDef { const char* key; int def; const char* env; };
+// Option keys, defaults, the environment variables that override the defaults at create (ablation scripts) and kinds
+// (handle_core.inc): every alternative kernel path is selectable per handle so the parity suite can run each of them in one process.
 static const OptDef kUnet1dOpts[] = {
-    {"mfma_f32", 0, nullptr},          // 1: every product on the exact fp32 MFMA kernels (CINDM_MFMA=f32)
-    {"local_gn", 1, "CINDM_LOCAL_GN"}, // producer-side GroupNorm + Mish, block tails folded into launch B
-    {"attn_site", 1, "CINDM_ATTN_SITE"},   // one launch per attention site
-    {"level0", 1, "CINDM_LEVEL0"},     // level kernels (master switch)
-    {"level1", 1, "CINDM_LEVEL1"},     // level1_down_kernel: samples per workgroup (0 = off, 1, 2)
-    {"ups_last", 1, "CINDM_UPS_LAST"},
-    {"ups_tail", 1, "CINDM_UPS_TAIL"},
-    {"attn_head", 1, "CINDM_ATTN_HEAD"},   // deep attention sites with the heads split over workgroups (attn1d_head_kernel)
-    {"dconv", 1, "CINDM_DCONV"},       // deep-level k=5 convolutions on dconv_kernel (LDS-resident activation planes)
-    {"ws_alias", 1, "CINDM_WS_ALIAS"}, // sampling path (taps = 0): dead intermediates' workspace blocks are recycled: 0 never, 1 above 320 rows, 2 always
-    {"pingpong", 1, "CINDM_PINGPONG"}, // plain sample loops: step counter / epochs in two slots advanced by the step's update (no step_counter_kernel launch)
-    {"dresample", 2, "CINDM_DRESAMPLE"},   // the resampling convolutions between the deep levels on dresample_kernel: 2 = 16 columns per workgroup, 1 = 32 (0: conv_gemm_h3_kernel<3 | 4>)
-    {"dconv2", 1, "CINDM_DCONV2"},     // a whole deep-level ResidualTemporalBlock per launch (dconv2_kernel: in-launch all-gather between its convolutions)
-    {"l2_prefetch", 1, "CINDM_L2_PREFETCH"},   // launches touch the next launch's weights (L2 warm-up)
-    {"fuse_gather", 1, nullptr},       // time composition of two-body states: level0_down_kernel reads the state's windows in place (no compose_gather_kernel launch)
-    {"fuse_update", 1, "CINDM_FUSE_UPDATE"},   // plain single-model steps: the reverse-step update inside ups_last_kernel (no update launch)
-    {"taps", 0, "CINDM_TAPS"},         // 1: the level kernels also store the block outputs that only cindm_unet1d_tap reads
-    {"recover", 1, nullptr},                   // run-time: 0 = a chain whose exchange timed out is an error instead of an exchange-free re-run
-    {"no_exchange", 0, "CINDM_NO_EXCHANGE"},   // 1: only kernels without an in-launch exchange between workgroups (run-time option: does not un-finalize)
-    {"tune", 0, "CINDM_TUNE"},         // same-box A/B switches (run-time; 0 = the shipped choices): bit 0 = round 5's L2 warm-up placement, regions and issuers, bit 1 = round 5's plain output stores, bits 2 + i = launch i of the forward issues no warm-up (tools/pf_mask_scan.py)
-    {"stress", 0, "CINDM_STRESS"},     // > 0 (a seed): pseudo-random pauses before the in-kernel hand-overs (dconv pair exchange, attention heads)
-    {"auto_range", 1, "CINDM_AUTO_RANGE"}, // per-layer fall-back to the fp32 MFMA kernels when weights leave the fp16-safe window
-    {"range_fallback", 0, nullptr},    // (read-only) 1 after finalize when a weight left the split-fp16 window: fp32 kernels in use
-    {"dbg", 0, "CINDM_DBG"},           // timing ablations / forced time-outs (wrong results)
+    {"mfma_f32", 0, nullptr, OPT_PACK},          // 1: every product on the exact fp32 MFMA kernels (CINDM_MFMA=f32)
+    {"local_gn", 1, "CINDM_LOCAL_GN", OPT_PACK}, // producer-side GroupNorm + Mish, block tails folded into launch B
+    {"attn_site", 1, "CINDM_ATTN_SITE", OPT_PACK},   // one launch per attention site
+    {"level0", 1, "CINDM_LEVEL0", OPT_PACK},     // level kernels (master switch)
+    {"level1", 1, "CINDM_LEVEL1", OPT_PACK},     // level1_down_kernel: samples per workgroup (0 = off, 1, 2)
+    {"ups_last", 1, "CINDM_UPS_LAST", OPT_PACK},
+    {"ups_tail", 1, "CINDM_UPS_TAIL", OPT_PACK},
+    {"attn_head", 1, "CINDM_ATTN_HEAD", OPT_PACK},   // deep attention sites with the heads split over workgroups (attn1d_head_kernel)
+    {"dconv", 1, "CINDM_DCONV", OPT_PACK},       // deep-level k=5 convolutions on dconv_kernel (LDS-resident activation planes)
+    {"ws_alias", 1, "CINDM_WS_ALIAS", OPT_PACK}, // sampling path (taps = 0): dead intermediates' workspace blocks are recycled: 0 never, 1 above 320 rows, 2 always
+    {"pingpong", 1, "CINDM_PINGPONG", OPT_PACK}, // plain sample loops: step counter / epochs in two slots advanced by the step's update (no step_counter_kernel launch)
+    {"dresample", 2, "CINDM_DRESAMPLE", OPT_PACK},   // the resampling convolutions between the deep levels on dresample_kernel: 2 = 16 columns per workgroup, 1 = 32 (0: conv_gemm_h3_kernel<3 | 4>)
+    {"dconv2", 1, "CINDM_DCONV2", OPT_PACK},     // a whole deep-level ResidualTemporalBlock per launch (dconv2_kernel: in-launch all-gather between its convolutions)
+    {"l2_prefetch", 1, "CINDM_L2_PREFETCH", OPT_PACK},   // launches touch the next launch's weights (L2 warm-up)
+    {"fuse_gather", 1, nullptr, OPT_PACK},       // time composition of two-body states: level0_down_kernel reads the state's windows in place (no compose_gather_kernel launch)
+    {"fuse_update", 1, "CINDM_FUSE_UPDATE", OPT_PACK},   // plain single-model steps: the reverse-step update inside ups_last_kernel (no update launch)
+    {"taps", 0, "CINDM_TAPS", OPT_PACK},         // 1: the level kernels also store the block outputs that only cindm_unet1d_tap reads
+    {"recover", 1, nullptr, OPT_RUNTIME},                   // 0 = a chain whose exchange timed out is an error instead of an exchange-free re-run
+    {"no_exchange", 0, "CINDM_NO_EXCHANGE", OPT_RUNTIME},   // 1: only kernels without an in-launch exchange between workgroups
+    {"tune", 0, "CINDM_TUNE", OPT_RUNTIME},         // same-box A/B switches (0 = the shipped choices): bit 0 = round 5's L2 warm-up placement, regions and issuers, bit 1 = round 5's plain output stores, bits 2 + i = launch i of the forward issues no warm-up (tools/pf_mask_scan.py)
+    {"stress", 0, "CINDM_STRESS", OPT_PACK},     // > 0 (a seed): pseudo-random pauses before the in-kernel hand-overs (dconv pair exchange, attention heads)
+    {"auto_range", 1, "CINDM_AUTO_RANGE", OPT_PACK}, // per-layer fall-back to the fp32 MFMA kernels when weights leave the fp16-safe window
+    {"range_fallback", 0, nullptr, OPT_READONLY},    // 1 after finalize when a weight left the split-fp16 window: fp32 kernels in use
+    {"dbg", 0, "CINDM_DBG", OPT_PACK},           // timing ablations / forced time-outs (wrong results)
 };
-static void unet1d_default_options(cindm_unet1d* h) {
-    for (const auto& o : kUnet1dOpts) {
-        int v = o.def;
-        if (o.env) { const char* e = getenv(o.env); if (e) v = atoi(e); }
-        h->opt[o.key] = v;
-    }
-    const char* e = getenv("CINDM_MFMA");
-    if (e && std::strcmp(e, "f32") == 0) h->opt["mfma_f32"] = 1;
-}
 
 static void unet1d_plan(cindm_unet1d* h);
 extern "C" int cindm_unet1d_set_option(cindm_unet1d* h, const char* key, int32_t value) {
-    REQUIRE(h && key, "null argument");
-    auto it = h->opt.find(key);
-    if (it == h->opt.end()) return fail(std::string("unknown option: ") + key);
-    if (it->second != value) {
-        it->second = value;
-        // "no_exchange" only selects among kernels whose operands are all packed already: the handle stays finalized
-        if (std::strcmp(key, "no_exchange") != 0 && std::strcmp(key, "tune") != 0 && std::strcmp(key, "recover") != 0) h->finalized = false;
-        else {
-            h->generation = ++g_generation;         // (captured steps embed the switch: never replay an older capture)
-            if (std::strcmp(key, "tune") == 0 && h->finalized) unet1d_plan(h);      // (a tune bit may change what a launch registers for the warm-up)
-        }
+    const int rc = core_set_option(h, key, value);
+    if (rc == 1) {
+        h->generation = ++g_generation;         // (captured steps embed the run-time switches: never replay an older capture)
+        if (std::string(key) == "tune" && h->finalized) unet1d_plan(h);      // (a tune bit may change what a launch registers for the warm-up)
     }
-    return 0;
+    return rc < 0 ? -1 : 0;
 }
 
-extern "C" int cindm_unet1d_get_option(const cindm_unet1d* h, const char* key, int32_t* value) {
-    REQUIRE(h && key && value, "null argument");
-    auto it = h->opt.find(key);
-    if (it == h->opt.end()) return fail(std::string("unknown option: ") + key);
-    *value = it->second;
-    return 0;
-}
+extern "C" int cindm_unet1d_get_option(const cindm_unet1d* h, const char* key, int32_t* value) { return core_get_option(h, key, value); }
 
 extern "C" int cindm_unet1d_create(const cindm_unet1d_desc* desc, cindm_unet1d** out) {
     REQUIRE(desc && out, "null argument");
@@ -274,7 +226,7 @@ extern "C" int cindm_unet1d_create(const cindm_unet1d_desc* desc, cindm_unet1d**
     REQUIRE(desc->timesteps >= 1, "timesteps must be >= 1");
     auto* h = new cindm_unet1d();
     h->d = *desc;
-    unet1d_default_options(h);
+    h->init_options(kUnet1dOpts);
     if (build_manifest(h) != 0) { delete h; return -1; }
     // every internal length must stay integral
     int L = desc->horizon;
@@ -295,37 +247,15 @@ extern "C" void cindm_unet1d_destroy(cindm_unet1d* h) {
     delete h;
 }
 
-extern "C" int cindm_unet1d_num_params(const cindm_unet1d* h) { return h ? (int)h->params.size() : fail("null handle"); }
-
+extern "C" int cindm_unet1d_num_params(const cindm_unet1d* h) { return core_num_params(h); }
 extern "C" int cindm_unet1d_param_info(const cindm_unet1d* h, int idx, char* name, int cap, int64_t shape[4], int* ndim) {
-    REQUIRE(h && idx >= 0 && idx < (int)h->params.size(), "bad param index");
-    const Param& p = h->params[idx];
-    if (name && cap > 0) { std::strncpy(name, p.name.c_str(), cap - 1); name[cap - 1] = 0; }
-    for (int i = 0; i < 4; ++i) shape[i] = i < (int)p.shape.size() ? p.shape[i] : 1;
-    if (ndim) *ndim = (int)p.shape.size();
-    return 0;
+    return core_param_info(h, idx, name, cap, shape, ndim);
 }
-
 extern "C" int cindm_unet1d_set_param(cindm_unet1d* h, const char* key, const float* src, int64_t numel, int on_device) {
-    REQUIRE(h && key && src, "null argument");
-    auto it = h->index.find(key);
-    if (it == h->index.end()) return fail(std::string("unexpected key in state_dict: ") + key);
-    Param& p = h->params[it->second];
-    if ((int64_t)p.numel != numel) return fail(std::string("size mismatch for ") + key);
-    p.host.resize(p.numel);
-    if (on_device) HIPCHK(hipMemcpy(p.host.data(), src, p.numel * sizeof(float), hipMemcpyDeviceToHost));
-    else std::memcpy(p.host.data(), src, p.numel * sizeof(float));
-    p.set = true;
-    h->finalized = false;
-    return 0;
+    return core_set_param(h, key, src, numel, on_device);
 }
-
 extern "C" int cindm_unet1d_set_sinusoid_table(cindm_unet1d* h, const float* t, int64_t numel) {
-    REQUIRE(h && t, "null argument");
-    REQUIRE(numel == (int64_t)h->d.timesteps * h->d.dim, "sinusoid table must be [timesteps, dim]");
-    h->sinus.assign(t, t + numel);
-    h->finalized = false;
-    return 0;
+    return core_set_sinusoid(h, t, numel, h ? (int64_t)h->d.timesteps * h->d.dim : 0);
 }
 
 // ---- weight packing ([tap][CinP][Npad], zero padded) -------------------------------------------
@@ -579,7 +509,7 @@ static void pack_weight(cindm_unet1d* h, BlobBuilder& bb, const std::string& pre
     else if (kind == 1) { Ci = (int)w.shape[0]; Co = (int)w.shape[1]; K = (int)w.shape[2]; }
     else { Co = (int)w.shape[0]; Ci = (int)w.shape[1]; K = 1; }
     if (kind == 0 && K == 5 && h->use_h3) { pack_weight_h3(h, bb, prefix, split); return; }
-    if (h->use_h3 && h->use_h3_resample && ((kind == 0 && K == 3) || (kind == 1 && K == 4))) { pack_weight_h3(h, bb, prefix, split, kind); return; }
+    if (h->use_h3 && ((kind == 0 && K == 3) || (kind == 1 && K == 4))) { pack_weight_h3(h, bb, prefix, split, kind); return; }
     const int C0 = split ? split : Ci, C1 = Ci - C0;
     // stage width: tap-ful convolutions stage 32 channels x T taps; 1x1 layers stage 64 or 128 channels
     const int KC = (K > 1) ? 32 : ((C0 % 128 == 0 && C1 % 128 == 0) ? 128 : 64);
@@ -927,7 +857,7 @@ static void dconv_launch(Emitter& E, int L, int k0, int k1, bool res, const Dcon
 }
 
 static bool dconv_applicable(cindm_unet1d* h, const std::string& p, const Ten& x0, const Ten* x1, int cout) {
-    if (!h->O("dconv") || !h->use_h3 || !h->use_local_gn) return false;
+    if (!h->O("dconv") || !h->use_h3 || !h->O("local_gn")) return false;
     const int L = x0.L, gw = cout / 8;
     if ((L != 3 && L != 6) || cout % 32 || (gw != 16 && gw != 32 && gw != 64)) return false;
     if (gw == 64 && ((cout / 32) % 2 || h->NX())) return false;
@@ -1112,7 +1042,7 @@ static Ten emit_rtb(Emitter& E, const std::string& p, const Ten& x0, const Ten* 
     float* st1 = E.tmp((size_t)Bp * 8 * Pn * 2, k1);
     GemmArgs a;
     // GroupNorm groups inside one 32-column tile (cout <= 256): the producers normalise + activate their own output
-    const bool local_gn = gw <= TN && h->use_local_gn;
+    const bool local_gn = gw <= TN && h->O("local_gn");
     auto rc = h->packed.find(p + ".residual_conv");
     const bool identity = rc == h->packed.end();
     // the 1x1 residual_conv rides on launch A's centre tap (split-fp16 kernel only): r = Wr . x + br
@@ -1685,26 +1615,17 @@ static int unet1d_finalize_pack(cindm_unet1d* h, void* stream_) {
     }
     BlobBuilder bb;
     h->use_h3 = !h->O("mfma_f32") && !h->force_f32;
-    // Range rule of the split-fp16 products (hi = fp16(w), lo = fp16((w - hi) * 2^11)): every element of a weight
-    // tensor is represented to 2^-24 of the tensor's largest magnitude M as long as 2^-12 <= M <= 2^15 (below, hi and lo
-    // fall into fp16's subnormals together; above, hi overflows).  A checkpoint with a conv / projection weight outside
-    // that window runs on the exact fp32 MFMA kernels instead ("range_fallback" reads 1); "auto_range" = 0 disables
-    // the check.  Activations need no rule: they are GroupNorm / LayerNorm outputs of O(gamma), and an input beyond
-    // 65504 shows up as inf / nan in the output rather than as a silent loss.
+    // Range rule of the split-fp16 products: a checkpoint with a conv / projection weight outside the window of
+    // max_abs_in_fp16_window runs on the exact fp32 MFMA kernels instead ("range_fallback" reads 1); "auto_range" = 0
+    // disables the check.  Activations need no rule: they are GroupNorm / LayerNorm outputs of O(gamma), and an input
+    // beyond 65504 shows up as inf / nan in the output rather than as a silent loss.
     h->opt["range_fallback"] = h->force_f32 ? (h->force_reason ? h->force_reason : 2) : 0;
     if (h->use_h3 && h->O("auto_range")) {
         for (const auto& p : h->params) {
             if (p.shape.size() < 2 || p.name.find("time_mlp") != std::string::npos) continue;      // time path: fp32 kernels at finalize
-            float M = 0.f;
-            for (float v : p.host) M = std::max(M, std::fabs(v));
-            if (M > 32768.0f || (M < 1.0f / 4096.0f && M > 0.f) || !(M == M)) { h->use_h3 = false; h->opt["range_fallback"] = 1; break; }
+            if (!max_abs_in_fp16_window(p)) { h->use_h3 = false; h->opt["range_fallback"] = 1; break; }
         }
     }
-    h->use_local_gn = h->O("local_gn") != 0;
-    h->use_wide_qkv = true;
-    h->use_attn_site = h->O("attn_site") != 0;
-    h->use_level0 = h->O("level0") != 0;
-    h->use_h3_resample = true;
     h->packed.clear(); h->vec_off.clear(); h->tb_off.clear();
     std::vector<RtbDesc> rtbs;
     int tb_ld = 0;
@@ -1719,13 +1640,13 @@ static int unet1d_finalize_pack(cindm_unet1d* h, void* stream_) {
         } else if (ends(".residual_conv.weight")) {
             int split = (k.rfind("ups.", 0) == 0 && k.find(".0.residual_conv") != std::string::npos) ? (int)p.shape[1] / 2 : 0;
             pack_weight(h, bb, k.substr(0, k.size() - 7), 0, split);
-            if (h->use_h3 && h->use_local_gn) pack_weight_h3_res(h, bb, k.substr(0, k.size() - 7), split);
+            if (h->use_h3 && h->O("local_gn")) pack_weight_h3_res(h, bb, k.substr(0, k.size() - 7), split);
         } else if (ends(".3.conv.weight")) {
             pack_weight(h, bb, k.substr(0, k.size() - 7), k.rfind("ups.", 0) == 0 ? 1 : 0, 0);
         } else if (ends("to_qkv.weight") || ends("to_out.weight") || k == "final_conv.1.weight") {
             pack_weight(h, bb, k.substr(0, k.size() - 7), 0, 0);
-            if (ends("to_qkv.weight") && h->use_wide_qkv) pack_weight_wide(h, bb, k.substr(0, k.size() - 7));
-            if (ends("to_out.weight") && h->use_attn_site) pack_attn_site(h, bb, k.substr(0, k.size() - std::strlen(".to_out.weight")));
+            if (ends("to_qkv.weight")) pack_weight_wide(h, bb, k.substr(0, k.size() - 7));
+            if (ends("to_out.weight") && h->O("attn_site")) pack_attn_site(h, bb, k.substr(0, k.size() - std::strlen(".to_out.weight")));
         } else if (ends("time_mlp.1.weight") || k == "time_mlp.3.weight") {
             pack_weight(h, bb, k.substr(0, k.size() - 7), 2, 0);
             if (k != "time_mlp.1.weight" && k != "time_mlp.3.weight") {
@@ -1740,7 +1661,7 @@ static int unet1d_finalize_pack(cindm_unet1d* h, void* stream_) {
     }
     h->tb_ld = tb_ld;
     h->level0_ok = false; h->level1_ok = false; h->ups_last_ok = false; h->ups_tail_ok = false;
-    if (h->use_h3 && h->use_attn_site && h->use_level0 && h->use_local_gn) pack_level0(h, bb);
+    if (h->use_h3 && h->O("attn_site") && h->O("level0") && h->O("local_gn")) pack_level0(h, bb);
     if (getenv("CINDM_VERBOSE")) fprintf(stderr, "[cindm] fused levels: level0 %d level1 %d ups_last %d\n", (int)h->level0_ok, (int)h->level1_ok, (int)h->ups_last_ok + 2 * (int)h->ups_tail_ok);
     if (h->blob) { (void)hipFree(h->blob); h->blob = nullptr; }
     if (h->ttable) { (void)hipFree(h->ttable); h->ttable = nullptr; }
@@ -1788,39 +1709,52 @@ extern "C" int cindm_unet1d_forward(cindm_unet1d* h, const float* x, int32_t t, 
                                     float* eps, int64_t rows, void* ws, size_t ws_bytes, void* stream);
 static int unet1d_check_flag(cindm_unet1d* h, hipStream_t stream);
 
+// The synthetic calibration batch of the range rule (both U-Nets): `n` elements of a unit-variance bell (sum of four uniforms,
+// |v| < 3.5) drawn from `seed`, zero in the padding channels (element i is data when i % CP < C); fwd(t, x, eps, ws) runs one
+// forward per timestep in {0, T/2, T-1}.  *finite = false when a forward failed or an eps element is inf / nan.
+template <typename Fwd>
+static int calibrate_at_finalize(size_t n, int C, int CP, uint32_t seed, int T, size_t wsb, hipStream_t stream, Fwd fwd, bool* finite) {
+    std::vector<float> hx(n, 0.f), he(n);
+    uint32_t st = seed;
+    for (size_t i = 0; i < n; ++i) {
+        if ((int)(i % CP) >= C) continue;
+        float a = 0.f;
+        for (int k = 0; k < 4; ++k) { st = st * 1664525u + 1013904223u; a += (float)(st >> 8) * (1.0f / 16777216.0f) - 0.5f; }
+        hx[i] = a * 1.7320508f;
+    }
+    float *dx = nullptr, *de = nullptr; void* ws = nullptr;
+    HIPCHK(hipMalloc((void**)&dx, n * 4)); HIPCHK(hipMalloc((void**)&de, n * 4)); HIPCHK(hipMalloc(&ws, wsb));
+    HIPCHK(hipMemcpyAsync(dx, hx.data(), n * 4, hipMemcpyHostToDevice, stream));
+    *finite = true;
+    for (int t : {0, T / 2, T - 1}) {
+        if (fwd(t, dx, de, ws) != 0) { *finite = false; break; }
+        HIPCHK(hipMemcpyAsync(he.data(), de, n * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        for (float v : he) if (!std::isfinite(v)) { *finite = false; break; }
+        if (!*finite) break;
+    }
+    (void)hipFree(dx); (void)hipFree(de); (void)hipFree(ws);
+    return 0;
+}
+
 // Repack + time tables (unet1d_finalize_pack), then -- on the split-fp16 kernels with "auto_range" -- ONE calibration
 // forward per timestep in {0, T/2, T-1} on a fixed unit-scale batch: an activation that leaves fp16's exponent range
 // (large un-normalised residual streams, huge projection weights) shows up as inf / nan in eps, and the handle is
 // repacked for the exact fp32 MFMA kernels ("range_fallback" reads 2; 1 = the weight-window rule fired).
+// A handle that is finalized already (nothing changed since its last finalize) returns at once.
 extern "C" int cindm_unet1d_finalize(cindm_unet1d* h, void* stream_) {
     REQUIRE(h, "null handle");
+    if (h->finalized) return 0;
     h->force_f32 = false; h->force_reason = 0;
     if (unet1d_finalize_pack(h, stream_) != 0) return -1;
     if (!h->use_h3 || !h->O("auto_range")) return 0;
     hipStream_t stream = (hipStream_t)stream_;
     const int64_t rows = 4;
-    const size_t n = (size_t)rows * h->d.horizon * h->d.transition_dim;
-    std::vector<float> hx(n), he(n);
-    uint32_t st = 0x2545F491u;
-    for (auto& v : hx) {                       // sum of four uniforms: unit-variance bell, |v| < 3.5
-        float a = 0.f;
-        for (int k = 0; k < 4; ++k) { st = st * 1664525u + 1013904223u; a += (float)(st >> 8) * (1.0f / 16777216.0f) - 0.5f; }
-        v = a * 1.7320508f;
-    }
+    const int F = h->d.transition_dim;
     const size_t wsb = cindm_unet1d_workspace_bytes(h, rows);
-    float *dx = nullptr, *de = nullptr; void* ws = nullptr;
-    HIPCHK(hipMalloc((void**)&dx, n * 4)); HIPCHK(hipMalloc((void**)&de, n * 4)); HIPCHK(hipMalloc(&ws, wsb));
-    HIPCHK(hipMemcpyAsync(dx, hx.data(), n * 4, hipMemcpyHostToDevice, stream));
+    auto fwd = [&](int t, const float* x, float* eps, void* ws) { return cindm_unet1d_forward(h, x, t, nullptr, eps, rows, ws, wsb, stream_); };
     bool finite = true;
-    const int T = h->d.timesteps;
-    for (int t : {0, T / 2, T - 1}) {
-        if (cindm_unet1d_forward(h, dx, t, nullptr, de, rows, ws, wsb, stream_) != 0) { finite = false; break; }
-        HIPCHK(hipMemcpyAsync(he.data(), de, n * 4, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        for (float v : he) if (!std::isfinite(v)) { finite = false; break; }
-        if (!finite) break;
-    }
-    (void)hipFree(dx); (void)hipFree(de); (void)hipFree(ws);
+    if (calibrate_at_finalize((size_t)rows * h->d.horizon * F, F, F, 0x2545F491u, h->d.timesteps, wsb, stream, fwd, &finite) != 0) return -1;
     h->seen_ws = nullptr; h->seen_rows = 0; h->taps.clear();
     if (unet1d_check_flag(h, stream) != 0) return -1;      // a calibration forward whose exchange timed out proves nothing
     if (!finite) {

@@ -11,41 +11,37 @@
 
 struct FuPacked { size_t off = 0, off_b = 0, bias = 0, off_h3 = 0, off_h3b = 0, off_sb = 0, off_sf3 = 0, off_sb3 = 0; bool has_bias = false, h3 = false, stem_b = false, unshuf = false; int KS = 1, Cin = 0, Cout = 0, CinP = 0, CoutP = 0, NB = 4, CinPb = 0, CoutPb = 0, NBb = 4; };
 
-struct cindm_forceunet {
+struct cindm_forceunet : ModelCore {
     cindm_forceunet_desc d;
-    std::vector<Param> params;
-    std::unordered_map<std::string, int> index;
     std::vector<int> dims;
     float* blob = nullptr;
     std::unordered_map<std::string, FuPacked> conv;
     std::unordered_map<std::string, size_t> vec;
-    bool finalized = false;
     bool fwd_h3 = true;      // forward 3x3 convolutions on the diffusion path's persistent split-fp16 kernel (option "h3" = 0 / range fallback: off)
     bool bwd_h3 = true;      // ... and the input-gradient ones behind a GroupNorm, scaled by the gradient's maximum (option "h3_bwd" = 0: off)
     unsigned* err_dev = nullptr;       // raised by a timed-out exchange of fu_gn_silu_bwd_cluster_kernel (cindm_forceunet_status)
     int nx_force = 0;                  // the exchange-free re-run of a chain / gradient call is in progress
     int recovered = 0;                 // chains / calls re-run on the exchange-free derivative after a time-out
-    // kernel-path options (cindm_forceunet_set_option), as on the U-Net handles: "h3", "h3_bwd" select the split-fp16
-    // convolutions (1, default) or the exact fp32-MFMA kernel (0); "auto_range" (1) = calibration forward at finalize;
-    // "range_fallback" (read-only) = 1 when that calibration switched the forward convolutions to fp32
-    // "la_fused" (1): LinearAttention sites of 64 / 128 channels without q | k | v tensors (forceunet_la.h); 0 = the layer-by-layer path
-    // "gn_bwd_fused": GroupNorm + SiLU derivative in one register-resident pass instead of reduce + apply: 1 = workgroup per (image, group),
-    // 2 (default) = workgroup per (image, slab of pixels) with whole rows, partial sums exchanged between the image's workgroups
-    std::map<std::string, int> opt{{"h3", 1}, {"h3_bwd", 1}, {"auto_range", 1}, {"range_fallback", 0}, {"stress", 0}, {"la_fused", 1}, {"gn_bwd_fused", 2}, {"ws_nosplit", 2},
-                                    {"no_exchange", 0},      // run-time: 1 = no kernel that waits for another workgroup (gn_bwd_fused behaves as 1)
-                                    {"recover", 1},          // 0: a timed-out exchange is an error instead of an exchange-free re-run
-                                    {"dbg", 0}};             // 39: force the exchange time-out (tests)
-    int O(const char* k) const { auto it = opt.find(k); return it == opt.end() ? 0 : it->second; }
 };
 
-extern "C" int cindm_forceunet_set_option(cindm_forceunet* h, const char* key, int32_t value) {
-    REQUIRE(h && key, "null argument");
-    auto it = h->opt.find(key);
-    if (it == h->opt.end() || std::strcmp(key, "range_fallback") == 0) return fail(std::string("unknown option: ") + key);
-    const bool runtime = std::strcmp(key, "no_exchange") == 0 || std::strcmp(key, "recover") == 0 || std::strcmp(key, "dbg") == 0 || std::strcmp(key, "stress") == 0;
-    if (it->second != value) { it->second = value; if (!runtime) h->finalized = false; }
-    return 0;
-}
+// kernel-path options (cindm_forceunet_set_option), as on the U-Net handles
+static const OptDef kForceUnetOpts[] = {
+    {"h3", 1, nullptr, OPT_PACK},             // forward 3x3 convolutions on the split-fp16 kernel (1) or the exact fp32-MFMA kernel (0)
+    {"h3_bwd", 1, nullptr, OPT_PACK},         // ... the input-gradient ones
+    {"auto_range", 1, nullptr, OPT_PACK},     // calibration forward at finalize
+    {"range_fallback", 0, nullptr, OPT_READONLY},   // 1 when the range rule switched the forward convolutions to fp32
+    {"stress", 0, nullptr, OPT_RUNTIME},      // > 0 (a seed): pseudo-random pauses before the in-kernel hand-overs (race tests)
+    {"la_fused", 1, nullptr, OPT_PACK},       // LinearAttention sites of 64 / 128 channels without q | k | v tensors (forceunet_la.h); 0 = layer by layer
+    // GroupNorm + SiLU derivative in one register-resident pass instead of reduce + apply: 1 = workgroup per (image, group),
+    // 2 = workgroup per (image, slab of pixels) with whole rows, partial sums exchanged between the image's workgroups
+    {"gn_bwd_fused", 2, nullptr, OPT_PACK},
+    {"ws_nosplit", 2, nullptr, OPT_PACK},     // conv2d_ws_kernel: K of a chunk not split over the matrix waves (as on the 2-D U-Net)
+    {"no_exchange", 0, nullptr, OPT_RUNTIME}, // 1 = no kernel that waits for another workgroup (gn_bwd_fused behaves as 1)
+    {"recover", 1, nullptr, OPT_RUNTIME},     // 0: a timed-out exchange is an error instead of an exchange-free re-run
+    {"dbg", 0, nullptr, OPT_RUNTIME},         // 39: force the exchange time-out (tests)
+};
+
+extern "C" int cindm_forceunet_set_option(cindm_forceunet* h, const char* key, int32_t value) { return core_set_option(h, key, value) < 0 ? -1 : 0; }
 
 // 1 when an in-kernel exchange of this handle timed out since the last call (the flag is cleared), 0 otherwise, -1 on error.
 // Synchronises `stream`.
@@ -60,20 +56,7 @@ extern "C" int cindm_forceunet_status(cindm_forceunet* h, void* stream) {
 }
 extern "C" int cindm_forceunet_recovered(const cindm_forceunet* h) { return h ? h->recovered : 0; }
 
-extern "C" int cindm_forceunet_get_option(const cindm_forceunet* h, const char* key, int32_t* value) {
-    REQUIRE(h && key && value, "null argument");
-    auto it = h->opt.find(key);
-    if (it == h->opt.end()) return fail(std::string("unknown option: ") + key);
-    *value = it->second;
-    return 0;
-}
-
-static void fu_add(cindm_forceunet* h, const std::string& n, std::vector<int64_t> s) {
-    Param p; p.name = n; p.shape = s; p.numel = 1;
-    for (auto v : s) p.numel *= (size_t)v;
-    h->index[n] = (int)h->params.size();
-    h->params.push_back(std::move(p));
-}
+extern "C" int cindm_forceunet_get_option(const cindm_forceunet* h, const char* key, int32_t* value) { return core_get_option(h, key, value); }
 
 extern "C" int cindm_forceunet_create(const cindm_forceunet_desc* desc, cindm_forceunet** out) {
     REQUIRE(desc && out, "null argument");
@@ -96,14 +79,15 @@ extern "C" int cindm_forceunet_create(const cindm_forceunet_desc* desc, cindm_fo
     auto* h = new cindm_forceunet();
     h->d = *desc;
     h->dims = dims;
+    h->init_options(kForceUnetOpts);
     auto conv = [&](const std::string& p, int ci, int co, int k, bool bias = true) {
-        fu_add(h, p + ".weight", {co, ci, k, k});
-        if (bias) fu_add(h, p + ".bias", {co});
+        h->add_param(p + ".weight", {co, ci, k, k});
+        if (bias) h->add_param(p + ".bias", {co});
     };
     auto rb = [&](const std::string& p, int c) {
         for (const char* b : {"block1", "block2"}) {
             conv(p + "." + b + ".proj", c, c, 3);
-            fu_add(h, p + "." + b + ".norm.weight", {c}); fu_add(h, p + "." + b + ".norm.bias", {c});
+            h->add_param(p + "." + b + ".norm.weight", {c}); h->add_param(p + "." + b + ".norm.bias", {c});
         }
     };
     conv("init_conv", desc->channels, dim, 7);
@@ -113,17 +97,17 @@ extern "C" int cindm_forceunet_create(const cindm_forceunet_desc* desc, cindm_fo
         rb(p + ".0", ci); rb(p + ".1", ci);
         conv(p + ".2.fn.fn.to_qkv", ci, 384, 1, false);
         conv(p + ".2.fn.fn.to_out.0", 128, ci, 1);
-        fu_add(h, p + ".2.fn.fn.to_out.1.g", {1, ci, 1, 1});
-        fu_add(h, p + ".2.fn.norm.g", {1, ci, 1, 1});
+        h->add_param(p + ".2.fn.fn.to_out.1.g", {1, ci, 1, 1});
+        h->add_param(p + ".2.fn.norm.g", {1, ci, 1, 1});
         if (ind < n - 1) conv(p + ".3.1", ci * 4, co, 1); else conv(p + ".3", ci, co, 3);
     }
     const int mid = h->dims[n];
     rb("mid_block1", mid);
     conv("mid_attn.fn.fn.to_qkv", mid, 384, 1, false);
     conv("mid_attn.fn.fn.to_out", 128, mid, 1);
-    fu_add(h, "mid_attn.fn.norm.g", {1, mid, 1, 1});
+    h->add_param("mid_attn.fn.norm.g", {1, mid, 1, 1});
     rb("mid_block2", mid);
-    fu_add(h, "final.weight", {2, 512}); fu_add(h, "final.bias", {2});
+    h->add_param("final.weight", {2, 512}); h->add_param("final.bias", {2});
     *out = h;
     return 0;
 }
@@ -133,26 +117,12 @@ extern "C" void cindm_forceunet_destroy(cindm_forceunet* h) {
     if (h->err_dev) (void)hipFree(h->err_dev);
     delete h;
 }
-extern "C" int cindm_forceunet_num_params(const cindm_forceunet* h) { return h ? (int)h->params.size() : fail("null handle"); }
+extern "C" int cindm_forceunet_num_params(const cindm_forceunet* h) { return core_num_params(h); }
 extern "C" int cindm_forceunet_param_info(const cindm_forceunet* h, int idx, char* name, int cap, int64_t shape[4], int* ndim) {
-    REQUIRE(h && idx >= 0 && idx < (int)h->params.size(), "bad param index");
-    const Param& p = h->params[idx];
-    if (name && cap > 0) { std::strncpy(name, p.name.c_str(), cap - 1); name[cap - 1] = 0; }
-    for (int i = 0; i < 4; ++i) shape[i] = i < (int)p.shape.size() ? p.shape[i] : 1;
-    if (ndim) *ndim = (int)p.shape.size();
-    return 0;
+    return core_param_info(h, idx, name, cap, shape, ndim);
 }
 extern "C" int cindm_forceunet_set_param(cindm_forceunet* h, const char* key, const float* src, int64_t numel, int on_device) {
-    REQUIRE(h && key && src, "null argument");
-    auto it = h->index.find(key);
-    if (it == h->index.end()) return fail(std::string("unexpected key in state_dict: ") + key);
-    Param& p = h->params[it->second];
-    if ((int64_t)p.numel != numel) return fail(std::string("size mismatch for ") + key);
-    p.host.resize(p.numel);
-    if (on_device) HIPCHK(hipMemcpy(p.host.data(), src, p.numel * sizeof(float), hipMemcpyDeviceToHost));
-    else std::memcpy(p.host.data(), src, p.numel * sizeof(float));
-    p.set = true; h->finalized = false;
-    return 0;
+    return core_set_param(h, key, src, numel, on_device);
 }
 
 // conv weight [Co][Ci][KS][KS] -> forward fragments Wp[tap][kc][ntq][lane][NB] and the backward-data ones (input <->
@@ -291,7 +261,7 @@ static void fu_pack_conv(cindm_forceunet* h, BlobBuilder& bb, const std::string&
 
 extern "C" int cindm_forceunet_finalize(cindm_forceunet* h, void* stream) {
     REQUIRE(h, "null handle");
-    (void)stream;
+    if (h->finalized) return 0;
     if (!h->err_dev) { HIPCHK(hipMalloc((void**)&h->err_dev, 256)); HIPCHK(hipMemset(h->err_dev, 0, 256)); }
     for (auto& p : h->params) if (!p.set) return fail("missing key in state_dict: " + p.name);
     BlobBuilder bb;
@@ -367,9 +337,7 @@ extern "C" int cindm_forceunet_finalize(cindm_forceunet* h, void* stream) {
         // convolutions to the exact fp32 kernel; the input-gradient ones rescale by the gradient's maximum and need no rule.
         for (const auto& p : h->params) {
             if (p.shape.size() != 4 || p.name.find(".proj.") != std::string::npos) continue;
-            float M = 0.f;
-            for (float v : p.host) M = std::max(M, std::fabs(v));
-            if (M > 32768.0f || (M < 1.0f / 4096.0f && M > 0.f) || !(M == M)) { h->fwd_h3 = false; h->opt["range_fallback"] = 1; break; }
+            if (!max_abs_in_fp16_window(p)) { h->fwd_h3 = false; h->opt["range_fallback"] = 1; break; }
         }
     }
     if (h->fwd_h3 && h->O("auto_range")) {

@@ -8,52 +8,38 @@ struct Packed2 {
     bool identity = false;    // 1x1 kernel's identity mode: no weights
 };
 
-struct cindm_unet2d {
+struct cindm_unet2d : ModelCore {
     cindm_unet2d_desc d;
     bool use_h3 = true;                                      // CINDM_MFMA=f32 selects the fp32-MFMA 3x3 kernel
-    bool use_la_site = true;                                 // LinearAttention sites without the q|k|v tensor (CINDM_LA_SITE=0 disables)
     bool force_f32 = false;                                  // the calibration forward overflowed on the split-fp16 kernels
-    std::vector<Param> params;
-    std::unordered_map<std::string, int> index;
     std::vector<int> dims;
-    std::vector<float> sinus;
     float* blob = nullptr;
     std::unordered_map<std::string, Packed2> packed;        // convolutions
     std::unordered_map<std::string, Packed> lin;            // time-path linears (1-D GEMM kernel)
     std::unordered_map<std::string, size_t> vec_off;
     float* ttable = nullptr; int tt_ld = 0;                 // [T][tt_ld]: per ResnetBlock (scale C | shift C)
     std::unordered_map<std::string, int> tt_off;
-    bool finalized = false;
     int launches = 0;
     struct Tap { size_t off; int HW, C; };
     std::unordered_map<std::string, Tap> taps;
     int64_t taps_imgs = 0;
     int CP() const { return ceil_to(d.channels, 4); }
-    std::map<std::string, int> opt;                          // cindm_unet2d_set_option
-    int O(const char* k) const { auto it = opt.find(k); return it == opt.end() ? 0 : it->second; }
 };
 
 static const OptDef kUnet2dOpts[] = {
-    {"mfma_f32", 0, nullptr},          // 1: 3x3 convolutions / stem / attention products on the exact fp32 MFMA kernels
-    {"la_site", 1, "CINDM_LA_SITE"},   // LinearAttention sites without the q|k|v tensor
-    {"ws_alias", 1, "CINDM_WS_ALIAS"}, // block-internal temporaries share workspace (0: every intermediate keeps its own slice)
-    {"tail_h3", 1, "CINDM_TAIL_H3"},   // ResnetBlock tails with a res_conv GEMM on the split-fp16 products (0: fp32 MFMA)
-    {"la_nsplit", 8, nullptr},         // LinearAttention context kernel at C = 64: workgroups (partial records) per image
-    {"la_wpi", 32, nullptr},           // LinearAttention apply kernel at C = 64: workgroups per image (each loops over its share of 64-pixel tiles)
-    {"ws_nosplit", 2, "CINDM_WS_NOSPLIT"},   // conv2d_ws_kernel: K of a chunk not split over the matrix waves (no in-tile reduction; 0 = round 2's k-groups)
-    {"conv_ws", 1, "CINDM_CONV_WS"},   // 3x3 convolutions: persistent wave-specialised conv2d_ws_kernel; 0 = conv2d_h3_kernel
-    {"stress", 0, "CINDM_STRESS"},     // > 0 (a seed): pseudo-random pauses before the hand-overs inside conv2d_ws_kernel (race tests)
-    {"auto_range", 1, "CINDM_AUTO_RANGE"},
-    {"range_fallback", 0, nullptr},
-    {"dbg2", 0, "CINDM_DBG2"},
+    {"mfma_f32", 0, nullptr, OPT_PACK},          // 1: 3x3 convolutions / stem / attention products on the exact fp32 MFMA kernels
+    {"la_site", 1, "CINDM_LA_SITE", OPT_PACK},   // LinearAttention sites without the q|k|v tensor
+    {"ws_alias", 1, "CINDM_WS_ALIAS", OPT_PACK}, // block-internal temporaries share workspace (0: every intermediate keeps its own slice)
+    {"tail_h3", 1, "CINDM_TAIL_H3", OPT_PACK},   // ResnetBlock tails with a res_conv GEMM on the split-fp16 products (0: fp32 MFMA)
+    {"la_nsplit", 8, nullptr, OPT_PACK},         // LinearAttention context kernel at C = 64: workgroups (partial records) per image
+    {"la_wpi", 32, nullptr, OPT_PACK},           // LinearAttention apply kernel at C = 64: workgroups per image (each loops over its share of 64-pixel tiles)
+    {"ws_nosplit", 2, "CINDM_WS_NOSPLIT", OPT_PACK},   // conv2d_ws_kernel: K of a chunk not split over the matrix waves (no in-tile reduction; 0 = round 2's k-groups)
+    {"conv_ws", 1, "CINDM_CONV_WS", OPT_PACK},   // 3x3 convolutions: persistent wave-specialised conv2d_ws_kernel; 0 = conv2d_h3_kernel
+    {"stress", 0, "CINDM_STRESS", OPT_PACK},     // > 0 (a seed): pseudo-random pauses before the hand-overs inside conv2d_ws_kernel (race tests)
+    {"auto_range", 1, "CINDM_AUTO_RANGE", OPT_PACK},
+    {"range_fallback", 0, nullptr, OPT_READONLY},
+    {"dbg2", 0, "CINDM_DBG2", OPT_PACK},
 };
-
-static void add_param2(cindm_unet2d* h, const std::string& n, std::vector<int64_t> s) {
-    Param p; p.name = n; p.shape = s; p.numel = 1;
-    for (auto v : s) p.numel *= (size_t)v;
-    h->index[n] = (int)h->params.size();
-    h->params.push_back(std::move(p));
-}
 
 static int build_manifest2(cindm_unet2d* h) {
     const auto& d = h->d;
@@ -61,24 +47,24 @@ static int build_manifest2(cindm_unet2d* h) {
     h->dims.clear(); h->dims.push_back(dim);
     for (int i = 0; i < d.n_mults; ++i) h->dims.push_back(dim * d.dim_mults[i]);
     auto conv = [&](const std::string& p, int i, int o, int k, bool bias = true) {
-        add_param2(h, p + ".weight", {o, i, k, k});
-        if (bias) add_param2(h, p + ".bias", {o});
+        h->add_param(p + ".weight", {o, i, k, k});
+        if (bias) h->add_param(p + ".bias", {o});
     };
     auto rb = [&](const std::string& p, int i, int o) {
-        add_param2(h, p + ".mlp.1.weight", {2 * o, tdim}); add_param2(h, p + ".mlp.1.bias", {2 * o});
-        conv(p + ".block1.proj", i, o, 3); add_param2(h, p + ".block1.norm.weight", {o}); add_param2(h, p + ".block1.norm.bias", {o});
-        conv(p + ".block2.proj", o, o, 3); add_param2(h, p + ".block2.norm.weight", {o}); add_param2(h, p + ".block2.norm.bias", {o});
+        h->add_param(p + ".mlp.1.weight", {2 * o, tdim}); h->add_param(p + ".mlp.1.bias", {2 * o});
+        conv(p + ".block1.proj", i, o, 3); h->add_param(p + ".block1.norm.weight", {o}); h->add_param(p + ".block1.norm.bias", {o});
+        conv(p + ".block2.proj", o, o, 3); h->add_param(p + ".block2.norm.weight", {o}); h->add_param(p + ".block2.norm.bias", {o});
         if (i != o) conv(p + ".res_conv", i, o, 1);
     };
     auto lattn = [&](const std::string& p, int c) {
         conv(p + ".fn.fn.to_qkv", c, hid * 3, 1, false);
         conv(p + ".fn.fn.to_out.0", hid, c, 1);
-        add_param2(h, p + ".fn.fn.to_out.1.g", {1, c, 1, 1});
-        add_param2(h, p + ".fn.norm.g", {1, c, 1, 1});
+        h->add_param(p + ".fn.fn.to_out.1.g", {1, c, 1, 1});
+        h->add_param(p + ".fn.norm.g", {1, c, 1, 1});
     };
     conv("init_conv", d.channels, dim, 7);
-    add_param2(h, "time_mlp.1.weight", {tdim, dim}); add_param2(h, "time_mlp.1.bias", {tdim});
-    add_param2(h, "time_mlp.3.weight", {tdim, tdim}); add_param2(h, "time_mlp.3.bias", {tdim});
+    h->add_param("time_mlp.1.weight", {tdim, dim}); h->add_param("time_mlp.1.bias", {tdim});
+    h->add_param("time_mlp.3.weight", {tdim, tdim}); h->add_param("time_mlp.3.bias", {tdim});
     const int n = d.n_mults;
     for (int ind = 0; ind < n; ++ind) {
         const int ci = h->dims[ind], co = h->dims[ind + 1];
@@ -96,7 +82,7 @@ static int build_manifest2(cindm_unet2d* h) {
     rb("mid_block1", mid, mid);
     conv("mid_attn.fn.fn.to_qkv", mid, hid * 3, 1, false);
     conv("mid_attn.fn.fn.to_out", hid, mid, 1);
-    add_param2(h, "mid_attn.fn.norm.g", {1, mid, 1, 1});
+    h->add_param("mid_attn.fn.norm.g", {1, mid, 1, 1});
     rb("mid_block2", mid, mid);
     rb("final_res_block", dim * 2, dim);
     conv("final_conv", dim, d.channels, 1);
@@ -116,62 +102,28 @@ extern "C" int cindm_unet2d_create(const cindm_unet2d_desc* desc, cindm_unet2d**
     REQUIRE(desc->timesteps >= 1, "timesteps must be >= 1");
     auto* h = new cindm_unet2d();
     h->d = *desc;
-    for (const auto& o : kUnet2dOpts) {
-        int v = o.def;
-        if (o.env) { const char* e = getenv(o.env); if (e) v = atoi(e); }
-        h->opt[o.key] = v;
-    }
-    { const char* e = getenv("CINDM_MFMA"); if (e && std::strcmp(e, "f32") == 0) h->opt["mfma_f32"] = 1; }
+    h->init_options(kUnet2dOpts);
     build_manifest2(h);
     *out = h;
     return 0;
 }
-extern "C" int cindm_unet2d_get_option(const cindm_unet2d* h, const char* key, int32_t* value) {
-    REQUIRE(h && key && value, "null argument");
-    auto it = h->opt.find(key);
-    if (it == h->opt.end()) return fail(std::string("unknown option: ") + key);
-    *value = it->second;
-    return 0;
-}
-extern "C" int cindm_unet2d_set_option(cindm_unet2d* h, const char* key, int32_t value) {
-    REQUIRE(h && key, "null argument");
-    auto it = h->opt.find(key);
-    if (it == h->opt.end()) return fail(std::string("unknown option: ") + key);
-    if (it->second != value) { it->second = value; h->finalized = false; }
-    return 0;
-}
+extern "C" int cindm_unet2d_get_option(const cindm_unet2d* h, const char* key, int32_t* value) { return core_get_option(h, key, value); }
+extern "C" int cindm_unet2d_set_option(cindm_unet2d* h, const char* key, int32_t value) { return core_set_option(h, key, value) < 0 ? -1 : 0; }
 extern "C" void cindm_unet2d_destroy(cindm_unet2d* h) {
     if (!h) return;
     if (h->blob) (void)hipFree(h->blob);
     if (h->ttable) (void)hipFree(h->ttable);
     delete h;
 }
-extern "C" int cindm_unet2d_num_params(const cindm_unet2d* h) { return h ? (int)h->params.size() : fail("null handle"); }
+extern "C" int cindm_unet2d_num_params(const cindm_unet2d* h) { return core_num_params(h); }
 extern "C" int cindm_unet2d_param_info(const cindm_unet2d* h, int idx, char* name, int cap, int64_t shape[4], int* ndim) {
-    REQUIRE(h && idx >= 0 && idx < (int)h->params.size(), "bad param index");
-    const Param& p = h->params[idx];
-    if (name && cap > 0) { std::strncpy(name, p.name.c_str(), cap - 1); name[cap - 1] = 0; }
-    for (int i = 0; i < 4; ++i) shape[i] = i < (int)p.shape.size() ? p.shape[i] : 1;
-    if (ndim) *ndim = (int)p.shape.size();
-    return 0;
+    return core_param_info(h, idx, name, cap, shape, ndim);
 }
 extern "C" int cindm_unet2d_set_param(cindm_unet2d* h, const char* key, const float* src, int64_t numel, int on_device) {
-    REQUIRE(h && key && src, "null argument");
-    auto it = h->index.find(key);
-    if (it == h->index.end()) return fail(std::string("unexpected key in state_dict: ") + key);
-    Param& p = h->params[it->second];
-    if ((int64_t)p.numel != numel) return fail(std::string("size mismatch for ") + key);
-    p.host.resize(p.numel);
-    if (on_device) HIPCHK(hipMemcpy(p.host.data(), src, p.numel * sizeof(float), hipMemcpyDeviceToHost));
-    else std::memcpy(p.host.data(), src, p.numel * sizeof(float));
-    p.set = true; h->finalized = false;
-    return 0;
+    return core_set_param(h, key, src, numel, on_device);
 }
 extern "C" int cindm_unet2d_set_sinusoid_table(cindm_unet2d* h, const float* t, int64_t numel) {
-    REQUIRE(h && t, "null argument");
-    REQUIRE(numel == (int64_t)h->d.timesteps * h->d.dim, "sinusoid table must be [timesteps, dim]");
-    h->sinus.assign(t, t + numel); h->finalized = false;
-    return 0;
+    return core_set_sinusoid(h, t, numel, h ? (int64_t)h->d.timesteps * h->d.dim : 0);
 }
 extern "C" int cindm_unet2d_padded_channels(const cindm_unet2d* h) { return h ? h->CP() : 0; }
 
@@ -1006,12 +958,9 @@ static int unet2d_finalize_pack(cindm_unet2d* h, void* stream_) {
     if (h->use_h3 && h->O("auto_range")) {
         for (const auto& p : h->params) {
             if (p.shape.size() != 4 || p.name.find(".proj.") != std::string::npos) continue;
-            float M = 0.f;
-            for (float v : p.host) M = std::max(M, std::fabs(v));
-            if (M > 32768.0f || (M < 1.0f / 4096.0f && M > 0.f) || !(M == M)) { h->use_h3 = false; h->opt["range_fallback"] = 1; break; }
+            if (!max_abs_in_fp16_window(p)) { h->use_h3 = false; h->opt["range_fallback"] = 1; break; }
         }
     }
-    h->use_la_site = h->O("la_site") != 0;
     h->packed.clear(); h->lin.clear(); h->vec_off.clear(); h->tt_off.clear();
     std::vector<std::pair<std::string, int>> rbs;          // (prefix, Cout)
     int tt_ld = 0;
@@ -1036,7 +985,7 @@ static int unet2d_finalize_pack(cindm_unet2d* h, void* stream_) {
                 }
             }
             if (pack_conv2d(h, bb, pre, kind, ws, split) != 0) return -1;
-            if (h->use_h3 && h->use_la_site && ends(".fn.fn.to_out.0.weight"))
+            if (h->use_h3 && h->O("la_site") && ends(".fn.fn.to_out.0.weight"))
                 pack_la_site2(h, bb, k.substr(0, k.size() - std::strlen(".to_out.0.weight")));
         } else if (k == "time_mlp.1.weight" || k == "time_mlp.3.weight") {
             pack_linear2(h, bb, k.substr(0, k.size() - 7));
@@ -1119,34 +1068,15 @@ extern "C" int cindm_unet2d_forward(cindm_unet2d* h, const float* x, int32_t t, 
 // finalize = repack (unet2d_finalize_pack) + calibration forward on the split-fp16 kernels, as cindm_unet1d_finalize
 extern "C" int cindm_unet2d_finalize(cindm_unet2d* h, void* stream_) {
     REQUIRE(h, "null handle");
+    if (h->finalized) return 0;
     h->force_f32 = false;
     if (unet2d_finalize_pack(h, stream_) != 0) return -1;
     if (!h->use_h3 || !h->O("auto_range")) return 0;
-    hipStream_t stream = (hipStream_t)stream_;
     const int HW = h->d.image_size * h->d.image_size, CP = h->CP();
-    const size_t n = (size_t)HW * CP;                       // one image, device layout [pixel][padded channel]
-    std::vector<float> hx(n, 0.f), he(n);
-    uint32_t st = 0x9E3779B1u;
-    for (size_t i = 0; i < n; ++i) {
-        if ((int)(i % CP) >= h->d.channels) continue;
-        float a = 0.f;
-        for (int k = 0; k < 4; ++k) { st = st * 1664525u + 1013904223u; a += (float)(st >> 8) * (1.0f / 16777216.0f) - 0.5f; }
-        hx[i] = a * 1.7320508f;
-    }
     const size_t wsb = cindm_unet2d_workspace_bytes(h, 1);
-    float *dx = nullptr, *de = nullptr; void* ws = nullptr;
-    HIPCHK(hipMalloc((void**)&dx, n * 4)); HIPCHK(hipMalloc((void**)&de, n * 4)); HIPCHK(hipMalloc(&ws, wsb));
-    HIPCHK(hipMemcpyAsync(dx, hx.data(), n * 4, hipMemcpyHostToDevice, stream));
-    bool finite = true;
-    const int T = h->d.timesteps;
-    for (int t : {0, T / 2, T - 1}) {
-        if (cindm_unet2d_forward(h, dx, t, nullptr, de, 1, ws, wsb, stream_) != 0) { finite = false; break; }
-        HIPCHK(hipMemcpyAsync(he.data(), de, n * 4, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        for (float v : he) if (!std::isfinite(v)) { finite = false; break; }
-        if (!finite) break;
-    }
-    (void)hipFree(dx); (void)hipFree(de); (void)hipFree(ws);
+    auto fwd = [&](int t, const float* x, float* eps, void* ws) { return cindm_unet2d_forward(h, x, t, nullptr, eps, 1, ws, wsb, stream_); };
+    bool finite = true;       // (one image, device layout [pixel][padded channel])
+    if (calibrate_at_finalize((size_t)HW * CP, h->d.channels, CP, 0x9E3779B1u, h->d.timesteps, wsb, (hipStream_t)stream_, fwd, &finite) != 0) return -1;
     h->taps.clear();
     if (!finite) {
         h->force_f32 = true;

@@ -269,7 +269,7 @@ class GaussianDiffusion1D(nn.Module):
             for m in ms:
                 m.exchange_free(False)
         for m in ms:
-            m._py_recovered = getattr(m, "_py_recovered", 0) + 1
+            m.note_recovered()
         return out
 
     @torch.no_grad()

@@ -6,18 +6,14 @@ gradient of (summed lift / drag surrogate forces + lambda * boundary overlap) wi
 evaluated by libcindm_hip.so (forward AND input-gradient kernels) instead of ``torch.autograd.grad``.  It plugs into
 ``GaussianDiffusion.sample(design_fn=..., design_guidance="standard-alpha")`` unchanged: the 2-D convention is that
 ``design_fn(x)`` returns the gradient tensor (model/diffusion_2d.py:813)."""
-import ctypes as C
-import math
-
 import torch
-from torch import nn
 
 from . import _ffi
-from .unet1d import _attach
+from ._native import _ExchangeRecovery, _NativeModel
 from .unet2d import from_device_layout, to_device_layout
 
 
-class ForceUnet(nn.Module):
+class ForceUnet(_ExchangeRecovery, _NativeModel):
     """Drop-in for ``ForceUnet(dim, dim_mults=(1, 2, 4, 8), channels=4)``.  ``forward(x[N, 4, H, W]) -> [N, 2]``;
     ``input_grad(x, lambda_force)`` returns d(sum lambda |out[:, 0]| + out[:, 1]) / dx as well."""
 
@@ -27,73 +23,21 @@ class ForceUnet(nn.Module):
         if self_condition or learned_variance or resnet_block_groups != 8 or (init_dim not in (None, dim)):
             raise NotImplementedError("ForceUnet: only the configuration of inference/inverse_design_2d.py:157-161 is built")
         self.channels, self.dim, self.dim_mults, self.image_size = channels, dim, tuple(dim_mults), int(image_size)
-        L = _ffi.lib()
         d = _ffi.ForceUnetDesc()
         d.dim, d.n_mults, d.channels, d.image_size = dim, len(self.dim_mults), channels, self.image_size
         for i, m in enumerate(self.dim_mults):
             d.dim_mults[i] = m
-        h = C.c_void_p()
-        _ffi.check(L.cindm_forceunet_create(C.byref(d), C.byref(h)))
-        self._h, self._sig, self._ws = h, None, None
-        self._py_recovered = 0
-        name = C.create_string_buffer(256)
-        shape = (C.c_int64 * 4)()
-        nd = C.c_int()
-        manifest = []
-        for i in range(L.cindm_forceunet_num_params(h)):
-            _ffi.check(L.cindm_forceunet_param_info(h, i, name, 256, C.byref(shape), C.byref(nd)))
-            manifest.append((name.value.decode(), tuple(int(shape[j]) for j in range(nd.value))))
-        fan = {k[:-7]: int(torch.tensor(s[1:]).prod()) for k, s in manifest if k.endswith(".weight") and len(s) >= 2}
-        for k, s in manifest:
-            t = torch.empty(s)
-            if k.endswith(".g") or k.endswith(".norm.weight"):
-                t.fill_(1.0)
-            elif k.endswith(".norm.bias"):
-                t.zero_()
-            else:
-                t.uniform_(-1.0 / math.sqrt(fan[k.rsplit(".", 1)[0]]), 1.0 / math.sqrt(fan[k.rsplit(".", 1)[0]]))
-            _attach(self, k, nn.Parameter(t))
+        self._create(d)
 
-    def __del__(self):
-        h = self.__dict__.get("_h")
-        if h is not None and h.value:
-            try:
-                _ffi.lib().cindm_forceunet_destroy(h)
-            except Exception:
-                pass
-            self.__dict__["_h"] = None
+    _PREFIX = "forceunet"
+    _CPU_TEXT = "ForceUnet parameters are on the CPU: move the module to a ROCm device; there is no CPU execution path"
+    _WS_PROBE = (1, 0)
+    _POLL = "status"
+    TIMEOUT_TEXT = "an in-kernel exchange of the surrogate's GroupNorm derivative timed out (foreign load on the device)"
+    RERUN_TIMEOUT_TEXT = "an exchange timed out during the exchange-free re-run (internal error)"
 
-    def sync_weights(self):
-        sig = tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if sig == self._sig:
-            return
-        L = _ffi.lib()
-        dev = None
-        for k, p in self.named_parameters():
-            t = p.detach().to(torch.float32).contiguous()
-            if t.is_cuda:
-                dev = t.device
-            _ffi.check(L.cindm_forceunet_set_param(self._h, k.encode(), _ffi.ptr(t), t.numel(), int(t.is_cuda)))
-        if dev is None:
-            raise _ffi.CindmError("ForceUnet parameters are on the CPU: move the module to a ROCm device; there is no CPU execution path")
-        with torch.cuda.device(dev):
-            _ffi.check(L.cindm_forceunet_finalize(self._h, _ffi.current_stream(dev)))
-        self._sig = sig
-
-    def set_option(self, key, value):
-        """Selects a kernel path of this model (``cindm_forceunet_set_option``): ``h3`` / ``h3_bwd`` = 0 run the forward /
-        input-gradient 3x3 convolutions on the exact fp32 MFMA kernel, ``auto_range`` = 0 skips the range rule's calibration
-        forward.  Takes effect at the next call."""
-        _ffi.check(_ffi.lib().cindm_forceunet_set_option(self._h, key.encode(), int(value)))
-        if key not in ("no_exchange", "recover", "dbg", "stress"):       # (run-time options: the packed weights stay valid)
-            self._sig = None
-        return self
-
-    @property
-    def recovered(self):
-        """How many gradient calls / guided chains of this model were re-run on the exchange-free GroupNorm derivative after an
-        in-kernel exchange timed out (foreign load on the device); 0 in normal operation."""
-        return int(_ffi.lib().cindm_forceunet_recovered(self._h)) + self._py_recovered
+    def _param_tensor(self, key, p):
+        return p.detach().to(torch.float32).contiguous()
 
     # True (default): every gradient call reads the handle's exchange flag before its result is handed back -- a stream synchronise
     # and a 4-byte device-to-host copy per call, which serialises a Python-driven guided loop on the host.  False: asynchronous calls
@@ -107,40 +51,11 @@ class ForceUnet(nn.Module):
         with torch.cuda.device(dev):
             return int(_ffi.lib().cindm_forceunet_status(self._h, _ffi.current_stream(dev)))
 
-    def _checked(self, call, device):
+    def _grad_call(self, call, device):
         """Runs ``call()`` (one library gradient call on the current stream) and hands its result back only after the handle's
         exchange flag has been read: a timed-out exchange (NaN gradients) is re-run once with ``no_exchange`` = 1 -- or raised,
         with ``recover`` = 0.  Skipped under stream capture (a capture cannot synchronise; the chain entry points check)."""
-        out = call()
-        if torch.cuda.is_current_stream_capturing() or not self.check_exchange:
-            return out
-        L = _ffi.lib()
-        st = L.cindm_forceunet_status(self._h, _ffi.current_stream(device))
-        if st < 0:
-            _ffi.check(st)
-        if st == 0:
-            return out
-        v = C.c_int32()
-        _ffi.check(L.cindm_forceunet_get_option(self._h, b"recover", C.byref(v)))
-        if not v.value:
-            raise _ffi.CindmError("an in-kernel exchange of the surrogate's GroupNorm derivative timed out (foreign load on the device)")
-        _ffi.check(L.cindm_forceunet_set_option(self._h, b"no_exchange", 1))
-        try:
-            out = call()
-            st = L.cindm_forceunet_status(self._h, _ffi.current_stream(device))
-        finally:
-            _ffi.check(L.cindm_forceunet_set_option(self._h, b"no_exchange", 0))
-        if st != 0:
-            raise _ffi.CindmError("an exchange timed out during the exchange-free re-run (internal error)")
-        self._py_recovered += 1
-        return out
-
-    def get_option(self, key):
-        """Current option value; ``get_option("range_fallback")`` is 1 after the calibration forward left fp16's range."""
-        self.sync_weights()
-        v = C.c_int32()
-        _ffi.check(_ffi.lib().cindm_forceunet_get_option(self._h, key.encode(), C.byref(v)))
-        return int(v.value)
+        return self._checked(call, device, self.check_exchange and not torch.cuda.is_current_stream_capturing())
 
     def _workspace(self, nbytes, device):
         if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
@@ -167,10 +82,10 @@ class ForceUnet(nn.Module):
             dx = torch.empty_like(xd)
             if dout is not None:
                 do = dout.detach().to(device=x.device, dtype=torch.float32).reshape(n, 2).contiguous()
-                self._checked(lambda: _ffi.check(L.cindm_forceunet_vjp(self._h, _ffi.ptr(xd), _ffi.ptr(do), _ffi.ptr(out), _ffi.ptr(dx), n,
+                self._grad_call(lambda: _ffi.check(L.cindm_forceunet_vjp(self._h, _ffi.ptr(xd), _ffi.ptr(do), _ffi.ptr(out), _ffi.ptr(dx), n,
                                                                        _ffi.ptr(ws), ws.numel(), _ffi.current_stream(x.device))), x.device)
             else:
-                self._checked(lambda: _ffi.check(L.cindm_forceunet_grad(self._h, _ffi.ptr(xd), float(lambda_force), _ffi.ptr(out), _ffi.ptr(dx), n,
+                self._grad_call(lambda: _ffi.check(L.cindm_forceunet_grad(self._h, _ffi.ptr(xd), float(lambda_force), _ffi.ptr(out), _ffi.ptr(dx), n,
                                                                         _ffi.ptr(ws), ws.numel(), _ffi.current_stream(x.device))), x.device)
         return out, dx.reshape(n, hh, ww, c).permute(0, 3, 1, 2).contiguous()
 
@@ -240,7 +155,7 @@ class ForceObjective:
         if self._ws is None or self._ws.numel() < nbytes or self._ws.device != x.device:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         with torch.cuda.device(x.device):
-            m._checked(lambda: _ffi.check(L.cindm_airfoil_design_grad(m._h, _ffi.ptr(xd), self.B, self.nb, self.frames, cp, self.p_min, self.p_max,
+            m._grad_call(lambda: _ffi.check(L.cindm_airfoil_design_grad(m._h, _ffi.ptr(xd), self.B, self.nb, self.frames, cp, self.p_min, self.p_max,
                                                                       self.lambda_force, self.lambda_overlap, self.factor, int(self.sum_boundary),
                                                                       _ffi.ptr(g), _ffi.ptr(self._ws), self._ws.numel(),
                                                                       _ffi.current_stream(x.device))), x.device)

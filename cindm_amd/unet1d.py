@@ -10,23 +10,9 @@ import ctypes as C
 import math
 
 import torch
-from torch import nn
 
 from . import _ffi
-
-
-class _Node(nn.Module):
-    """Anonymous container used to rebuild the reference's dotted key hierarchy."""
-
-
-def _attach(root, dotted, param):
-    parts = dotted.split(".")
-    mod = root
-    for p in parts[:-1]:
-        if p not in mod._modules:
-            mod.add_module(p, _Node())
-        mod = mod._modules[p]
-    mod.register_parameter(parts[-1], param)
+from ._native import _ExchangeRecovery, _NativeModel
 
 
 def sinusoid_table(timesteps, dim):
@@ -40,7 +26,7 @@ def sinusoid_table(timesteps, dim):
     return torch.cat((arg.sin(), arg.cos()), dim=-1).contiguous()
 
 
-class TemporalUnet1D(nn.Module):
+class TemporalUnet1D(_ExchangeRecovery, _NativeModel):
     """Drop-in for ``TemporalUnet1D(horizon, transition_dim, cond_dim, dim=64,
     dim_mults=(1, 2, 4, 8), attention=False)`` (model/diffusion_1d.py:519-527).
 
@@ -58,107 +44,25 @@ class TemporalUnet1D(nn.Module):
         self.dim_mults = tuple(dim_mults)
         self.attention = bool(attention)
         self.timesteps = int(timesteps)
-        L = _ffi.lib()
         d = _ffi.UnetDesc()
         d.horizon, d.transition_dim, d.dim, d.n_mults = horizon, transition_dim, dim, len(self.dim_mults)
         for i, m in enumerate(self.dim_mults):
             d.dim_mults[i] = m
         d.attention, d.timesteps = int(self.attention), self.timesteps
-        h = C.c_void_p()
-        _ffi.check(L.cindm_unet1d_create(C.byref(d), C.byref(h)))
-        self._h = h
-        self._sig = None
-        self._ws = None
-        self._ws_rows = 0
-        # An in-kernel exchange between workgroups that timed out (foreign load on the device kept a partner workgroup from
-        # becoming resident) is recovered by re-running the work once on the exchange-free kernels; False: raise CindmError
-        self._recover = True
-        # parameters under the reference's key names, PyTorch-default initialisation
-        name = C.create_string_buffer(256)
-        shape = (C.c_int64 * 4)()
-        nd = C.c_int()
-        manifest = []
-        for i in range(L.cindm_unet1d_num_params(h)):
-            _ffi.check(L.cindm_unet1d_param_info(h, i, name, 256, C.byref(shape), C.byref(nd)))
-            manifest.append((name.value.decode(), tuple(int(shape[j]) for j in range(nd.value))))
-        fan = {}
-        for k, s in manifest:
-            if k.endswith(".weight") and len(s) >= 2:
-                f = s[1] * (s[2] if len(s) > 2 else 1)
-                fan[k[:-7]] = f
-        for k, s in manifest:
-            base = k.rsplit(".", 1)[0]
-            t = torch.empty(s)
-            if k.endswith(".norm.g") or (".block.2." in k and k.endswith(".weight")):
-                t.fill_(1.0)
-            elif ".block.2." in k:
-                t.zero_()
-            else:
-                bound = 1.0 / math.sqrt(fan[base])
-                t.uniform_(-bound, bound)
-            _attach(self, k, nn.Parameter(t))
-        self._manifest = manifest
+        self._create(d)
 
-    def __del__(self):
-        h = self.__dict__.get("_h")
-        if h is not None and h.value:
-            try:
-                _ffi.lib().cindm_unet1d_destroy(h)
-            except Exception:
-                pass
-            self.__dict__["_h"] = None
+    _PREFIX = "unet1d"
+    _CPU_TEXT = ("TemporalUnet1D parameters are on the CPU: move the module to a ROCm device (.to('cuda')); "
+                 "there is no CPU execution path")
 
-    # ------------------------------------------------------------------ weights -> library
-    def _signature(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+    @staticmethod
+    def _fill(key):
+        if key.endswith(".norm.g") or (".block.2." in key and key.endswith(".weight")):
+            return 1.0
+        return 0.0 if ".block.2." in key else None
 
-    def sync_weights(self, force=False):
-        """Copies the current parameter values into the library handle and re-runs its
-        finalisation (weight repack + per-timestep bias table) if anything changed."""
-        sig = self._signature()
-        if not force and sig == self._sig:
-            return
-        L = _ffi.lib()
-        dev = None
-        for k, p in self.named_parameters():
-            if p.dtype != torch.float32:
-                raise TypeError(f"{k}: fp32 parameters required, got {p.dtype}")
-            t = p.detach().contiguous()
-            if t.is_cuda:
-                dev = t.device
-            _ffi.check(L.cindm_unet1d_set_param(self._h, k.encode(), _ffi.ptr(t), t.numel(), int(t.is_cuda)))
-        if dev is None:
-            raise _ffi.CindmError("TemporalUnet1D parameters are on the CPU: move the module to a ROCm device "
-                                  "(.to('cuda')); there is no CPU execution path")
-        tab = sinusoid_table(self.timesteps, self.dim)
-        _ffi.check(L.cindm_unet1d_set_sinusoid_table(self._h, _ffi.ptr(tab), tab.numel()))
-        with torch.cuda.device(dev):
-            _ffi.check(L.cindm_unet1d_finalize(self._h, _ffi.current_stream(dev)))
-        self._sig = sig
-
-    def set_option(self, key, value):
-        """Selects a kernel path of this model (``cindm_unet1d_set_option``; keys in include/cindm_hip.h), e.g.
-        ``set_option("mfma_f32", 1)``.  Every path computes the same function; takes effect at the next call."""
-        _ffi.check(_ffi.lib().cindm_unet1d_set_option(self._h, key.encode(), int(value)))
-        self._sig = None
-        self._ws = None
-        return self
-
-    def get_option(self, key):
-        """Current value of a kernel-path option; ``get_option("range_fallback")`` is 1 after the weights were found outside
-        the split-fp16 window and the exact fp32 kernels were selected (evaluated when the weights are synchronised)."""
-        self.sync_weights()
-        v = C.c_int32()
-        _ffi.check(_ffi.lib().cindm_unet1d_get_option(self._h, key.encode(), C.byref(v)))
-        return int(v.value)
-
-    def workspace(self, rows, device):
-        L = _ffi.lib()
-        if self._ws is None or self._ws_rows < rows or self._ws.device != device:
-            nbytes = L.cindm_unet1d_workspace_bytes(self._h, rows)
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            self._ws_rows = rows
-        return self._ws
+    def _sinusoid_table(self):
+        return sinusoid_table(self.timesteps, self.dim)
 
     @property
     def launches_per_forward(self):
@@ -190,18 +94,16 @@ class TemporalUnet1D(nn.Module):
         self.sync_weights()
         x = x.contiguous().float()
         out = torch.empty_like(x)
-        ws = self.workspace(x.shape[0], x.device)
         if check is None:
             check = not torch.cuda.is_current_stream_capturing()
 
         def launch():
+            ws = self.workspace(x.shape[0], x.device)          # (inside: a range escalation re-runs on a plan of its own size)
             with torch.cuda.device(x.device):
                 _ffi.check(_ffi.lib().cindm_unet1d_forward(self._h, _ffi.ptr(x), t, None, _ffi.ptr(out), x.shape[0],
                                                            _ffi.ptr(ws), ws.numel(), _ffi.current_stream(x.device)))
 
-        launch()
-        if check and self.poll_status(x.device):
-            self.rerun_exchange_free(launch, x.device)
+        self._checked(launch, x.device, check)
         if check and self.range_guard_pending():
             # the range rule on the caller's own data: the FIRST checked forward after a weight synchronisation
             self.range_guard(lambda: out, launch, x.device)
@@ -210,8 +112,9 @@ class TemporalUnet1D(nn.Module):
     # ------------------------------------------------------------------ range rule on the caller's data (round 6)
     def range_guard_pending(self):
         """True until the first result after the last weight synchronisation has been checked -- and only where the check can
-        change anything: the handle runs the split-fp16 kernels with ``auto_range`` on."""
-        if self.__dict__.get("_range_checked_sig") == self._sig and self._sig is not None:
+        change anything: the handle runs the split-fp16 kernels with ``auto_range`` on.  Every finalize of the handle (new weights,
+        a change of an option that selects what is packed) makes it pending again; a run-time option does not."""
+        if self._range_checked:
             return False
         return bool(self.get_option("auto_range")) and not self.get_option("mfma_f32") and not self.get_option("range_fallback")
 
@@ -222,13 +125,13 @@ class TemporalUnet1D(nn.Module):
         for the exact fp32-MFMA kernels (``get_option("range_fallback")`` reads 3), ``rerun()`` repeats the work; if that is not
         finite either the cause was not the range (non-finite inputs / weights) and the split-fp16 pack is restored.
         Returns True when the handle was escalated."""
-        self._range_checked_sig = self._sig
+        self._range_checked = True
         if bool(torch.isfinite(result()).all()):
             return False
         import warnings
         with torch.cuda.device(device):
             _ffi.check(_ffi.lib().cindm_unet1d_range_escalate(self._h, 1, _ffi.current_stream(device)))
-        self._ws = None; self._ws_rows = 0           # (the fp32 plan has its own workspace size)
+        self._ws = None           # (the fp32 plan has its own workspace size)
         rerun()
         if bool(torch.isfinite(result()).all()):
             warnings.warn("cindm_amd: the first result after loading these weights was not finite on the split-fp16 kernels (an activation left "
@@ -237,31 +140,13 @@ class TemporalUnet1D(nn.Module):
             return True
         with torch.cuda.device(device):
             _ffi.check(_ffi.lib().cindm_unet1d_range_escalate(self._h, 0, _ffi.current_stream(device)))
-        self._ws = None; self._ws_rows = 0
+        self._ws = None
         return False
 
     TIMEOUT_TEXT = ("an in-kernel exchange between workgroups timed out (GroupNorm pair / attention head exchange): "
                     "the results of that forward are invalid")
-
-    @property
-    def recover_exchange_timeouts(self):
-        return self._recover
-
-    @recover_exchange_timeouts.setter
-    def recover_exchange_timeouts(self, on):
-        """Also tells the library (run-time option ``recover``): its chain entry points (sample / ddim_sample / the built-in guided
-        loop) return an error instead of re-running a timed-out chain."""
-        self._recover = bool(on)
-        _ffi.check(_ffi.lib().cindm_unet1d_set_option(self._h, b"recover", int(self._recover)))
-
-    def poll_raw(self, device):
-        """True when an exchange of a forward issued so far timed out (the flag is cleared); synchronises; never raises for a
-        time-out."""
-        with torch.cuda.device(device):
-            rc = _ffi.lib().cindm_unet1d_poll(self._h, _ffi.current_stream(device))
-        if rc < 0:
-            _ffi.check(rc)
-        return rc == 1
+    RERUN_TIMEOUT_TEXT = TIMEOUT_TEXT
+    _POLL = "poll"
 
     def check_status(self, device):
         """Raises CindmError when an in-kernel exchange between workgroups of a forward issued so far timed out (its
@@ -272,37 +157,10 @@ class TemporalUnet1D(nn.Module):
     def poll_status(self, device):
         """True when an exchange of a forward issued so far timed out (the flag is cleared); synchronises the current
         stream.  With ``recover_exchange_timeouts = False`` a time-out raises CindmError here instead."""
-        with torch.cuda.device(device):
-            rc = _ffi.lib().cindm_unet1d_poll(self._h, _ffi.current_stream(device))
-        if rc < 0:
-            _ffi.check(rc)
-        if rc == 1 and not self.recover_exchange_timeouts:
+        hit = self.poll_raw(device)
+        if hit and not self.recover_exchange_timeouts:
             raise _ffi.CindmError(self.TIMEOUT_TEXT)
-        return rc == 1
-
-    def exchange_free(self, on):
-        """Run-time switch (``cindm_unet1d_set_option("no_exchange")``; does not touch the packed weights or the workspace):
-        only kernels without an in-launch exchange between workgroups."""
-        _ffi.check(_ffi.lib().cindm_unet1d_set_option(self._h, b"no_exchange", int(bool(on))))
-
-    def rerun_exchange_free(self, fn, device):
-        """``fn()`` once more with this model on the exchange-free kernels (after a time-out); a second time-out cannot
-        happen there and raises."""
-        self.exchange_free(True)
-        try:
-            fn()
-            with torch.cuda.device(device):
-                rc = _ffi.lib().cindm_unet1d_poll(self._h, _ffi.current_stream(device))
-            if rc != 0:
-                raise _ffi.CindmError(self.TIMEOUT_TEXT if rc == 1 else _ffi.lib().cindm_last_error().decode())
-        finally:
-            self.exchange_free(False)
-        self._py_recovered = getattr(self, "_py_recovered", 0) + 1
-
-    @property
-    def recovered(self):
-        """Forwards / chains of this model that were re-run on the exchange-free kernels after a time-out."""
-        return _ffi.lib().cindm_unet1d_recovered(self._h) + getattr(self, "_py_recovered", 0)
+        return hit
 
     # kind 4 = the k=5 convolutions: conv_gemm_h3_kernel<5,48,*> (split-fp16 MFMA; default) or
     # conv_gemm_kernel<5,32,48,*> (fp32 MFMA; CINDM_MFMA=f32)

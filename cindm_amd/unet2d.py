@@ -10,10 +10,10 @@ import ctypes as C
 import math
 
 import torch
-from torch import nn
 
 from . import _ffi
-from .unet1d import _attach, sinusoid_table
+from ._native import _NativeModel
+from .unet1d import sinusoid_table
 
 
 def to_device_layout(x, cp):
@@ -30,7 +30,7 @@ def from_device_layout(y, c, h, w):
     return y[:, :, :c].reshape(n, h, w, c).permute(0, 3, 1, 2).contiguous()
 
 
-class Unet(nn.Module):
+class Unet(_NativeModel):
     """Drop-in for ``Unet(dim, dim_mults=(1, 2), channels=21)`` (model/diffusion_2d.py:282-367) on the sampling
     path.  Options the airfoil checkpoints never use (self-conditioning, learned variance, learned / random
     sinusoidal embeddings, init_dim / out_dim overrides, GroupNorm groups != 8) are rejected.
@@ -55,96 +55,19 @@ class Unet(nn.Module):
         self.dim_mults = tuple(dim_mults)
         self.image_size = int(image_size)
         self.timesteps = int(timesteps)
-        L = _ffi.lib()
         d = _ffi.Unet2dDesc()
         d.dim, d.n_mults = dim, len(self.dim_mults)
         for i, m in enumerate(self.dim_mults):
             d.dim_mults[i] = m
         d.channels, d.image_size, d.timesteps = channels, self.image_size, self.timesteps
-        h = C.c_void_p()
-        _ffi.check(L.cindm_unet2d_create(C.byref(d), C.byref(h)))
-        self._h = h
-        self._sig = None
-        self._ws = None
-        self._ws_images = 0
-        self.padded_channels = L.cindm_unet2d_padded_channels(h)
-        name = C.create_string_buffer(256)
-        shape = (C.c_int64 * 4)()
-        nd = C.c_int()
-        manifest = []
-        for i in range(L.cindm_unet2d_num_params(h)):
-            _ffi.check(L.cindm_unet2d_param_info(h, i, name, 256, C.byref(shape), C.byref(nd)))
-            manifest.append((name.value.decode(), tuple(int(shape[j]) for j in range(nd.value))))
-        fan = {k[:-7]: int(torch.tensor(s[1:]).prod()) for k, s in manifest if k.endswith(".weight") and len(s) >= 2}
-        for k, s in manifest:
-            t = torch.empty(s)
-            if k.endswith(".g") or k.endswith(".norm.weight"):
-                t.fill_(1.0)
-            elif k.endswith(".norm.bias"):
-                t.zero_()
-            else:
-                bound = 1.0 / math.sqrt(fan[k.rsplit(".", 1)[0]])
-                t.uniform_(-bound, bound)
-            _attach(self, k, nn.Parameter(t))
-        self._manifest = manifest
+        self._create(d)
+        self.padded_channels = _ffi.lib().cindm_unet2d_padded_channels(self._h)
 
-    def __del__(self):
-        h = self.__dict__.get("_h")
-        if h is not None and h.value:
-            try:
-                _ffi.lib().cindm_unet2d_destroy(h)
-            except Exception:
-                pass
-            self.__dict__["_h"] = None
+    _PREFIX = "unet2d"
+    _CPU_TEXT = "Unet parameters are on the CPU: move the module to a ROCm device (.to('cuda')); there is no CPU execution path"
 
-    def _signature(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
-
-    def sync_weights(self, force=False):
-        """Copies the current parameter values into the library handle and re-runs its finalisation (weight
-        standardisation + repack + per-timestep scale/shift table) if anything changed."""
-        sig = self._signature()
-        if not force and sig == self._sig:
-            return
-        L = _ffi.lib()
-        dev = None
-        for k, p in self.named_parameters():
-            if p.dtype != torch.float32:
-                raise TypeError(f"{k}: fp32 parameters required, got {p.dtype}")
-            t = p.detach().contiguous()
-            if t.is_cuda:
-                dev = t.device
-            _ffi.check(L.cindm_unet2d_set_param(self._h, k.encode(), _ffi.ptr(t), t.numel(), int(t.is_cuda)))
-        if dev is None:
-            raise _ffi.CindmError("Unet parameters are on the CPU: move the module to a ROCm device (.to('cuda')); "
-                                  "there is no CPU execution path")
-        tab = sinusoid_table(self.timesteps, self.dim)
-        _ffi.check(L.cindm_unet2d_set_sinusoid_table(self._h, _ffi.ptr(tab), tab.numel()))
-        with torch.cuda.device(dev):
-            _ffi.check(L.cindm_unet2d_finalize(self._h, _ffi.current_stream(dev)))
-        self._sig = sig
-
-    def set_option(self, key, value):
-        """Selects a kernel path of this model (``cindm_unet2d_set_option``; keys in include/cindm_hip.h)."""
-        _ffi.check(_ffi.lib().cindm_unet2d_set_option(self._h, key.encode(), int(value)))
-        self._sig = None
-        self._ws = None
-        return self
-
-    def get_option(self, key):
-        """Current value of a kernel-path option; ``get_option("range_fallback")`` is 1 after the weights were found outside
-        the split-fp16 window and the exact fp32 kernels were selected (evaluated when the weights are synchronised)."""
-        self.sync_weights()
-        v = C.c_int32()
-        _ffi.check(_ffi.lib().cindm_unet2d_get_option(self._h, key.encode(), C.byref(v)))
-        return int(v.value)
-
-    def workspace(self, images, device):
-        if self._ws is None or self._ws_images < images or self._ws.device != device:
-            nbytes = _ffi.lib().cindm_unet2d_workspace_bytes(self._h, images)
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            self._ws_images = images
-        return self._ws
+    def _sinusoid_table(self):
+        return sinusoid_table(self.timesteps, self.dim)
 
     @property
     def launches_per_forward(self):

@@ -83,12 +83,17 @@ int  cindm_unet1d_set_param(cindm_unet1d* h, const char* key, const float* src, 
 int  cindm_unet1d_set_sinusoid_table(cindm_unet1d* h, const float* table_host, int64_t numel);
 /* Repack weights to the kernels' [tap][Cin][Cout] layout and precompute, for every timestep,
  * the time path time_mlp -> per-block Mish->Linear biases (:537-542, :493-497, :509) with the
- * GEMM kernels.  Synchronises `stream`. */
+ * GEMM kernels.  Synchronises `stream`.  On all three model handles *_finalize returns at once when the handle is finalized
+ * already (no parameter, sinusoid table or pack option changed since its last finalize), and *_workspace_bytes returns 0 for a
+ * handle that is not finalized. */
 int  cindm_unet1d_finalize(cindm_unet1d* h, void* stream);
 
-/* Kernel-path selection for this handle (before *_finalize; changing an option un-finalizes the handle, except the run-time options
- * "no_exchange", "recover", "tune").  Every alternative path computes the same function (the parity suite runs all of them); defaults
- * are the fast path.  Keys (round 6: 24; DESIGN.md section 4.6 lists what was removed and why):
+/* Kernel-path selection for this handle.  The options of the three model handles are of three kinds:
+ *   pack options select what *_finalize packs: changing one un-finalizes the handle (the next *_finalize repacks);
+ *   run-time options select among kernels whose operands are packed already: the handle stays finalized --
+ *     cindm_unet1d: "no_exchange", "recover", "tune";  cindm_unet2d: none;  cindm_forceunet: "no_exchange", "recover", "dbg", "stress";
+ *   "range_fallback" is read-only: *_set_option refuses it as an unknown key ("unknown option: range_fallback").
+ * Every alternative path computes the same function (the parity suite runs all of them); defaults are the fast path.  Keys (round 6: 24; DESIGN.md section 4.6 lists what was removed and why):
  *   "mfma_f32" (1 = exact fp32 MFMA kernels instead of the split-fp16 ones), "local_gn", "attn_site", "attn_head" (0 / 1 / 2),
  *   "level0" (master switch of the level kernels), "level1" (0 / 1 / 2 samples per workgroup), "ups_last", "ups_tail", "dconv", "dconv2",
  *   "dresample" (0 / 1 / 2: general kernel / 32 / 16-or-32 columns per workgroup), "l2_prefetch" (launches touch their successor's weights), "ws_alias", "pingpong" (the sample loops keep t / step index /
@@ -352,7 +357,7 @@ int  cindm_unet2d_set_sinusoid_table(cindm_unet2d* h, const float* table, int64_
 /* Weight standardisation (WeightStandardizedConv2d :116-124) folded, MFMA-fragment repack,
  * time path (SinusoidalPosEmb -> Linear -> GELU -> Linear -> per block SiLU -> Linear, :320-326,
  * :205-208) evaluated for every timestep into a device table. */
-/* Kernel-path selection, as cindm_unet1d_set_option.  Keys: "mfma_f32", "la_site", "conv_ws" (1 = persistent
+/* Kernel-path selection, as cindm_unet1d_set_option (every key a pack option).  Keys: "mfma_f32", "la_site", "conv_ws" (1 = persistent
  * wave-specialised 3x3 kernel, 0 = per-tile kernel, 2 / 3 = only the plain-source / GroupNorm-on-load convolutions on
  * it), "ws_nosplit" (0 / 1 / 2: where that kernel splits K over its matrix waves), "tail_h3" (ResnetBlock tails with a res_conv GEMM
  * on the split-fp16 products), "ws_alias" (block-internal temporaries share workspace), "la_wpi" / "la_nsplit" (workgroups per image of
@@ -440,11 +445,11 @@ void cindm_forceunet_destroy(cindm_forceunet* h);
 int  cindm_forceunet_num_params(const cindm_forceunet* h);
 int  cindm_forceunet_param_info(const cindm_forceunet* h, int idx, char* name, int name_cap, int64_t shape[4], int* ndim);
 int  cindm_forceunet_set_param(cindm_forceunet* h, const char* key, const float* src, int64_t numel, int on_device);
-/* Kernel-path options of a handle (as cindm_unet1d_set_option; take effect at the next finalize): "h3" = 0 keeps the
+/* Kernel-path options of a handle (as cindm_unet1d_set_option; pack options take effect at the next finalize): "h3" = 0 keeps the
  * forward 3x3 convolutions, "h3_bwd" = 0 the input-gradient ones, on the exact fp32 MFMA kernel instead of the
  * split-fp16 one (both paths meet the 2e-5 parity bound); "auto_range" = 0 skips the calibration forward of the range
  * rule; "range_fallback" (read-only) = 1 when that forward switched the handle to the fp32 convolutions; "stress" > 0:
- * pseudo-random delays before the producer -> consumer hand-overs of the persistent convolution kernel (race tests);
+ * pseudo-random delays before the producer -> consumer hand-overs of the persistent convolution kernel (race tests; run-time);
  * "la_fused" (0 = LinearAttention sites layer by layer), "gn_bwd_fused" (0 / 1 / 2: the GroupNorm + SiLU derivative), "ws_nosplit",
  * and the run-time options "no_exchange", "recover", "dbg". */
 int  cindm_forceunet_set_option(cindm_forceunet* h, const char* key, int32_t value);

@@ -149,6 +149,35 @@ def test_range_rule_on_the_callers_first_batch(device):
     assert m3.get_option("range_fallback") == 3 and d.last_chain_info()["range_fallback"] == 3
 
 
+def test_range_escalation_is_a_property_of_the_pack(device):
+    """The escalation of the range rule on the caller's data belongs to the pack it repacked: run-time options (no_exchange,
+    recover) leave `range_fallback` at 3 and the guard checked; new weights (sync_weights(force=True)) or an option that selects
+    what is packed finalize the handle again, which re-arms the guard, and the next checked forward escalates again.  The
+    escalated re-run takes a workspace sized for the fp32 plan."""
+    import warnings
+    sd = _scaled()
+    x = torch.randn((3, 24, 8), generator=torch.Generator().manual_seed(5)) * 1.0e6
+    ref = O.unet1d_forward(sd, x, torch.full((3,), 77))
+    xd, td = x.to(device), torch.full((3,), 77, device=device)
+    m = _model(device, sd)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        out = m(xd, td)
+    assert m.get_option("range_fallback") == 3 and rel(out, ref) < TOL_FWD
+    assert m._ws is not None and m._ws.numel() >= cindm_amd._ffi.lib().cindm_unet1d_workspace_bytes(m._h, 3)
+    for key, value in (("no_exchange", 1), ("no_exchange", 0), ("recover", 0), ("recover", 1)):
+        m.set_option(key, value)
+        assert m.get_option("range_fallback") == 3 and not m.range_guard_pending(), (key, value)
+    assert rel(m(xd, td), ref) < TOL_FWD and m.get_option("range_fallback") == 3
+    for rearm in (lambda: m.sync_weights(force=True), lambda: m.set_option("ws_alias", 0)):
+        rearm()
+        assert m.get_option("range_fallback") == 0 and m.range_guard_pending()
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            out = m(xd, td)
+        assert m.get_option("range_fallback") == 3 and rel(out, ref) < TOL_FWD
+
+
 @pytest.mark.parametrize("scale,fallback", [(4.0, (0,)), (1.0e-4, (1,))])
 def test_weight_scale_2d_vs_oracle(device, scale, fallback):
     sd = O.synth_state_dict_2d(O.unet2d_param_shapes(64, (1, 2), 21), 0)

@@ -136,6 +136,59 @@ def test_constructor_validation_2d_and_force():
     cindm_amd.ForceUnet(dim=64, dim_mults=(1, 2, 4, 8), channels=4, image_size=128)  # four levels: 128 -> ... -> 16 (256 tokens)
 
 
+# every option key of each handle with its default (include/cindm_hip.h, section "Kernel-path options")
+OPTION_DEFAULTS = {
+    "unet1d": {"mfma_f32": 0, "local_gn": 1, "attn_site": 1, "level0": 1, "level1": 1, "ups_last": 1, "ups_tail": 1, "attn_head": 1,
+               "dconv": 1, "ws_alias": 1, "pingpong": 1, "dresample": 2, "dconv2": 1, "l2_prefetch": 1, "fuse_gather": 1,
+               "fuse_update": 1, "taps": 0, "recover": 1, "no_exchange": 0, "tune": 0, "stress": 0, "auto_range": 1,
+               "range_fallback": 0, "dbg": 0},
+    "unet2d": {"mfma_f32": 0, "la_site": 1, "ws_alias": 1, "tail_h3": 1, "la_nsplit": 8, "la_wpi": 32, "ws_nosplit": 2, "conv_ws": 1,
+               "stress": 0, "auto_range": 1, "range_fallback": 0, "dbg2": 0},
+    "forceunet": {"h3": 1, "h3_bwd": 1, "auto_range": 1, "range_fallback": 0, "stress": 0, "la_fused": 1, "gn_bwd_fused": 2,
+                  "ws_nosplit": 2, "no_exchange": 0, "recover": 1, "dbg": 0},
+}
+
+
+def _handles():
+    return {"unet1d": cindm_amd.TemporalUnet1D(24, 8, False, attention=True),
+            "unet2d": cindm_amd.Unet(dim=64, dim_mults=(1, 2), channels=21),
+            "forceunet": cindm_amd.ForceUnet(dim=64, dim_mults=(1, 2, 4, 8), channels=4)}
+
+
+def test_option_tables_round_trip(monkeypatch):
+    """Each handle reports every key's default (no device: the library's get / set entry points, not the Python get_option, which
+    synchronises the weights first); every key but the read-only "range_fallback" can be written and read back."""
+    for k in list(os.environ):
+        if k.startswith("CINDM_"):
+            monkeypatch.delenv(k)
+    L = _ffi.lib()
+    v = C.c_int32()
+    for prefix, m in _handles().items():
+        get, put = getattr(L, f"cindm_{prefix}_get_option"), getattr(L, f"cindm_{prefix}_set_option")
+        for key, default in OPTION_DEFAULTS[prefix].items():
+            assert get(m._h, key.encode(), C.byref(v)) == 0 and v.value == default, (prefix, key, v.value)
+            if key == "range_fallback":
+                continue
+            for val in (default + 1, default):
+                assert put(m._h, key.encode(), val) == 0, (prefix, key)
+                assert get(m._h, key.encode(), C.byref(v)) == 0 and v.value == val, (prefix, key)
+
+
+def test_read_only_and_unknown_options_are_refused():
+    """Writing "range_fallback" is refused on all three handles with the text of an unknown key, and so is an unknown key;
+    the value stays as it was."""
+    L = _ffi.lib()
+    v = C.c_int32()
+    for prefix, m in _handles().items():
+        get, put = getattr(L, f"cindm_{prefix}_get_option"), getattr(L, f"cindm_{prefix}_set_option")
+        for key in (b"range_fallback", b"no_such_switch"):
+            assert put(m._h, key, 1) != 0 and L.cindm_last_error() == b"unknown option: " + key, (prefix, key)
+        assert get(m._h, b"no_such_switch", C.byref(v)) != 0 and L.cindm_last_error() == b"unknown option: no_such_switch"
+        assert get(m._h, b"range_fallback", C.byref(v)) == 0 and v.value == 0
+        with pytest.raises(_ffi.CindmError, match="unknown option: range_fallback"):
+            m.set_option("range_fallback", 1)
+
+
 def test_diffusion_buffers_and_schedule(gold_dir):
     g = np.load(os.path.join(gold_dir, "schedule.npz"))
     m = cindm_amd.TemporalUnet1D(24, 8, False, attention=True)
@@ -195,7 +248,7 @@ def test_no_allocation_outside_create_finalize_destroy():
     allowed = re.compile(r"(_create|_destroy|_finalize|finalize_pack|_phase_prof_enable)$")
     csrc = os.path.join(ROOT, "cindm_amd", "csrc")
     seen = 0
-    for fn in ("cindm_hip.hip", "unet2d_host.inc", "forceunet_host.inc"):
+    for fn in ("cindm_hip.hip", "unet2d_host.inc", "forceunet_host.inc", "handle_core.inc"):
         cur = None
         for i, line in enumerate(open(os.path.join(csrc, fn)).read().split("\n"), 1):
             if line and not line[0].isspace() and line[0] not in "}#/" and "(" in line:
