@@ -136,6 +136,8 @@ SIGNATURES = {
     "cindm_ddpm2d_sample": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _u64, _i64, _i32, _i32, _vp, _sz, _vp,
                                       _i32]),
     "cindm_ddpm2d_predict": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cindm_ddpm2d_sample_ddim": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp, _vp, _u64, _i64,
+                                           _vp, _sz, _vp, _i32]),
     "cindm_fill_noise2d": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _u64, _i64, _i32, _vp]),
     "cindm_forceunet_create": (C.c_int, [C.POINTER(ForceUnetDesc), C.POINTER(_vp)]),
     "cindm_forceunet_destroy": (None, [_vp]),

@@ -22,7 +22,7 @@ from torch import nn
 
 from . import _ffi
 from .objectives import PointObjective
-from .schedule import make_schedule
+from .schedule import ddim_schedule, make_schedule
 
 ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"])
 
@@ -589,27 +589,8 @@ class GaussianDiffusion1D(nn.Module):
     # ------------------------------------------------------------------ DDIM
     def ddim_schedule(self):
         """(times [S+1] descending to -1, coefs [S,3] = (sqrt(alpha_next), c, sigma)) of ddim_sample (:1743-1777), in the
-        reference's fp32 tensor arithmetic (time_next = -1 indexes the last table entry, as the reference's negative
-        index does; that step returns x_start and its coefficients are not used)."""
-        T, S, eta = self.num_timesteps, self.sampling_timesteps, self.ddim_sampling_eta
-        # the table is a pure function of (T, S, eta, alphas_cumprod): built once (250 iterations of scalar tensor arithmetic and
-        # a device -> host copy cost 7 ms per ddim_sample call, 8 % of a 250-step chain of 256 designs)
-        key = (T, S, float(eta), self.alphas_cumprod.data_ptr(), self.alphas_cumprod._version)
-        cached = getattr(self, "_ddim_cache", None)
-        if cached is not None and cached[0] == key:
-            return list(cached[1]), cached[2].clone()
-        times = torch.linspace(-1, T - 1, steps=S + 1)
-        times = list(reversed(times.int().tolist()))
-        ac = self.alphas_cumprod.detach().to("cpu", torch.float32)
-        coefs = torch.zeros((S, 3), dtype=torch.float32)
-        for i, (time, time_next) in enumerate(zip(times[:-1], times[1:])):
-            alpha, alpha_next = ac[time], ac[time_next]
-            sigma = eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
-            c = (1 - alpha_next - sigma ** 2).sqrt()
-            coefs[i, 0], coefs[i, 1], coefs[i, 2] = alpha_next.sqrt(), c, sigma
-        coefs = torch.nan_to_num(coefs, nan=0.0)
-        self._ddim_cache = (key, list(times), coefs.clone())
-        return times, coefs
+        reference's fp32 tensor arithmetic (schedule.ddim_schedule)."""
+        return ddim_schedule(self)
 
     @torch.no_grad()
     def ddim_sample(self, shape, cond, n_composed=None, clip_denoised=True, compose_start_step=4, compose_n_bodies=2,

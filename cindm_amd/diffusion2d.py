@@ -8,7 +8,11 @@ What runs where
     step replayed per timestep), the state staying in the library's channel-last layout for the whole chain;
   * ``design_fn`` is a user Python callable returning a gradient tensor (:813); it is evaluated between library
     calls, exactly where the reference evaluates it.
-Training, DDIM and self-conditioning are outside this build's scope and raise NotImplementedError.
+  * DDIM (``sampling_timesteps < timesteps``, ``ddim_sample``) without ``design_fn`` is ONE call too
+    (``cindm_ddpm2d_sample_ddim``: U-Net + one element-wise DDIM update per captured step, t and the step index
+    advanced on the device).  The reference's own 2-D DDIM cannot run; the semantics are defined in ``ddim_sample``.
+Training, self-conditioning, guided DDIM, DDIM with share_noise=False and return_all_timesteps are outside this
+build's scope and raise NotImplementedError.
 """
 import ctypes as C
 from collections import namedtuple
@@ -17,7 +21,7 @@ import torch
 from torch import nn
 
 from . import _ffi
-from .schedule import make_schedule
+from .schedule import ddim_schedule, make_schedule
 from .unet2d import from_device_layout, to_device_layout
 
 
@@ -89,6 +93,7 @@ class GaussianDiffusion(nn.Module):
         self._h = None
         self._tab_sig = None
         self._ws = None
+        self._ddim_tab = None
 
     def __del__(self):
         h = self.__dict__.get("_h")
@@ -353,18 +358,86 @@ class GaussianDiffusion(nn.Module):
             img, _ = self.p_sample(shape, img, t, None, design_fn=design_fn, design_guidance=design_guidance, noise=nz)
         return img.reshape(B, nb, Cc, H, W)
 
-    def ddim_sample(self, *a, **k):
-        raise NotImplementedError("DDIM sampling is out of scope (SURVEY.md section 8)")
+    # ------------------------------------------------------------------ DDIM
+    def ddim_schedule(self):
+        """(times [S+1] descending to -1, coefs [S,3] = (sqrt(alpha_next), c, sigma)) of ddim_sample, in the reference's fp32
+        tensor arithmetic -- the 1-D path's schedule (schedule.ddim_schedule)."""
+        return ddim_schedule(self)
+
+    @torch.no_grad()
+    def ddim_sample(self, shape, design_fn=None, design_guidance="standard", return_all_timesteps=False, *, noise=None, seed=0,
+                    sample_offset=0, use_graph=True, init_img=None, step_range=None, device=None):
+        """DDIM sampling of the 2-D path (:910-949; the reference's own body cannot run, so this build defines it from its
+        working pieces).  Returns [B, nb, C, H, W].  With (times, coefs) = ddim_schedule(), for each pair (t, t_next):
+        (pred_noise, x_start) = model_predictions(x, t, clip_x_start=True, rederive_pred_noise=True, share_noise=True);
+        x = x_start if t_next < 0, else x_start * sqrt(alpha_next) + c * pred_noise + sigma * z, with z = sample_noise (state
+        channels shared over the boundary copies of a design, boundary channels per image).  x_T is sample_noise too.
+        The whole loop is one library call (``cindm_ddpm2d_sample_ddim``: one captured HIP graph step replayed per DDIM step).
+        Build-only keywords: ``noise`` = a NoiseTape2D whose ``step_*`` rows are indexed by the DDIM STEP index; otherwise x_T
+        and z come from the library's counter-based generator keyed by (seed, sample_offset + design); ``init_img`` +
+        ``step_range=(i0, i1)`` run DDIM steps i0 .. i1-1 from a given state (teacher-forced segments for parity tests: the
+        deterministic sampler amplifies a 1e-6 difference of the U-Net to 1e-3 over long chains).
+        Refused (NotImplementedError): ``design_fn`` (the reference has no working guided 2-D DDIM), share_noise False and
+        ``return_all_timesteps``."""
+        if design_fn is not None:
+            raise NotImplementedError("DDIM with design_fn: the reference has no working guided 2-D DDIM (its ddim_sample takes no "
+                                      "design_fn); sample with sampling_timesteps == timesteps for guidance")
+        if not self.share_noise:
+            raise NotImplementedError("DDIM with share_noise=False: the reference's 2-D DDIM shares the predicted noise "
+                                      "(model_predictions share_noise=True); there is no DDIM form of the shared posterior mean")
+        if return_all_timesteps:
+            raise NotImplementedError("return_all_timesteps is outside this build's scope (the reference's 2-D sampler does not build it)")
+        B, nb, Cc, H, W = shape
+        device = device or self.betas.device
+        if device.type != "cuda":
+            raise _ffi.CindmError("sampling needs a ROCm device; there is no CPU execution path")
+        cp = self.model.padded_channels
+        L = _ffi.lib()
+        times, coefs = self.ddim_schedule()
+        i0, i1 = (0, len(times) - 1) if step_range is None else step_range
+        if not 0 <= i0 < i1 <= len(times) - 1:
+            raise ValueError(f"step_range must satisfy 0 <= i0 < i1 <= {len(times) - 1}")
+        times, coefs = times[i0:i1 + 1], coefs[i0:i1].contiguous()
+        S = len(times) - 1
+        if init_img is not None:
+            x = to_device_layout(init_img.reshape(B * nb, Cc, H, W).to(device, torch.float32), cp)
+        elif noise is not None:
+            x = to_device_layout(torch.cat([noise.init[0].expand(-1, nb, -1, -1, -1), noise.init[1]], dim=2)
+                                 .reshape(B * nb, Cc, H, W).to(device, torch.float32), cp)
+        else:
+            x = torch.empty((B * nb, H * W, cp), dtype=torch.float32, device=device)
+            with torch.cuda.device(device):
+                _ffi.check(L.cindm_fill_noise2d(_ffi.ptr(x), B, nb, H * W, Cc, cp, seed, sample_offset, self.num_timesteps,
+                                                _ffi.current_stream(device)))
+        ns = nbnd = None
+        if noise is not None:
+            if (noise.step_state.shape[0] < i1 or noise.step_boundary.shape[0] < i1 or tuple(noise.step_state.shape[1:]) != (B, 1, Cc - 3, H, W)
+                    or tuple(noise.step_boundary.shape[1:]) != (B, nb, 3, H, W)):
+                raise ValueError(f"the noise tape needs step_state [>= {i1}, {B}, 1, {Cc - 3}, {H}, {W}] and step_boundary "
+                                 f"[>= {i1}, {B}, {nb}, 3, {H}, {W}] (rows indexed by the DDIM step)")
+            ns = _state_cl(noise.step_state[i0:i1].to(device, torch.float32))
+            nbnd = _boundary_cl(noise.step_boundary[i0:i1].to(device, torch.float32))
+        h, ws = self._prepare(B * nb, device)
+        # the per-step device tables live in a caller tensor (the library allocates nothing): [S][4] coefficients + [S] time_next
+        if self._ddim_tab is None or self._ddim_tab.numel() < 5 * S or self._ddim_tab.device != device:
+            self._ddim_tab = torch.empty(5 * max(S, self.sampling_timesteps), dtype=torch.float32, device=device)
+        tab = self._ddim_tab
+        tarr = (C.c_int32 * (S + 1))(*times)
+        with torch.cuda.device(device):
+            _ffi.check(L.cindm_ddpm2d_sample_ddim(h, self.model._h, _ffi.ptr(x), B, nb, self._share_mode(), S, tarr, _ffi.ptr(coefs),
+                                                  _ffi.ptr(tab), tab.numel() * 4, _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset,
+                                                  _ffi.ptr(ws), ws.numel(), _ffi.current_stream(device), int(use_graph)))
+        return from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W)
 
     @torch.no_grad()
     def sample(self, batch_size=16, design_fn=None, design_guidance="standard", num_boundaries=1,
                return_all_timesteps=False, **kw):
-        """:960-963."""
-        if self.is_ddim_sampling:
-            return self.ddim_sample()
+        """:960-963 (``sampling_timesteps < timesteps``: ddim_sample)."""
         S = self.image_size
-        return self.p_sample_loop((batch_size, num_boundaries, self.channels, S, S), design_fn, design_guidance,
-                                  return_all_timesteps=return_all_timesteps, **kw)
+        shape = (batch_size, num_boundaries, self.channels, S, S)
+        if self.is_ddim_sampling:
+            return self.ddim_sample(shape, design_fn, design_guidance, return_all_timesteps=return_all_timesteps, **kw)
+        return self.p_sample_loop(shape, design_fn, design_guidance, return_all_timesteps=return_all_timesteps, **kw)
 
     def forward(self, *a, **k):
         raise NotImplementedError("training (p_losses) is out of this build's scope (SURVEY.md section 8)")

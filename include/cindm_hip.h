@@ -420,6 +420,25 @@ int  cindm_ddpm2d_sample(cindm_ddpm1d* sched, cindm_unet2d* u, float* x, int64_t
                          const float* noise_boundary_steps, uint64_t seed, int64_t sample_offset,
                          int32_t t_start, int32_t t_end, void* ws, size_t ws_bytes, void* stream,
                          int32_t use_graph);
+/* DDIM loop of the 2-D path (GaussianDiffusion.ddim_sample, design_fn == None, share_noise True): n_steps updates
+ * in place on x at times[0] > times[1] > ... > times[n_steps] >= -1, each
+ *   (eps, x0) = model_predictions(x, t, clip_x_start=1, rederive_pred_noise=1, share_noise=1)   (:727-754)
+ *   x = times[i+1] < 0 ? x0 : x0 * sqrt(alpha_next) + c * eps + sigma * z
+ * with z shared over the boundaries for the state channels (sample_noise :775-785).  times [n_steps + 1]
+ * and coefs [n_steps][3] = (sqrt(alpha_next), c, sigma) are HOST arrays computed by the caller (as for
+ * cindm_ddpm1d_sample_ddim); the library copies them to tab, a caller-owned DEVICE buffer of at least
+ * n_steps * 5 * 4 bytes, 16-byte aligned, that must stay alive until the call's work has finished.
+ * use_average_share: bit 0 mean / sum, bits 4-5 objective (bit 1, share_noise False, is refused).
+ * noise_*_steps, when given, are indexed by the DDIM STEP index: [n_steps, B, H*W, C-3] /
+ * [n_steps, B*nb, H*W, 3]; else z comes from the counter-based generator (seed, sample_offset + b, t).
+ * One captured HIP graph (U-Net + one element-wise update + the step counter) replayed per step when
+ * use_graph; ws as cindm_ddpm2d_step. */
+int  cindm_ddpm2d_sample_ddim(cindm_ddpm1d* sched, cindm_unet2d* u, float* x, int64_t B, int32_t nb,
+                              int32_t use_average_share, int32_t n_steps, const int32_t* times,
+                              const float* coefs, void* tab, size_t tab_bytes,
+                              const float* noise_state_steps, const float* noise_boundary_steps,
+                              uint64_t seed, int64_t sample_offset, void* ws, size_t ws_bytes,
+                              void* stream, int32_t use_graph);
 /* x_T for the 2-D path (sample_noise :775-785, :895): state channels shared over the boundaries of a design. */
 int  cindm_fill_noise2d(float* x, int64_t B, int32_t nb, int32_t hw, int32_t channels,
                         int32_t padded_channels, uint64_t seed, int64_t sample_offset,
