@@ -2506,6 +2506,27 @@ extern "C" int cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_un
     });
 }
 
+// The DDIM loop's per-step tables ([n_steps][4] floats, then [n_steps] ints) go to their slice of the caller's workspace
+// (step_layout's off_ddim); shared by the DDIM loop and the autoregressive rollout, whose segments all read the same tables.
+static int upload_ddim_tables(const cindm_ddpm1d* h, const cindm_unet1d* pair, int32_t n_steps, const int32_t* times,
+                              const float* coefs, float* ddim_buf, hipStream_t stream, int** tn_out) {
+    REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    for (int i = 0; i < n_steps; ++i) REQUIRE(times[i] >= 0 && times[i] < h->T && times[i + 1] < times[i] && times[i + 1] >= -1, "bad DDIM time schedule");
+    REQUIRE(n_steps <= pair->d.timesteps, "more DDIM steps than the U-Net's timesteps");
+    std::vector<float> tabv((size_t)n_steps * 4, 0.f);
+    std::vector<int> tnv(n_steps);
+    for (int i = 0; i < n_steps; ++i) {
+        tabv[4 * i] = coefs[3 * i]; tabv[4 * i + 1] = coefs[3 * i + 1]; tabv[4 * i + 2] = coefs[3 * i + 2];
+        tnv[i] = times[i + 1];
+    }
+    int* tn_dev = reinterpret_cast<int*>(ddim_buf + (size_t)n_steps * 4);
+    HIPCHK(hipMemcpyAsync(ddim_buf, tabv.data(), tabv.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(tn_dev, tnv.data(), tnv.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+    HIPCHK(hipStreamSynchronize(stream));            // the host vectors go out of scope
+    *tn_out = tn_dev;
+    return 0;
+}
+
 extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, const cindm_compose_desc* c,
                                         float* x, const float* cond, int32_t n_steps, const int32_t* times,
                                         const float* coefs, const float* noise_steps, uint64_t seed, int64_t sample_offset,
@@ -2520,20 +2541,10 @@ extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cin
         HIPCHK(hipDeviceSynchronize());
         stream = h->own;
     }
-    // the per-step tables ([n_steps][4] floats, then [n_steps] ints) and the x_T snapshot live in the caller's workspace
-    REQUIRE(n_steps <= pair->d.timesteps, "more DDIM steps than the U-Net's timesteps");
-    float* xT = nullptr; float* ddim_buf = nullptr;
+    // the per-step tables and the x_T snapshot live in the caller's workspace
+    float* xT = nullptr; float* ddim_buf = nullptr; int* tn_dev = nullptr;
     if (chain_slices(pair, uncond, c, B, ws, ws_bytes, &xT, &ddim_buf) != 0) return -1;
-    std::vector<float> tabv((size_t)n_steps * 4, 0.f);
-    std::vector<int> tnv(n_steps);
-    for (int i = 0; i < n_steps; ++i) {
-        tabv[4 * i] = coefs[3 * i]; tabv[4 * i + 1] = coefs[3 * i + 1]; tabv[4 * i + 2] = coefs[3 * i + 2];
-        tnv[i] = times[i + 1];
-    }
-    int* tn_dev = reinterpret_cast<int*>(ddim_buf + (size_t)n_steps * 4);
-    HIPCHK(hipMemcpyAsync(ddim_buf, tabv.data(), tabv.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(tn_dev, tnv.data(), tnv.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream));            // the host vectors go out of scope
+    if (upload_ddim_tables(h, pair, n_steps, times, coefs, ddim_buf, stream, &tn_dev) != 0) return -1;
     const int Ltot = state_len(pair, c);
     const int F = c->n_bodies * 4;
     StepIO io{};
@@ -2557,6 +2568,71 @@ extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cin
         return replay_steps(h, K.k, stream, n_steps, use_graph,
                             [&](int q) { StepIO it = io; it.parity = q; return run_step(h, pair, uncond, c, it, 0, h->t_dev, B, ws, ws_bytes, stream); },
                             pair, un, pp);
+    });
+}
+
+// Autoregressive time composition (autoregress_time_compose_sample, model/diffusion_1d.py:2240-2327): n_seg unguided DDIM chains, each
+// from a fresh x_T and conditioned on the last Lc rows of the previous one.  The whole rollout is ONE chain for the recovery and the
+// in-flight registry: its body draws segment 0's x_T and copies the caller's cond into cond_buf itself, so it is a pure function of
+// its inputs and a time-out re-runs all of it once on the exchange-free kernels.  Per segment: start_loop with that segment's seed,
+// the DDIM step replayed n_steps times (io.cond = cond_buf: a fixed address, and the seed lives in the device counter -- one captured
+// graph serves every segment), then autoregress_handover_kernel (out slice, next cond, next x_T).
+extern "C" int cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, const cindm_compose_desc* c,
+                                               float* x, const float* cond, float* cond_buf, float* out, int32_t n_seg,
+                                               int32_t n_steps, const int32_t* times, const float* coefs, const uint64_t* seeds,
+                                               const float* init_tape, const float* noise_steps, int64_t sample_offset, int64_t B,
+                                               void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
+    REQUIRE(h && pair && c && x && cond && cond_buf && out && times && coefs && seeds, "null argument");
+    REQUIRE(c->mode == CINDM_COMPOSE_PLAIN || c->mode == CINDM_COMPOSE_MULTIBODY, "the rollout runs the plain (or multibody) prediction");
+    REQUIRE(c->cond_steps >= 1, "conditioned_steps == 0: the reference's img[:, -0:] hands over the whole state and its slice assignment fails");
+    REQUIRE(n_seg >= 1, "n_seg must be >= 1");
+    const int R = state_len(pair, c), Lc = c->cond_steps, F = c->n_bodies * 4;
+    REQUIRE(R >= Lc, "rollout_steps < conditioned_steps: the next segment's condition would be shorter than the model's horizon needs");
+    for (const void* p : {(const void*)x, (const void*)cond_buf, (const void*)out, (const void*)init_tape})
+        REQUIRE(((uintptr_t)p & 15) == 0, "x, cond_buf, out and init_tape must be 16-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (use_graph && stream == nullptr) {
+        if (!h->own) HIPCHK(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
+        HIPCHK(hipDeviceSynchronize());
+        stream = h->own;
+    }
+    float* xT = nullptr; float* ddim_buf = nullptr; int* tn_dev = nullptr;
+    if (chain_slices(pair, uncond, c, B, ws, ws_bytes, &xT, &ddim_buf) != 0) return -1;
+    if (upload_ddim_tables(h, pair, n_steps, times, coefs, ddim_buf, stream, &tn_dev) != 0) return -1;
+    const int64_t n_state = B * (int64_t)R * F;
+    StepIO io{};
+    io.x = x; io.cond = cond_buf; io.x_out = x;
+    io.noise_t_stride = n_state; io.add_noise = 1;
+    io.dec_t = 1; io.ddim_tab = ddim_buf; io.ddim_tnext = tn_dev;
+    io.dyn = reinterpret_cast<const unsigned long long*>(h->t_dev + 16);
+    const bool pp = pair->O("pingpong") != 0;
+    io.pingpong = pp ? 1 : 0;
+    cindm_unet1d* un = c->mode == CINDM_COMPOSE_MULTIBODY ? uncond : nullptr;
+    const unsigned hblocks = (unsigned)((n_state / 4 + 255) / 256);
+    return run_chain_with_recovery(h, pair, un, x, xT, (size_t)n_state, stream, [&]() -> int {
+        if (prepare_step_ws(pair, uncond, c, B, ws, ws_bytes, stream) != 0) return -1;
+        if (init_tape) HIPCHK(hipMemcpyAsync(x, init_tape, (size_t)n_state * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        else hipLaunchKernelGGL(fill_normal_kernel, dim3((unsigned)((n_state + 255) / 256)), dim3(256), 0, stream,
+                                x, B, (int64_t)R * F, seeds[0], sample_offset, (uint32_t)h->T);
+        HIPCHK(hipMemcpyAsync(cond_buf, cond, (size_t)B * Lc * F * sizeof(float), hipMemcpyDeviceToDevice, stream));
+        for (int k = 0; k < n_seg; ++k) {
+            start_loop(h, pair, uncond, c, (int)times[0], stream, seeds[k], sample_offset);
+            StepIO seg = io;
+            seg.noise = noise_steps ? noise_steps + (size_t)k * n_steps * n_state : nullptr;      // (a tape re-captures per segment)
+            KeyBuilder K;
+            key_common(K, 1, pair, uncond, c, seg, B, ws, ws_bytes);
+            K(pp);
+            const int rc = replay_steps(h, K.k, stream, n_steps, use_graph,
+                                        [&](int q) { StepIO it = seg; it.parity = q; return run_step(h, pair, uncond, c, it, 0, h->t_dev, B, ws, ws_bytes, stream); },
+                                        pair, un, pp);
+            if (rc != 0) return rc;
+            const int has_next = k + 1 < n_seg;
+            hipLaunchKernelGGL(autoregress_handover_kernel, dim3(hblocks), dim3(256), 0, stream, x, out, cond_buf,
+                               (has_next && init_tape) ? init_tape + (size_t)(k + 1) * n_state : (const float*)nullptr,
+                               B, R, F, Lc, k, (int)n_seg, has_next, has_next ? seeds[k + 1] : (uint64_t)0, sample_offset, (uint32_t)h->T);
+            HIPCHK(hipGetLastError());
+        }
+        return 0;
     });
 }
 

@@ -3203,6 +3203,37 @@ __global__ void fill_normal_kernel(float* out, int64_t B, int64_t per, uint64_t 
     out[i] = counter_normal(seed, (uint64_t)(off + b), step, (uint32_t)e);
 }
 
+// Hand-over between two segments of the autoregressive rollout (autoregress_time_compose_sample, model/diffusion_1d.py:2296-2326):
+// segment k's final state x [B, R, F] goes to out[:, k R : (k+1) R] ([B, n_seg R, F]), its last Lc rows become the next
+// segment's condition cond_buf [B, Lc, F], and -- when another segment follows -- x is overwritten with that segment's x_T:
+// next_init [B, R, F] when given, else the draw fill_normal_kernel makes for (seed, off + b, tag, element).  One thread per
+// four elements of x (F % 4 == 0: the four share b and l); each thread only writes what it read, so nothing is ordered
+// between threads.  Every pointer is 16-byte aligned (checked by the caller).
+__global__ void autoregress_handover_kernel(float* __restrict__ x, float* __restrict__ out, float* __restrict__ cond_buf,
+                                            const float* __restrict__ next_init, int64_t B, int R, int F, int Lc, int k,
+                                            int n_seg, int has_next, uint64_t seed, int64_t off, uint32_t tag) {
+    const int64_t per = (int64_t)R * F;
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= B * per) return;
+    const int64_t b = i / per, e = i - b * per;
+    const int l = (int)(e / F), f = (int)(e - (int64_t)l * F);
+    const float4 v = *reinterpret_cast<const float4*>(x + i);
+    *reinterpret_cast<float4*>(out + ((b * n_seg + k) * R + l) * F + f) = v;
+    if (l >= R - Lc) *reinterpret_cast<float4*>(cond_buf + (b * Lc + (l - (R - Lc))) * F + f) = v;
+    if (!has_next) return;
+    float4 z;
+    if (next_init) {
+        z = *reinterpret_cast<const float4*>(next_init + i);
+    } else {       // element by element through counter_normal: bit-identical to fill_normal_kernel's x_T
+        const uint64_t s = (uint64_t)(off + b);
+        z.x = counter_normal(seed, s, tag, (uint32_t)e);
+        z.y = counter_normal(seed, s, tag, (uint32_t)(e + 1));
+        z.z = counter_normal(seed, s, tag, (uint32_t)(e + 2));
+        z.w = counter_normal(seed, s, tag, (uint32_t)(e + 3));
+    }
+    *reinterpret_cast<float4*>(x + i) = z;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Composition: gather U-Net input rows, and scatter-aggregate + DDPM posterior update.
 // (struct ComposeArgs is defined above UpsLastArgs: ups_last_kernel can carry the update of a plain single-model step)

@@ -11,6 +11,9 @@ What runs where
   * DDIM (``sampling_timesteps < timesteps``, ``ddim_sample`` :1724-1804): unguided = ONE library call
     (``cindm_ddpm1d_sample_ddim``, same captured-step replay with per-step coefficient tables); guided (recurrence
     guidance) = library predictions + the user's gradient per step.
+  * autoregressive time composition (``autoregress_time_compose_sample`` :2240-2327): the whole rollout -- every segment's
+    DDIM chain and the hand-over of its tail to the next segment -- is ONE library call (``cindm_ddpm1d_sample_autoregress``,
+    the DDIM step's captured graph replayed for every segment).
 Training (``forward`` / ``p_losses``) and the unreachable ULA/UHMC samplers of the reference are out of this build's
 scope and raise NotImplementedError.
 """
@@ -30,7 +33,9 @@ ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"])
 class NoiseTape:
     """Explicit noise for parity runs, replacing the reference's ``torch.randn`` draws:
     ``init`` [B,L,F] (x_T, :1673 / :1987); ``step`` [T,B,L,F] indexed by timestep (:1281 / :1118);
-    ``recur`` [T,R,B,L,F] relaxation draws (:1365); ``cond`` [T,B,Lc,F] inpainting draws (:1717)."""
+    ``recur`` [T,R,B,L,F] relaxation draws (:1365); ``cond`` [T,B,Lc,F] inpainting draws (:1717).
+    ``autoregress_time_compose_sample`` reads a leading SEGMENT index: ``init`` [K,B,R,F] (each segment's x_T, :2299 /
+    :2264) and ``step`` [K,S,B,R,F] (segment k's draw of DDIM step i, :2315 / :2280)."""
 
     def __init__(self, init, step, recur=None, cond=None):
         self.init, self.step, self.recur, self.cond = init, step, recur, cond
@@ -42,6 +47,40 @@ class NoiseTape:
 
 def _exists(x):
     return x is not None
+
+
+_SEGMENT_SEED_STRIDE = 0x9E3779B97F4A7C15
+
+
+def autoregress_segment_seeds(seed, n_seg):
+    """The seeds of the autoregressive rollout's segments: seed_k = (seed + k * 0x9E3779B97F4A7C15) mod 2**64, so seed_0 = seed
+    and a one-segment rollout is ``ddim_sample(seed=seed)``.  Segment k draws its x_T and its step noise as
+    ``ddim_sample(seed=seed_k)`` does."""
+    return [(int(seed) + k * _SEGMENT_SEED_STRIDE) % (1 << 64) for k in range(n_seg)]
+
+
+def autoregress_segments(conditioned_steps, rollout_steps, n_composed, is_single_step_prediction=False, prediction_steps=40):
+    """Number of segments of ``autoregress_time_compose_sample`` (:2252-2259 / :2296): n_composed + 1, or
+    ceil(prediction_steps / conditioned_steps) for the single-step variant.  Raises for the cases where the reference fails."""
+    Lc, R = int(conditioned_steps), int(rollout_steps)
+    if Lc == 0:
+        raise NotImplementedError("autoregress_time_compose_sample with conditioned_steps == 0: the reference hands img[:, -0:] (the whole "
+                                  "state) over as the next condition and its slice assignment into the output fails on shape")
+    if R < Lc:
+        raise NotImplementedError(f"autoregress_time_compose_sample with rollout_steps (image_size) {R} < conditioned_steps {Lc}: the next "
+                                  "segment's condition img[:, -conditioned_steps:] is shorter than the model's horizon needs")
+    if not is_single_step_prediction:
+        if int(n_composed) < 0:
+            raise ValueError(f"n_composed must be >= 0, got {n_composed}")
+        return int(n_composed) + 1
+    P = int(prediction_steps)
+    if P < 1:
+        raise ValueError(f"prediction_steps must be >= 1, got {P}")
+    K = -(-P // Lc)
+    if K * R != P:
+        raise ValueError(f"single-step prediction: ceil(prediction_steps / conditioned_steps) * rollout_steps = {K} * {R} != prediction_steps "
+                         f"{P}: the reference's last slice assignment into its [B, {P}, F] output fails on shape")
+    return K
 
 
 class GaussianDiffusion1D(nn.Module):
@@ -179,10 +218,12 @@ class GaussianDiffusion1D(nn.Module):
         return {"recovered": bool(info[0]), "exchange_free_up_front": bool(info[1]), "chains_in_flight": int(info[2]),
                 "range_fallback": int(info[3])}
 
-    def _chain(self, img, desc, call):
+    def _chain(self, img, desc, call, result=None):
         """One library chain over ``img`` (in place): ``call(h, un, ws)`` issues it.  The FIRST chain after a weight synchronisation
         also carries the range rule on the caller's own data (TemporalUnet1D.range_guard): x_T is kept, the designs are
-        checked once, and a chain that came back inf / nan from the split-fp16 kernels is repeated on the exact fp32-MFMA kernels."""
+        checked once, and a chain that came back inf / nan from the split-fp16 kernels is repeated on the exact fp32-MFMA kernels.
+        ``result``: the tensor the chain hands back, when that is not ``img`` (the autoregressive rollout's output; its ``call``
+        draws every x_T itself and re-runs from the caller's condition) -- it is what is checked and returned."""
         device, B = img.device, img.shape[0]
         h, un, ws = self._prepare(desc, B, device)
         models = [self.model] + ([self.model_unconditioned] if un is not None else [])
@@ -195,9 +236,10 @@ class GaussianDiffusion1D(nn.Module):
             img.copy_(x0)
             call(*self._prepare(desc, B, device))        # (the fp32 plan sizes its own workspace)
             self._note_chain()
+        res = img if result is None else result
         for m in pend:
-            m.range_guard(lambda: img, rerun, device)
-        return img
+            m.range_guard(lambda: res, rerun, device)
+        return res
 
     def _note_chain(self):
         info = self.last_chain_info()
@@ -670,3 +712,56 @@ class GaussianDiffusion1D(nn.Module):
         if self._timed_out(desc, device):
             img = self._rerun_exchange_free(chain, desc, device)
         return img
+
+    # ------------------------------------------------------------------ autoregressive time composition
+    @torch.no_grad()
+    def autoregress_time_compose_sample(self, batch_size, cond, n_composed, is_single_step_prediction=False, prediction_steps=40,
+                                        *, noise=None, seed=None, sample_offset=0, use_graph=True):
+        """:2240-2327 (the default ``--time_compose_method autoregress`` of inference/inference_1d_composing_time_steps.py, :179-213).
+        K segments -- n_composed + 1, or ceil(prediction_steps / conditioned_steps) with ``is_single_step_prediction`` --
+        each an unguided DDIM chain on a fresh x_T [B, rollout_steps, F] conditioned on ``cond`` (segment 0) or on the last
+        conditioned_steps rows of the previous segment; exactly ``ddim_sample(design_fn=None)``'s prediction and update per step
+        (:2266-2287 / :2301-2322; clip_x_start, eta = ddim_sampling_eta).  Returns [B, K * rollout_steps, F], segment k at
+        rows k R .. (k+1) R.  ``batch_size`` is not used (B = cond.shape[0]), as in the reference.
+        Build-only keywords as ``ddim_sample``: ``seed`` (segment k uses ``autoregress_segment_seeds(seed, K)[k]``, so segment k
+        equals ``ddim_sample(seed=seed_k)`` on its condition), ``sample_offset``, ``use_graph``, ``noise`` = NoiseTape(init
+        [K,B,R,F], step [K,S,B,R,F]).  The whole rollout is one library call (``cindm_ddpm1d_sample_autoregress``)."""
+        K = autoregress_segments(self.conditioned_steps, self.rollout_steps, n_composed, is_single_step_prediction,
+                                 prediction_steps)
+        Lc, R = self.conditioned_steps, self.rollout_steps
+        if cond is None or cond.dim() != 3 or cond.shape[1] != Lc:
+            raise ValueError(f"cond must be [B, conditioned_steps = {Lc}, F], got {None if cond is None else tuple(cond.shape)}")
+        if cond.shape[2] != self.channels:
+            raise ValueError(f"cond has {cond.shape[2]} features, the model's transition_dim is {self.channels}")
+        device = self.betas.device
+        if device.type != "cuda":
+            raise _ffi.CindmError("GaussianDiffusion1D is on the CPU: move it to a ROCm device; there is no CPU execution path")
+        if seed is None and noise is None:
+            seed = self._draw_seed()
+        seed = 0 if seed is None else int(seed)
+        B, F = cond.shape[0], cond.shape[2]
+        shape = (B, R, F)
+        times, coefs = self.ddim_schedule()
+        S = len(times) - 1
+        init = step = None
+        if noise is not None:
+            noise = noise.to(device)
+            init, step = noise.init, noise.step
+            if init is None or tuple(init.shape) != (K,) + shape or step is None or tuple(step.shape) != (K, S) + shape:
+                raise ValueError(f"noise: init must be [{K}, {B}, {R}, {F}] and step [{K}, {S}, {B}, {R}, {F}] (segment first)")
+        desc = self._desc_for(shape, None, clip=True)
+        cond_d = self._f32(cond, device)
+        img = torch.empty(shape, dtype=torch.float32, device=device)
+        cond_buf = torch.empty((B, Lc, F), dtype=torch.float32, device=device)
+        out = torch.empty((B, K * R, F), dtype=torch.float32, device=device)
+        tarr = (C.c_int32 * (S + 1))(*times)
+        carr = coefs.contiguous()
+        sarr = (C.c_uint64 * K)(*autoregress_segment_seeds(seed, K))
+
+        def call(h, un, ws):
+            with torch.cuda.device(device):
+                _ffi.check(_ffi.lib().cindm_ddpm1d_sample_autoregress(
+                    h, self.model._h, un, C.byref(desc), _ffi.ptr(img), _ffi.ptr(cond_d), _ffi.ptr(cond_buf), _ffi.ptr(out), K, S,
+                    tarr, _ffi.ptr(carr), sarr, _ffi.ptr(init), _ffi.ptr(step), sample_offset, B, _ffi.ptr(ws), ws.numel(),
+                    _ffi.current_stream(device), int(use_graph)))
+        return self._chain(img, desc, call, result=out)

@@ -303,6 +303,27 @@ int  cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d*
                               const float* inpaint_noise_steps, int64_t B,
                               void* ws, size_t ws_bytes, void* stream, int32_t use_graph);
 
+/* Autoregressive time composition (autoregress_time_compose_sample, model/diffusion_1d.py:2240-2327):
+ * n_seg segments of the unguided DDIM loop above, each on a fresh x_T [B, R, F] (R = the state length
+ * the descriptor implies, c->cond_steps = Lc >= 1, R >= Lc) and conditioned on cond_buf [B, Lc, F]:
+ * segment 0 on the caller's cond [B, Lc, F], segment k > 0 on the last Lc rows of segment k-1.
+ * Segment k's final state goes to out[:, k*R : (k+1)*R] of out [B, n_seg*R, F].  x [B, R, F] and
+ * cond_buf are caller-owned scratch (x holds the last segment's state on return); x, cond_buf, out and
+ * init_tape must be 16-byte aligned.  times / coefs as cindm_ddpm1d_sample_ddim, shared by every
+ * segment; seeds is a HOST array [n_seg]: segment k's x_T is the cindm_fill_normal draw (seeds[k],
+ * sample_offset + b, step_tag = timesteps) and its step noise is keyed by seeds[k] as in
+ * cindm_ddpm1d_sample_ddim -- so segment k computes what cindm_ddpm1d_sample_ddim(seed = seeds[k])
+ * computes on its condition.  init_tape [n_seg, B, R, F] and noise_steps [n_seg, n_steps, B, R, F],
+ * when given, replace those draws.  One chain for the recovery (a time-out re-runs the whole rollout
+ * once, exchange-free) and one captured step graph for every segment when use_graph. */
+int  cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond,
+                                     const cindm_compose_desc* c, float* x, const float* cond,
+                                     float* cond_buf, float* out, int32_t n_seg, int32_t n_steps,
+                                     const int32_t* times, const float* coefs, const uint64_t* seeds,
+                                     const float* init_tape, const float* noise_steps,
+                                     int64_t sample_offset, int64_t B, void* ws, size_t ws_bytes,
+                                     void* stream, int32_t use_graph);
+
 /* out[n] ~ N(0,1): the library's counter-based Gaussian (Philox4x32-10 + Box-Muller) for the
  * initial state x_T (:1673), keyed by (seed, sample_offset + b, step_tag, element);
  * out is [B, per_sample]. */
