@@ -2011,6 +2011,8 @@ struct KeyBuilder {
     template <typename T> KeyBuilder& operator()(const T& v) { const auto* p = reinterpret_cast<const unsigned char*>(&v); k.insert(k.end(), p, p + sizeof(T)); return *this; }
 };
 
+#include "chain_host.inc"
+
 extern "C" int cindm_ddpm1d_create(const cindm_sched_desc* d, cindm_ddpm1d** out) {
     REQUIRE(d && out && d->timesteps > 0, "bad schedule descriptor");
     const float* src[13] = {d->betas, d->alphas_cumprod, d->alphas_cumprod_prev, d->sqrt_alphas_cumprod,
@@ -2308,8 +2310,9 @@ static void start_loop(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond
     }
 }
 
-// run one captured step n times (graph) or launch it n times (stream); shared tail of the sample loops.  The
-// instantiated graph is kept in the handle and reused while `key` (everything the captured launches embed) is unchanged.
+// run one captured step n times (graph) or launch it n times (stream): the 1-D loops' replay, on the chain driver's stream_steps /
+// graph_capture / graph_run (chain_host.inc).  The instantiated graph is kept in the handle and reused while `key` (everything the
+// captured launches embed) is unchanged.
 template <typename StepFn>
 static int replay_steps(cindm_ddpm1d* h, const std::vector<unsigned char>& key, hipStream_t stream, int nsteps, int use_graph, StepFn step,
                         cindm_unet1d* pair, cindm_unet1d* uncond, bool pingpong = false) {
@@ -2326,43 +2329,24 @@ static int replay_steps(cindm_ddpm1d* h, const std::vector<unsigned char>& key, 
         if (r0 < 0 || r1 < 0) return -1;
         return (r0 == 1 || r1 == 1) ? 1 : 0;
     };
-    if (!use_graph) {
-        for (int i = 0; i < nsteps; ++i) if (step(i & 1) != 0) return -1;
-        HIPCHK(hipGetLastError());
-        return finish();
-    }
+    if (!use_graph) return stream_steps(nsteps, step) != 0 ? -1 : finish();
     // ping-pong loops (the step state alternates between two slots, the step's own update advances it): the graph holds TWO
     // steps (parity 0 then 1); an odd count ends with a one-step graph of parity 0 -- after an even number of steps the
     // current state is in slot 0 again
     const int per = pingpong ? 2 : 1;
-    auto capture = [&](int nst, hipGraph_t* graph, hipGraphExec_t* exec) -> int {
-        HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        int rc = 0;
-        for (int q = 0; q < nst && rc == 0; ++q) rc = step(q);
-        hipError_t ce = hipStreamEndCapture(stream, graph);
-        if (rc != 0) { if (*graph) (void)hipGraphDestroy(*graph); *graph = nullptr; return -1; }
-        if (ce != hipSuccess) return fail(std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-        hipError_t ie = hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) { (void)hipGraphDestroy(*graph); *graph = nullptr; return fail(std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
-        return 0;
-    };
     if (!(h->gexec && h->gkey == key)) {
         h->drop_graph();
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-        if (capture(per, &graph, &exec) != 0) return -1;
+        if (graph_capture(stream, per, step, &graph, &exec) != 0) return -1;
         h->graph = graph; h->gexec = exec; h->gkey = key;
     }
-    if (pingpong && (nsteps & 1) && !h->gexec1) {
+    const bool odd = pingpong && (nsteps & 1);
+    if (odd && !h->gexec1) {
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-        if (capture(1, &graph, &exec) != 0) return -1;
+        if (graph_capture(stream, 1, step, &graph, &exec) != 0) return -1;
         h->graph1 = graph; h->gexec1 = exec;
     }
-    hipError_t le = hipSuccess;
-    for (int i = 0; i < nsteps / per && le == hipSuccess; ++i) le = hipGraphLaunch(h->gexec, stream);
-    if (pingpong && (nsteps & 1) && le == hipSuccess) le = hipGraphLaunch(h->gexec1, stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    if (le != hipSuccess) { h->drop_graph(); return fail(std::string("hipGraphLaunch: ") + hipGetErrorString(le)); }
-    if (se != hipSuccess) { h->drop_graph(); return fail(std::string("hipStreamSynchronize: ") + hipGetErrorString(se)); }
+    if (graph_run(stream, h->gexec, nsteps / per, odd ? h->gexec1 : nullptr) != 0) { h->drop_graph(); return -1; }
     return finish();
 }
 
@@ -2464,6 +2448,51 @@ static void key_common(KeyBuilder& K, int kind, const cindm_unet1d* pair, const 
     K(io.ddim_tab)(io.ddim_tnext)(io.iso)(io.iso_steps)(io.recur_t_stride);
 }
 
+// What the 1-D sample loops hand unchanged to every helper below them.
+struct Chain1D {
+    cindm_ddpm1d* h; cindm_unet1d* pair; cindm_unet1d* uncond; const cindm_compose_desc* c;
+    int64_t B; void* ws; size_t ws_bytes; hipStream_t stream; int use_graph;
+    cindm_unet1d* un() const { return c->mode == CINDM_COMPOSE_MULTIBODY ? uncond : nullptr; }      // the second model a chain really runs
+    int64_t n_state() const { return B * (int64_t)state_len(pair, c) * c->n_bodies * 4; }             // floats of the state x
+};
+
+// the StepIO fields every sample loop sets the same way: in-place state, per-step tapes (or the counter noise keyed in device
+// memory), inpainting.  What a loop adds -- DDIM tables, the design objective -- it sets itself; loop_steps sets dec_t and pingpong.
+static StepIO chain_io(const Chain1D& ch, float* x, const float* cond, const float* noise_steps, uint64_t seed, int64_t sample_offset,
+                       const float* inpaint_cond, int32_t inpaint_steps, const float* inpaint_noise_steps) {
+    StepIO io{};
+    io.x = x; io.cond = cond; io.x_out = x;
+    io.noise = noise_steps; io.noise_t_stride = ch.n_state(); io.seed = seed; io.sample_off = sample_offset; io.add_noise = 1;
+    io.inp_cond = inpaint_cond; io.inp_steps = inpaint_steps; io.inp_noise = inpaint_noise_steps;
+    io.inp_noise_t_stride = ch.B * inpaint_steps * ch.c->n_bodies * 4;
+    io.dyn = reinterpret_cast<const unsigned long long*>(ch.h->t_dev + 16);
+    return io;
+}
+
+// One unguided loop inside a chain body: start at t0 with (seed, sample_offset) in the device counter, then replay the step
+// nsteps times.  The step decrements the counter; with option "pingpong" the step state lives in two slots and the step's own
+// update advances it (no step_counter_kernel launch, and a plain single-model step runs its update inside the last U-Net kernel).
+// kind: 0 DDPM, 1 DDIM and the rollout's segments (whose keys are equal, so that one graph serves them all).
+static int loop_steps(const Chain1D& ch, StepIO io, int kind, int t0, int nsteps, uint64_t seed, int64_t sample_offset) {
+    const bool pp = ch.pair->O("pingpong") != 0;
+    io.dec_t = 1; io.pingpong = pp ? 1 : 0;
+    start_loop(ch.h, ch.pair, ch.uncond, ch.c, t0, ch.stream, seed, sample_offset);
+    KeyBuilder K;
+    key_common(K, kind, ch.pair, ch.uncond, ch.c, io, ch.B, ch.ws, ch.ws_bytes);
+    K(pp);
+    return replay_steps(ch.h, K.k, ch.stream, nsteps, ch.use_graph,
+                        [&](int q) { StepIO it = io; it.parity = q; return run_step(ch.h, ch.pair, ch.uncond, ch.c, it, 0, ch.h->t_dev, ch.B, ch.ws, ch.ws_bytes, ch.stream); },
+                        ch.pair, ch.un(), pp);
+}
+
+// the body of a chain that is one such loop (DDPM, DDIM): what a recovery re-run repeats
+static int loop_chain(const Chain1D& ch, const StepIO& io, int kind, int t0, int nsteps, float* x, float* xT, uint64_t seed, int64_t sample_offset) {
+    return run_chain_with_recovery(ch.h, ch.pair, ch.un(), x, xT, (size_t)ch.n_state(), ch.stream, [&]() -> int {
+        if (prepare_step_ws(ch.pair, ch.uncond, ch.c, ch.B, ch.ws, ch.ws_bytes, ch.stream) != 0) return -1;
+        return loop_steps(ch, io, kind, t0, nsteps, seed, sample_offset);
+    });
+}
+
 extern "C" int cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, const cindm_compose_desc* c,
                                    float* x, const float* cond, const float* noise_steps, uint64_t seed, int64_t sample_offset,
                                    const float* inpaint_cond, int32_t inpaint_steps, const float* inpaint_noise_steps,
@@ -2471,60 +2500,13 @@ extern "C" int cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_un
                                    int32_t use_graph) {
     REQUIRE(h && pair && c && x, "null argument");
     REQUIRE(t_start < h->T && t_end >= 0 && t_end <= t_start, "bad timestep range");
-    hipStream_t stream = (hipStream_t)stream_;
-    if (use_graph && stream == nullptr) {
-        // the legacy default stream cannot be captured: order against it with a device sync and
-        // run the loop on a private stream (the graph path synchronises at the end anyway)
-        if (!h->own) HIPCHK(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
-        HIPCHK(hipDeviceSynchronize());
-        stream = h->own;
-    }
-    const int Ltot = state_len(pair, c);
-    const int F = c->n_bodies * 4;
-    StepIO io{};
-    io.x = x; io.cond = cond; io.x_out = x;
-    io.noise = noise_steps; io.noise_t_stride = (int64_t)B * Ltot * F; io.seed = seed; io.sample_off = sample_offset; io.add_noise = 1;
-    io.inp_cond = inpaint_cond; io.inp_steps = inpaint_steps; io.inp_noise = inpaint_noise_steps;
-    io.inp_noise_t_stride = (int64_t)B * inpaint_steps * F;
-    io.dec_t = 1;
-    io.dyn = reinterpret_cast<const unsigned long long*>(h->t_dev + 16);
-    // the step state lives in two slots and the step's own update advances it (no step_counter_kernel launch)
-    const bool pp = pair->O("pingpong") != 0;
-    io.pingpong = pp ? 1 : 0;
-    cindm_unet1d* un = c->mode == CINDM_COMPOSE_MULTIBODY ? uncond : nullptr;
+    hipStream_t stream = nullptr;
+    if (chain_stream(h, stream_, use_graph, &stream) != 0) return -1;
+    const Chain1D ch{h, pair, uncond, c, B, ws, ws_bytes, stream, use_graph};
+    const StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     float* xT = nullptr;
     if (chain_slices(pair, uncond, c, B, ws, ws_bytes, &xT, nullptr) != 0) return -1;
-    return run_chain_with_recovery(h, pair, un, x, xT, (size_t)B * Ltot * F, stream, [&]() -> int {
-        if (prepare_step_ws(pair, uncond, c, B, ws, ws_bytes, stream) != 0) return -1;
-        start_loop(h, pair, uncond, c, (int)t_start, stream, seed, sample_offset);
-        KeyBuilder K;
-        key_common(K, 0, pair, uncond, c, io, B, ws, ws_bytes);
-        K(pp);
-        return replay_steps(h, K.k, stream, t_start - t_end + 1, use_graph,
-                            [&](int q) { StepIO it = io; it.parity = q; return run_step(h, pair, uncond, c, it, 0, h->t_dev, B, ws, ws_bytes, stream); },
-                            pair, un, pp);
-    });
-}
-
-// The DDIM loop's per-step tables ([n_steps][4] floats, then [n_steps] ints) go to their slice of the caller's workspace
-// (step_layout's off_ddim); shared by the DDIM loop and the autoregressive rollout, whose segments all read the same tables.
-static int upload_ddim_tables(const cindm_ddpm1d* h, const cindm_unet1d* pair, int32_t n_steps, const int32_t* times,
-                              const float* coefs, float* ddim_buf, hipStream_t stream, int** tn_out) {
-    REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    for (int i = 0; i < n_steps; ++i) REQUIRE(times[i] >= 0 && times[i] < h->T && times[i + 1] < times[i] && times[i + 1] >= -1, "bad DDIM time schedule");
-    REQUIRE(n_steps <= pair->d.timesteps, "more DDIM steps than the U-Net's timesteps");
-    std::vector<float> tabv((size_t)n_steps * 4, 0.f);
-    std::vector<int> tnv(n_steps);
-    for (int i = 0; i < n_steps; ++i) {
-        tabv[4 * i] = coefs[3 * i]; tabv[4 * i + 1] = coefs[3 * i + 1]; tabv[4 * i + 2] = coefs[3 * i + 2];
-        tnv[i] = times[i + 1];
-    }
-    int* tn_dev = reinterpret_cast<int*>(ddim_buf + (size_t)n_steps * 4);
-    HIPCHK(hipMemcpyAsync(ddim_buf, tabv.data(), tabv.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(tn_dev, tnv.data(), tnv.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream));            // the host vectors go out of scope
-    *tn_out = tn_dev;
-    return 0;
+    return loop_chain(ch, io, 0, (int)t_start, t_start - t_end + 1, x, xT, seed, sample_offset);
 }
 
 extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, const cindm_compose_desc* c,
@@ -2533,50 +2515,25 @@ extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cin
                                         const float* inpaint_cond, int32_t inpaint_steps, const float* inpaint_noise_steps,
                                         int64_t B, void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
     REQUIRE(h && pair && c && x && times && coefs, "null argument");
-    REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    for (int i = 0; i < n_steps; ++i) REQUIRE(times[i] >= 0 && times[i] < h->T && times[i + 1] < times[i] && times[i + 1] >= -1, "bad DDIM time schedule");
-    hipStream_t stream = (hipStream_t)stream_;
-    if (use_graph && stream == nullptr) {
-        if (!h->own) HIPCHK(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
-        HIPCHK(hipDeviceSynchronize());
-        stream = h->own;
-    }
-    // the per-step tables and the x_T snapshot live in the caller's workspace
+    hipStream_t stream = nullptr;
+    if (chain_stream(h, stream_, use_graph, &stream) != 0) return -1;
+    const Chain1D ch{h, pair, uncond, c, B, ws, ws_bytes, stream, use_graph};
+    // the per-step tables and the x_T snapshot live in the caller's workspace (step_layout's off_ddim holds timesteps * 5 words)
     float* xT = nullptr; float* ddim_buf = nullptr; int* tn_dev = nullptr;
     if (chain_slices(pair, uncond, c, B, ws, ws_bytes, &xT, &ddim_buf) != 0) return -1;
-    if (upload_ddim_tables(h, pair, n_steps, times, coefs, ddim_buf, stream, &tn_dev) != 0) return -1;
-    const int Ltot = state_len(pair, c);
-    const int F = c->n_bodies * 4;
-    StepIO io{};
-    io.x = x; io.cond = cond; io.x_out = x;
-    io.noise = noise_steps; io.noise_t_stride = (int64_t)B * Ltot * F; io.seed = seed; io.sample_off = sample_offset; io.add_noise = 1;
-    io.inp_cond = inpaint_cond; io.inp_steps = inpaint_steps; io.inp_noise = inpaint_noise_steps;
-    io.inp_noise_t_stride = (int64_t)B * inpaint_steps * F;
-    io.dec_t = 1; io.ddim_tab = ddim_buf; io.ddim_tnext = tn_dev;
-    io.dyn = reinterpret_cast<const unsigned long long*>(h->t_dev + 16);
-    // (round 4) as in the DDPM loop the step state -- t, the step index, the epochs -- lives in two slots advanced by the step's own
-    // update: no step_counter_kernel launch, and a plain single-model step runs its update inside the last U-Net kernel
-    const bool pp = pair->O("pingpong") != 0;
-    io.pingpong = pp ? 1 : 0;
-    cindm_unet1d* un = c->mode == CINDM_COMPOSE_MULTIBODY ? uncond : nullptr;
-    return run_chain_with_recovery(h, pair, un, x, xT, (size_t)B * Ltot * F, stream, [&]() -> int {
-        if (prepare_step_ws(pair, uncond, c, B, ws, ws_bytes, stream) != 0) return -1;
-        start_loop(h, pair, uncond, c, (int)times[0], stream, seed, sample_offset);
-        KeyBuilder K;
-        key_common(K, 1, pair, uncond, c, io, B, ws, ws_bytes);
-        K(pp);
-        return replay_steps(h, K.k, stream, n_steps, use_graph,
-                            [&](int q) { StepIO it = io; it.parity = q; return run_step(h, pair, uncond, c, it, 0, h->t_dev, B, ws, ws_bytes, stream); },
-                            pair, un, pp);
-    });
+    REQUIRE(n_steps <= pair->d.timesteps, "more DDIM steps than the U-Net's timesteps");
+    if (upload_ddim_tables(h->T, n_steps, times, coefs, ddim_buf, stream, &tn_dev) != 0) return -1;
+    StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
+    io.ddim_tab = ddim_buf; io.ddim_tnext = tn_dev;
+    return loop_chain(ch, io, 1, (int)times[0], n_steps, x, xT, seed, sample_offset);
 }
 
 // Autoregressive time composition (autoregress_time_compose_sample, model/diffusion_1d.py:2240-2327): n_seg unguided DDIM chains, each
 // from a fresh x_T and conditioned on the last Lc rows of the previous one.  The whole rollout is ONE chain for the recovery and the
 // in-flight registry: its body draws segment 0's x_T and copies the caller's cond into cond_buf itself, so it is a pure function of
-// its inputs and a time-out re-runs all of it once on the exchange-free kernels.  Per segment: start_loop with that segment's seed,
-// the DDIM step replayed n_steps times (io.cond = cond_buf: a fixed address, and the seed lives in the device counter -- one captured
-// graph serves every segment), then autoregress_handover_kernel (out slice, next cond, next x_T).
+// its inputs and a time-out re-runs all of it once on the exchange-free kernels.  Per segment: loop_steps with that segment's seed
+// (io.cond = cond_buf: a fixed address, and the seed lives in the device counter -- one captured graph serves every segment), then
+// autoregress_handover_kernel (out slice, next cond, next x_T).
 extern "C" int cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, const cindm_compose_desc* c,
                                                float* x, const float* cond, float* cond_buf, float* out, int32_t n_seg,
                                                int32_t n_steps, const int32_t* times, const float* coefs, const uint64_t* seeds,
@@ -2590,41 +2547,28 @@ extern "C" int cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pa
     REQUIRE(R >= Lc, "rollout_steps < conditioned_steps: the next segment's condition would be shorter than the model's horizon needs");
     for (const void* p : {(const void*)x, (const void*)cond_buf, (const void*)out, (const void*)init_tape})
         REQUIRE(((uintptr_t)p & 15) == 0, "x, cond_buf, out and init_tape must be 16-byte aligned");
-    hipStream_t stream = (hipStream_t)stream_;
-    if (use_graph && stream == nullptr) {
-        if (!h->own) HIPCHK(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
-        HIPCHK(hipDeviceSynchronize());
-        stream = h->own;
-    }
+    hipStream_t stream = nullptr;
+    if (chain_stream(h, stream_, use_graph, &stream) != 0) return -1;
+    const Chain1D ch{h, pair, uncond, c, B, ws, ws_bytes, stream, use_graph};
     float* xT = nullptr; float* ddim_buf = nullptr; int* tn_dev = nullptr;
     if (chain_slices(pair, uncond, c, B, ws, ws_bytes, &xT, &ddim_buf) != 0) return -1;
-    if (upload_ddim_tables(h, pair, n_steps, times, coefs, ddim_buf, stream, &tn_dev) != 0) return -1;
-    const int64_t n_state = B * (int64_t)R * F;
-    StepIO io{};
-    io.x = x; io.cond = cond_buf; io.x_out = x;
-    io.noise_t_stride = n_state; io.add_noise = 1;
-    io.dec_t = 1; io.ddim_tab = ddim_buf; io.ddim_tnext = tn_dev;
-    io.dyn = reinterpret_cast<const unsigned long long*>(h->t_dev + 16);
-    const bool pp = pair->O("pingpong") != 0;
-    io.pingpong = pp ? 1 : 0;
-    cindm_unet1d* un = c->mode == CINDM_COMPOSE_MULTIBODY ? uncond : nullptr;
+    REQUIRE(n_steps <= pair->d.timesteps, "more DDIM steps than the U-Net's timesteps");
+    if (upload_ddim_tables(h->T, n_steps, times, coefs, ddim_buf, stream, &tn_dev) != 0) return -1;
+    const int64_t n_state = ch.n_state();
+    // (the seed differs per segment and goes to the device counter; the tape per segment below; no inpainting)
+    StepIO io = chain_io(ch, x, cond_buf, nullptr, 0, 0, nullptr, 0, nullptr);
+    io.ddim_tab = ddim_buf; io.ddim_tnext = tn_dev;
     const unsigned hblocks = (unsigned)((n_state / 4 + 255) / 256);
-    return run_chain_with_recovery(h, pair, un, x, xT, (size_t)n_state, stream, [&]() -> int {
+    return run_chain_with_recovery(h, pair, ch.un(), x, xT, (size_t)n_state, stream, [&]() -> int {
         if (prepare_step_ws(pair, uncond, c, B, ws, ws_bytes, stream) != 0) return -1;
         if (init_tape) HIPCHK(hipMemcpyAsync(x, init_tape, (size_t)n_state * sizeof(float), hipMemcpyDeviceToDevice, stream));
         else hipLaunchKernelGGL(fill_normal_kernel, dim3((unsigned)((n_state + 255) / 256)), dim3(256), 0, stream,
                                 x, B, (int64_t)R * F, seeds[0], sample_offset, (uint32_t)h->T);
         HIPCHK(hipMemcpyAsync(cond_buf, cond, (size_t)B * Lc * F * sizeof(float), hipMemcpyDeviceToDevice, stream));
         for (int k = 0; k < n_seg; ++k) {
-            start_loop(h, pair, uncond, c, (int)times[0], stream, seeds[k], sample_offset);
             StepIO seg = io;
             seg.noise = noise_steps ? noise_steps + (size_t)k * n_steps * n_state : nullptr;      // (a tape re-captures per segment)
-            KeyBuilder K;
-            key_common(K, 1, pair, uncond, c, seg, B, ws, ws_bytes);
-            K(pp);
-            const int rc = replay_steps(h, K.k, stream, n_steps, use_graph,
-                                        [&](int q) { StepIO it = seg; it.parity = q; return run_step(h, pair, uncond, c, it, 0, h->t_dev, B, ws, ws_bytes, stream); },
-                                        pair, un, pp);
+            const int rc = loop_steps(ch, seg, 1, (int)times[0], n_steps, seeds[k], sample_offset);
             if (rc != 0) return rc;
             const int has_next = k + 1 < n_seg;
             hipLaunchKernelGGL(autoregress_handover_kernel, dim3(hblocks), dim3(256), 0, stream, x, out, cond_buf,
@@ -2650,22 +2594,14 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
     const int Ltot = state_len(pair, c);
     REQUIRE(dz->last_n_step >= 1 && dz->last_n_step <= Ltot, "last_n_step out of range");
     REQUIRE(!initial_state_overwrite || (overwrite_steps >= 1 && overwrite_steps <= Ltot), "bad overwrite_steps");
-    hipStream_t stream = (hipStream_t)stream_;
-    if (use_graph && stream == nullptr) {
-        if (!h->own) HIPCHK(hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking));
-        HIPCHK(hipDeviceSynchronize());
-        stream = h->own;
-    }
-    const int F = c->n_bodies * 4;
+    hipStream_t stream = nullptr;
+    if (chain_stream(h, stream_, use_graph, &stream) != 0) return -1;
+    const Chain1D ch{h, pair, uncond, c, B, ws, ws_bytes, stream, use_graph};
+    const int64_t n_state = ch.n_state();
     const int R = dz->recurrence;
-    StepIO io{};
-    io.x = x; io.cond = cond; io.x_out = x;
-    io.noise = noise_steps; io.noise_t_stride = (int64_t)B * Ltot * F; io.seed = seed; io.sample_off = sample_offset; io.add_noise = 1;
-    io.inp_cond = inpaint_cond; io.inp_steps = inpaint_steps; io.inp_noise = inpaint_noise_steps;
-    io.inp_noise_t_stride = (int64_t)B * inpaint_steps * F;
+    StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     io.dz = dz; io.iso = initial_state_overwrite; io.iso_steps = initial_state_overwrite ? overwrite_steps : 0;
-    io.recur_t_stride = (int64_t)(R > 0 ? R : 1) * B * Ltot * F;
-    io.dyn = reinterpret_cast<const unsigned long long*>(h->t_dev + 16);
+    io.recur_t_stride = (int64_t)(R > 0 ? R : 1) * n_state;
     // one reverse step (:1286-1370): R x [p_mean_variance, mean - grad, overwrite, relaxation]; the last iteration's
     // relaxation is never used by the reference, its pred + sigma z is the step's result
     auto step = [&](int) -> int {
@@ -2674,22 +2610,22 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
             StepIO it = io;
             it.relax = (r < iters - 1) ? 1 : 0;
             it.dec_t = it.relax ? 0 : 1;
-            it.recur_noise = recur_noise_steps ? recur_noise_steps + (size_t)r * B * Ltot * F : nullptr;
+            it.recur_noise = recur_noise_steps ? recur_noise_steps + (size_t)r * n_state : nullptr;
             it.recur_tag = 0x10000u * (uint32_t)(r + 1);
             if (run_step(h, pair, uncond, c, it, 0, h->t_dev, B, ws, ws_bytes, stream) != 0) return -1;
         }
         return 0;
     };
-    cindm_unet1d* un = c->mode == CINDM_COMPOSE_MULTIBODY ? uncond : nullptr;
     float* xT = nullptr;
     if (chain_slices(pair, uncond, c, B, ws, ws_bytes, &xT, nullptr) != 0) return -1;
-    return run_chain_with_recovery(h, pair, un, x, xT, (size_t)B * Ltot * F, stream, [&]() -> int {
+    // (its own tail rather than loop_steps: the step is the functor above, the key carries the objective, no ping-pong)
+    return run_chain_with_recovery(h, pair, ch.un(), x, xT, (size_t)n_state, stream, [&]() -> int {
         if (prepare_step_ws(pair, uncond, c, B, ws, ws_bytes, stream) != 0) return -1;
         start_loop(h, pair, uncond, c, (int)t_start, stream, seed, sample_offset);
         KeyBuilder K;
         key_common(K, 2, pair, uncond, c, io, B, ws, ws_bytes);
         K(*dz)(recur_noise_steps)(R);
-        return replay_steps(h, K.k, stream, t_start - t_end + 1, use_graph, step, pair, un);
+        return replay_steps(h, K.k, stream, t_start - t_end + 1, use_graph, step, pair, ch.un());
     });
 }
 

@@ -862,21 +862,13 @@ extern "C" int cindm_ddpm2d_sample_force(cindm_ddpm1d* s, cindm_unet2d* u, cindm
     REQUIRE(s && u && f && x && eta && grad && ws && ws_force, "null argument");
     REQUIRE(t_start < s->T && t_end >= 0 && t_end <= t_start, "bad timestep range");
     REQUIRE(u->d.image_size == f->d.image_size, "Unet and ForceUnet image sizes differ");
-    hipStream_t stream = (hipStream_t)stream_;
-    if (use_graph && stream == nullptr) {
-        if (!s->own) HIPCHK(hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking));
-        HIPCHK(hipDeviceSynchronize());
-        stream = s->own;
-    }
-    const int HW = u->d.image_size * u->d.image_size, Cs = u->d.channels - 3, CP = u->CP();
+    hipStream_t stream = nullptr;
+    if (chain_stream(s, stream_, use_graph, &stream) != 0) return -1;
+    const int HW = u->d.image_size * u->d.image_size, CP = u->CP();
     REQUIRE(u->d.channels == 3 * frames + 3, "state channels must be 3 * frames + 3");
-    Step2IO io{};
-    io.x = x; io.x_out = x;
-    io.noise_state = noise_state_steps; io.ns_stride = (int64_t)B * HW * Cs;
-    io.noise_bound = noise_boundary_steps; io.nb_stride = (int64_t)B * nb * HW * 3;
-    io.seed = seed; io.off = sample_offset; io.add_noise = 1; io.dec_t = 1;
+    const Step2IO io = chain_io2(u, x, B, nb, noise_state_steps, noise_boundary_steps, seed, sample_offset);
     const int64_t n4 = B * nb * (int64_t)HW * (CP / 4);
-    auto one_step = [&]() -> int {
+    auto one_step = [&](int) -> int {
         if (cindm_airfoil_design_grad(f, x, B, nb, frames, CP, p_min, p_max, lambda_force, lambda_overlap, down_factor, sum_boundary,
                                       grad, ws_force, ws_force_bytes, stream) != 0) return -1;
         if (run_step2(s, u, io, B, nb, use_average_share, 1, 0, s->t_dev, ws, ws_bytes, stream) != 0) return -1;
@@ -896,25 +888,7 @@ extern "C" int cindm_ddpm2d_sample_force(cindm_ddpm1d* s, cindm_unet2d* u, cindm
     if (guard) HIPCHK(hipMemcpyAsync(xT, x, n_floats * sizeof(float), hipMemcpyDeviceToDevice, stream));
     auto chain = [&]() -> int {
         hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (int)t_start, 0ull, 0ll);
-        if (!use_graph) {
-            for (int i = 0; i < nsteps; ++i) if (one_step() != 0) return -1;
-            return 0;
-        }
-        hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-        HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        int rc = one_step();
-        hipError_t ce = hipStreamEndCapture(stream, &graph);
-        if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return -1; }
-        if (ce != hipSuccess) return fail(std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-        hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) { (void)hipGraphDestroy(graph); return fail(std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
-        hipError_t le = hipSuccess;
-        for (int i = 0; i < nsteps && le == hipSuccess; ++i) le = hipGraphLaunch(exec, stream);
-        hipError_t se = hipStreamSynchronize(stream);
-        (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph);
-        if (le != hipSuccess) return fail(std::string("hipGraphLaunch: ") + hipGetErrorString(le));
-        if (se != hipSuccess) return fail(std::string("hipStreamSynchronize: ") + hipGetErrorString(se));
-        return 0;
+        return replay_once(stream, nsteps, use_graph, one_step);
     };
     if (chain() != 0) return -1;
     if (!guard) return 0;

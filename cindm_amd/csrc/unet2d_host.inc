@@ -1200,29 +1200,16 @@ extern "C" int cindm_ddpm2d_predict(cindm_ddpm1d* s, cindm_unet2d* u, const floa
                      (hipStream_t)stream);
 }
 
-// the 2-D chains' replay: step() enqueues one step; with use_graph it is captured once and the graph launched nsteps times
-template <class F>
-static int replay_steps2(hipStream_t stream, int nsteps, int use_graph, F step) {
-    if (!use_graph) {
-        for (int i = 0; i < nsteps; ++i)
-            if (step() != 0) return -1;
-        return 0;
-    }
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-    HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    int rc = step();
-    hipError_t ce = hipStreamEndCapture(stream, &graph);
-    if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return -1; }
-    if (ce != hipSuccess) return fail(std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-    hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    if (ie != hipSuccess) { (void)hipGraphDestroy(graph); return fail(std::string("hipGraphInstantiate: ") + hipGetErrorString(ie)); }
-    hipError_t le = hipSuccess;
-    for (int i = 0; i < nsteps && le == hipSuccess; ++i) le = hipGraphLaunch(exec, stream);
-    hipError_t se = hipStreamSynchronize(stream);
-    (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph);
-    if (le != hipSuccess) return fail(std::string("hipGraphLaunch: ") + hipGetErrorString(le));
-    if (se != hipSuccess) return fail(std::string("hipStreamSynchronize: ") + hipGetErrorString(se));
-    return 0;
+// the Step2IO of a 2-D sample loop: in-place state, per-step tapes (or counter noise), the device counter decremented by the step
+static Step2IO chain_io2(const cindm_unet2d* u, float* x, int64_t B, int nb, const float* noise_state_steps,
+                         const float* noise_boundary_steps, uint64_t seed, int64_t sample_offset) {
+    const int HW = u->d.image_size * u->d.image_size, Cs = u->d.channels - 3;
+    Step2IO io{};
+    io.x = x; io.x_out = x;
+    io.noise_state = noise_state_steps; io.ns_stride = (int64_t)B * HW * Cs;
+    io.noise_bound = noise_boundary_steps; io.nb_stride = (int64_t)B * nb * HW * 3;
+    io.seed = seed; io.off = sample_offset; io.add_noise = 1; io.dec_t = 1;
+    return io;
 }
 
 extern "C" int cindm_ddpm2d_sample(cindm_ddpm1d* s, cindm_unet2d* u, float* x, int64_t B, int32_t nb, int32_t use_average_share,
@@ -1231,21 +1218,12 @@ extern "C" int cindm_ddpm2d_sample(cindm_ddpm1d* s, cindm_unet2d* u, float* x, i
                                    void* stream_, int32_t use_graph) {
     REQUIRE(s && u && x, "null argument");
     REQUIRE(t_start < s->T && t_end >= 0 && t_end <= t_start, "bad timestep range");
-    hipStream_t stream = (hipStream_t)stream_;
-    if (use_graph && stream == nullptr) {
-        if (!s->own) HIPCHK(hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking));
-        HIPCHK(hipDeviceSynchronize());
-        stream = s->own;
-    }
-    const int HW = u->d.image_size * u->d.image_size, Cs = u->d.channels - 3;
-    Step2IO io{};
-    io.x = x; io.x_out = x;
-    io.noise_state = noise_state_steps; io.ns_stride = (int64_t)B * HW * Cs;
-    io.noise_bound = noise_boundary_steps; io.nb_stride = (int64_t)B * nb * HW * 3;
-    io.seed = seed; io.off = sample_offset; io.add_noise = 1; io.dec_t = 1;
+    hipStream_t stream = nullptr;
+    if (chain_stream(s, stream_, use_graph, &stream) != 0) return -1;
+    const Step2IO io = chain_io2(u, x, B, nb, noise_state_steps, noise_boundary_steps, seed, sample_offset);
     hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (int)t_start, 0ull, 0ll);
-    return replay_steps2(stream, t_start - t_end + 1, use_graph,
-                         [&]() { return run_step2(s, u, io, B, nb, use_average_share, 1, 0, s->t_dev, ws, ws_bytes, stream); });
+    return replay_once(stream, t_start - t_end + 1, use_graph,
+                       [&](int) { return run_step2(s, u, io, B, nb, use_average_share, 1, 0, s->t_dev, ws, ws_bytes, stream); });
 }
 
 // DDIM loop of the 2-D path (ddim_sample; DESIGN 4.5g): one step = the U-Net + ddim2d_update_kernel + step_counter_kernel
@@ -1275,33 +1253,19 @@ extern "C" int cindm_ddpm2d_sample_ddim(cindm_ddpm1d* s, cindm_unet2d* u, float*
     REQUIRE(((use_average_share >> 4) & 3) <= 2 && (use_average_share & ~0x31) == 0,
             "bad use_average_share word (bit 0 mean / sum, bits 4-5 objective 0..2; DDIM has no share_noise False)");
     REQUIRE(B > 0 && nb >= 1, "bad batch");
-    REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     REQUIRE(s->T <= u->d.timesteps, "the diffusion has more timesteps than the Unet's per-timestep table (construct Unet(..., timesteps=T))");
-    for (int i = 0; i < n_steps; ++i)
-        REQUIRE(times[i] >= 0 && times[i] < s->T && times[i + 1] < times[i] && times[i + 1] >= -1, "bad DDIM time schedule");
-    REQUIRE(tab_bytes >= (size_t)n_steps * 5 * sizeof(float) && ((uintptr_t)tab & 15) == 0, "DDIM table buffer too small or not 16-byte aligned");
+    // (n_steps < 1 and the schedule itself are refused by upload_ddim_tables, before anything is copied)
+    REQUIRE(tab_bytes >= (size_t)std::max(n_steps, 0) * 5 * sizeof(float) && ((uintptr_t)tab & 15) == 0, "DDIM table buffer too small or not 16-byte aligned");
     const int64_t NI = B * nb;
     const int HW = u->d.image_size * u->d.image_size, CP = u->CP(), Cs = u->d.channels - 3;
     REQUIRE(NI * (int64_t)HW * CP < (1ll << 31), "state too large for one launch");
     REQUIRE(ws_bytes >= cindm_ddpm2d_workspace_bytes(u, NI), "workspace too small");
-    hipStream_t stream = (hipStream_t)stream_;
-    if (use_graph && stream == nullptr) {
-        if (!s->own) HIPCHK(hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking));
-        HIPCHK(hipDeviceSynchronize());
-        stream = s->own;
-    }
-    // the per-step tables ([n_steps][4] floats, then [n_steps] ints) go to the caller's device buffer
-    std::vector<float> tabv((size_t)n_steps * 4, 0.f);
-    std::vector<int> tnv(n_steps);
-    for (int i = 0; i < n_steps; ++i) {
-        tabv[4 * i] = coefs[3 * i]; tabv[4 * i + 1] = coefs[3 * i + 1]; tabv[4 * i + 2] = coefs[3 * i + 2];
-        tnv[i] = times[i + 1];
-    }
+    hipStream_t stream = nullptr;
+    if (chain_stream(s, stream_, use_graph, &stream) != 0) return -1;
+    // the per-step tables go to the caller's device buffer
     float* tab_f = (float*)tab;
-    int* tn_dev = reinterpret_cast<int*>(tab_f + (size_t)n_steps * 4);
-    HIPCHK(hipMemcpyAsync(tab_f, tabv.data(), tabv.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(tn_dev, tnv.data(), tnv.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-    HIPCHK(hipStreamSynchronize(stream));            // the host vectors go out of scope
+    int* tn_dev = nullptr;
+    if (upload_ddim_tables(s->T, n_steps, times, coefs, tab_f, stream, &tn_dev) != 0) return -1;
     Ddim2dArgs a; std::memset(&a, 0, sizeof(a));
     a.x = x; a.x_out = x;
     a.B = (int)B; a.nb = nb; a.HW = HW; a.C = u->d.channels; a.CP = CP; a.use_avg = use_average_share;
@@ -1312,7 +1276,7 @@ extern "C" int cindm_ddpm2d_sample_ddim(cindm_ddpm1d* s, cindm_unet2d* u, float*
     a.noise_bound = noise_boundary_steps; a.nb_t_stride = NI * (int64_t)HW * 3;
     a.seed = seed; a.sample_off = sample_offset;
     hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (int)times[0], 0ull, 0ll);
-    return replay_steps2(stream, n_steps, use_graph, [&]() { return run_ddim_step2(s, u, a, B, nb, ws, ws_bytes, stream); });
+    return replay_once(stream, n_steps, use_graph, [&](int) { return run_ddim_step2(s, u, a, B, nb, ws, ws_bytes, stream); });
 }
 
 extern "C" int cindm_fill_noise2d(float* x, int64_t B, int32_t nb, int32_t hw, int32_t channels, int32_t padded_channels,

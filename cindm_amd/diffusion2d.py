@@ -295,6 +295,28 @@ class GaussianDiffusion(nn.Module):
         return pred - shift, x_start
 
     # ------------------------------------------------------------------ loops
+    def _x_T(self, shape, noise, seed, sample_offset, device):
+        """x_T in the device layout: the tape's init rows (state shared over a design's boundary copies), or the library's
+        counter-based draw (``cindm_fill_noise2d``)."""
+        B, nb, Cc, H, W = shape
+        cp = self.model.padded_channels
+        if noise is not None:
+            return to_device_layout(torch.cat([noise.init[0].expand(-1, nb, -1, -1, -1), noise.init[1]], dim=2)
+                                    .reshape(B * nb, Cc, H, W).to(device, torch.float32), cp)
+        x = torch.empty((B * nb, H * W, cp), dtype=torch.float32, device=device)
+        with torch.cuda.device(device):
+            _ffi.check(_ffi.lib().cindm_fill_noise2d(_ffi.ptr(x), B, nb, H * W, Cc, cp, seed, sample_offset, self.num_timesteps,
+                                                     _ffi.current_stream(device)))
+        return x
+
+    @staticmethod
+    def _tape_cl(noise, device, rows=slice(None)):
+        """(ns, nbnd): a tape's per-step draws (``rows`` of them) channel-last on the device, or (None, None) without a tape."""
+        if noise is None:
+            return None, None
+        return (_state_cl(noise.step_state[rows].to(device, torch.float32)),
+                _boundary_cl(noise.step_boundary[rows].to(device, torch.float32)))
+
     @torch.no_grad()
     def p_sample_loop(self, shape, design_fn=None, design_guidance="standard", return_all_timesteps=None, *,
                       noise=None, seed=0, sample_offset=0, use_graph=True, t_stop=0, device=None, fused=True):
@@ -304,23 +326,12 @@ class GaussianDiffusion(nn.Module):
         device = device or self.betas.device
         if device.type != "cuda":
             raise _ffi.CindmError("sampling needs a ROCm device; there is no CPU execution path")
-        cp = self.model.padded_channels
         L = _ffi.lib()
         T = self.num_timesteps
-        if noise is not None:
-            x = to_device_layout(torch.cat([noise.init[0].expand(-1, nb, -1, -1, -1), noise.init[1]], dim=2)
-                                 .reshape(B * nb, Cc, H, W).to(device, torch.float32), cp)
-        else:
-            x = torch.empty((B * nb, H * W, cp), dtype=torch.float32, device=device)
-            with torch.cuda.device(device):
-                _ffi.check(L.cindm_fill_noise2d(_ffi.ptr(x), B, nb, H * W, Cc, cp, seed, sample_offset, T,
-                                                _ffi.current_stream(device)))
+        x = self._x_T(shape, noise, seed, sample_offset, device)
         if design_fn is None:
             h, ws = self._prepare(B * nb, device)
-            ns = nbnd = None
-            if noise is not None:
-                ns = _state_cl(noise.step_state.to(device, torch.float32))
-                nbnd = _boundary_cl(noise.step_boundary.to(device, torch.float32))
+            ns, nbnd = self._tape_cl(noise, device)
             with torch.cuda.device(device):
                 _ffi.check(L.cindm_ddpm2d_sample(h, self.model._h, _ffi.ptr(x), B, nb, self._share_mode(),
                                                  _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, T - 1, int(t_stop),
@@ -339,10 +350,7 @@ class GaussianDiffusion(nn.Module):
             wsf = torch.empty(nfb, dtype=torch.uint8, device=device)
             g = torch.empty_like(x)
             eta = (self.coeff_ratio * self.betas.flip(0)).to(device, torch.float32).contiguous()
-            ns = nbnd = None
-            if noise is not None:
-                ns = _state_cl(noise.step_state.to(device, torch.float32))
-                nbnd = _boundary_cl(noise.step_boundary.to(device, torch.float32))
+            ns, nbnd = self._tape_cl(noise, device)
             with torch.cuda.device(device):
                 _ffi.check(L.cindm_ddpm2d_sample_force(h, self.model._h, fo.model._h, _ffi.ptr(x), B, nb, self._share_mode(),
                                                        _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, T - 1, int(t_stop),
@@ -401,22 +409,14 @@ class GaussianDiffusion(nn.Module):
         S = len(times) - 1
         if init_img is not None:
             x = to_device_layout(init_img.reshape(B * nb, Cc, H, W).to(device, torch.float32), cp)
-        elif noise is not None:
-            x = to_device_layout(torch.cat([noise.init[0].expand(-1, nb, -1, -1, -1), noise.init[1]], dim=2)
-                                 .reshape(B * nb, Cc, H, W).to(device, torch.float32), cp)
         else:
-            x = torch.empty((B * nb, H * W, cp), dtype=torch.float32, device=device)
-            with torch.cuda.device(device):
-                _ffi.check(L.cindm_fill_noise2d(_ffi.ptr(x), B, nb, H * W, Cc, cp, seed, sample_offset, self.num_timesteps,
-                                                _ffi.current_stream(device)))
-        ns = nbnd = None
+            x = self._x_T(shape, noise, seed, sample_offset, device)
         if noise is not None:
             if (noise.step_state.shape[0] < i1 or noise.step_boundary.shape[0] < i1 or tuple(noise.step_state.shape[1:]) != (B, 1, Cc - 3, H, W)
                     or tuple(noise.step_boundary.shape[1:]) != (B, nb, 3, H, W)):
                 raise ValueError(f"the noise tape needs step_state [>= {i1}, {B}, 1, {Cc - 3}, {H}, {W}] and step_boundary "
                                  f"[>= {i1}, {B}, {nb}, 3, {H}, {W}] (rows indexed by the DDIM step)")
-            ns = _state_cl(noise.step_state[i0:i1].to(device, torch.float32))
-            nbnd = _boundary_cl(noise.step_boundary[i0:i1].to(device, torch.float32))
+        ns, nbnd = self._tape_cl(noise, device, slice(i0, i1))
         h, ws = self._prepare(B * nb, device)
         # the per-step device tables live in a caller tensor (the library allocates nothing): [S][4] coefficients + [S] time_next
         if self._ddim_tab is None or self._ddim_tab.numel() < 5 * S or self._ddim_tab.device != device:
