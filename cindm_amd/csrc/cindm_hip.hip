@@ -2139,6 +2139,7 @@ struct StepIO {
     int relax; const float* recur_noise; int64_t recur_t_stride; uint32_t recur_tag;
     const float* iso; int iso_steps;
     int pingpong, parity;   // plain sample loop: step state in two slots, advanced by the update itself (no step_counter launch)
+    const float* ula_tab; int ula_L, ula_t_hi;         // Langevin loop: per-timestep (scalar, ss, std, -) rows (device), inner count, first timestep
 };
 
 // clears the exchange regions of the U-Net workspaces inside a step workspace (before a step is captured into a graph)
@@ -2249,7 +2250,12 @@ static int run_step(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, c
     h->last_step_launches = ((s.direct || gather_fused) ? 0 : 1) + pair->issued + (s.single_rows ? uncond->issued : 0) + (pair->fused_done ? 0 : 1) +
                             ((io.dec_t && !io.pingpong) ? 1 : 0);
     h->last_step_fused = pair->fused_done ? 1 : 0;
-    if (!pair->fused_done) hipLaunchKernelGGL(compose_update_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a);
+    if (io.ula_tab) {
+        // Langevin iteration: the update moves every row of the (full) state by the composed score; io.noise is the iteration tape
+        UlaArgs u;
+        u.c = a; u.tab = io.ula_tab; u.L = io.ula_L; u.t_hi = io.ula_t_hi; u.noise_it_stride = io.noise_t_stride;
+        hipLaunchKernelGGL(ula_update_kernel, dim3((unsigned)((ne / 4 + 255) / 256)), dim3(256), 0, stream, u);
+    } else if (!pair->fused_done) hipLaunchKernelGGL(compose_update_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a);
     pair->epoch_slot = 0;
     if (uncond) uncond->epoch_slot = 0;
     if (io.pingpong) {                       // the update has advanced t and the epochs for the next step
@@ -2257,6 +2263,9 @@ static int run_step(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, c
         if (s.single_rows && uncond) uncond->epoch_prebumped = true;
     } else if (io.dec_t) {
         // the counter kernel also advances the U-Nets' exchange epochs for the step that follows
+        if (io.ula_tab) hipLaunchKernelGGL(ula_counter_kernel, dim3(1), dim3(64), 0, stream, h->t_dev, io.ula_L, pair->epoch_dev,
+                                           (s.single_rows && uncond) ? uncond->epoch_dev : (int*)nullptr);
+        else
         hipLaunchKernelGGL(step_counter_kernel, dim3(1), dim3(64), 0, stream, h->t_dev, io.ddim_tab ? io.ddim_tnext : (const int*)nullptr,
                            pair->epoch_dev, (s.single_rows && uncond) ? uncond->epoch_dev : (int*)nullptr);
         pair->epoch_prebumped = true;
@@ -2472,14 +2481,14 @@ static StepIO chain_io(const Chain1D& ch, float* x, const float* cond, const flo
 // One unguided loop inside a chain body: start at t0 with (seed, sample_offset) in the device counter, then replay the step
 // nsteps times.  The step decrements the counter; with option "pingpong" the step state lives in two slots and the step's own
 // update advances it (no step_counter_kernel launch, and a plain single-model step runs its update inside the last U-Net kernel).
-// kind: 0 DDPM, 1 DDIM and the rollout's segments (whose keys are equal, so that one graph serves them all).
+// kind: 0 DDPM, 1 DDIM and the rollout's segments (whose keys are equal, so that one graph serves them all), 3 Langevin (2: the guided loop).
 static int loop_steps(const Chain1D& ch, StepIO io, int kind, int t0, int nsteps, uint64_t seed, int64_t sample_offset) {
     const bool pp = ch.pair->O("pingpong") != 0;
     io.dec_t = 1; io.pingpong = pp ? 1 : 0;
     start_loop(ch.h, ch.pair, ch.uncond, ch.c, t0, ch.stream, seed, sample_offset);
     KeyBuilder K;
     key_common(K, kind, ch.pair, ch.uncond, ch.c, io, ch.B, ch.ws, ch.ws_bytes);
-    K(pp);
+    K(pp)(io.ula_tab)(io.ula_L)(io.ula_t_hi);
     return replay_steps(ch.h, K.k, ch.stream, nsteps, ch.use_graph,
                         [&](int q) { StepIO it = io; it.parity = q; return run_step(ch.h, ch.pair, ch.uncond, ch.c, it, 0, ch.h->t_dev, ch.B, ch.ws, ch.ws_bytes, ch.stream); },
                         ch.pair, ch.un(), pp);
@@ -2578,6 +2587,43 @@ extern "C" int cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pa
         }
         return 0;
     });
+}
+
+// Langevin (ULA) phase of sample_compose_multibodies (model/diffusion_1d.py:2002-2022, sample_step_ULA :2048-2073): for
+// t = t_start .. t_end, L iterations of x <- x + (-scalar_t eps(x, t)) ss_t + std_t z on the WHOLE state (c->cond_steps == 0: the
+// conditioning rows are rows of x and move with it).  One iteration = one step of the chain driver (gather, both U-Nets,
+// ula_update_kernel); the step state (t, inner index) advances on the device, the timestep once per L iterations, so the
+// captured iteration is replayed (t_start - t_end + 1) * L times with no host code in between.
+extern "C" int cindm_ddpm1d_sample_ula(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, const cindm_compose_desc* c,
+                                       float* x, int32_t t_start, int32_t t_end, int32_t L, const float* scalar,
+                                       const float* step_size, const float* noise_std, void* tab, size_t tab_bytes,
+                                       const float* noise_tape, uint64_t seed, int64_t sample_offset, int64_t B,
+                                       void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
+    REQUIRE(h && pair && c && x && scalar && step_size && noise_std && tab, "null argument");
+    REQUIRE(c->mode == CINDM_COMPOSE_MULTIBODY && uncond, "the Langevin phase runs the multibody composition (pair + unconditioned model)");
+    REQUIRE(c->cond_steps == 0, "the Langevin phase moves the whole state: pass cat(cond, x) as x with cond_steps = 0");
+    REQUIRE(c->objective == CINDM_OBJ_PRED_NOISE, "the Langevin score is the composed noise prediction (objective pred_noise)");
+    REQUIRE(t_start < h->T && t_end >= 0 && t_end <= t_start, "bad timestep range");
+    REQUIRE(L >= 0 && L <= 32767 && h->T <= 65536, "L must be in 0 .. 32767 (and timesteps <= 65536): the noise key packs (l, t) into one word");
+    const int n_t = t_start - t_end + 1;
+    REQUIRE(tab_bytes >= (size_t)n_t * 4 * sizeof(float), "tab too small: (t_start - t_end + 1) * 16 bytes");
+    for (const void* p : {(const void*)x, (const void*)tab, (const void*)noise_tape})
+        REQUIRE(((uintptr_t)p & 15) == 0, "x, tab and noise_tape must be 16-byte aligned");
+    if (L == 0) return 0;
+    hipStream_t stream = nullptr;
+    if (chain_stream(h, stream_, use_graph, &stream) != 0) return -1;
+    const Chain1D ch{h, pair, uncond, c, B, ws, ws_bytes, stream, use_graph};
+    float* xT = nullptr;
+    if (chain_slices(pair, uncond, c, B, ws, ws_bytes, &xT, nullptr) != 0) return -1;
+    {
+        std::vector<float> tabv((size_t)n_t * 4, 0.f);
+        for (int j = 0; j < n_t; ++j) { tabv[4 * j] = scalar[j]; tabv[4 * j + 1] = step_size[j]; tabv[4 * j + 2] = noise_std[j]; }
+        HIPCHK(hipMemcpyAsync(tab, tabv.data(), tabv.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));            // the host vector goes out of scope
+    }
+    StepIO io = chain_io(ch, x, nullptr, noise_tape, seed, sample_offset, nullptr, 0, nullptr);
+    io.ula_tab = reinterpret_cast<const float*>(tab); io.ula_L = L; io.ula_t_hi = t_start;
+    return loop_chain(ch, io, 3, (int)t_start, n_t * L, x, xT, seed, sample_offset);
 }
 
 extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, const cindm_compose_desc* c,

@@ -3465,6 +3465,85 @@ __global__ void compose_update_kernel(const ComposeArgs a) {
     compose_update_element(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Langevin (ULA) update of sample_compose_multibodies' first phase (sample_step_ULA, model/diffusion_1d.py:2048-2073, on the
+// composed score of gradient(), :1865-1926).  The state x [B, Ltot, F] is the WHOLE sequence -- the conditioning rows are part
+// of it and move too (c.cond_steps == 0; compose_gather_kernel gathers the pair / single-body rows from it).  Per element
+//   eps = sum_{o != body} pair_eps(body, o) - uncond_coef * single_eps(body)          (mode 5 of compose_update_element)
+//   x'  = (x + (fl(-scalar_t) * eps) * fl(ss_t)) + z * fl(std_t)                       (:1924, :2056, :2059: separate roundings)
+// with (scalar_t, ss_t, std_t) = tab[4 * (t_hi - t) ..], t = t_ptr[0] and the inner iteration l = t_ptr[1] read from the
+// step state; z = noise[((t_hi - t) * L + l) * noise_it_stride + i] or the counter-based normal keyed by
+// (seed, sample_off + b, 0x80000000 + l * 65536 + t, element of the full state).  A NaN in eps reaches x' (nothing selects on it).
+// One thread per four consecutive features (F % 4 == 0: the four components of one body; x, noise and tab are 16-byte aligned).
+// With c.t_next set (ping-pong step state) thread 0 writes the next iteration's (t, l) and exchange epochs to the other slot.
+struct UlaArgs {
+    ComposeArgs c;
+    const float* tab;            // [n_t][4] = (scalar, ss, std, -), row t_hi - t
+    int L, t_hi;
+    int64_t noise_it_stride;     // floats per Langevin iteration of the tape (= B * Ltot * F)
+};
+__global__ void ula_update_kernel(const UlaArgs u) {
+    const ComposeArgs& a = u.c;
+    const int t = step_scalar(a.t_ptr, a.t_imm);
+    const int l = uniform_word(a.t_ptr + 1);
+    const int64_t i4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i4 == 0 && a.t_next) {
+        const bool wrap = l + 1 >= u.L;
+        a.t_next[0] = wrap ? t - 1 : t; a.t_next[1] = wrap ? 0 : l + 1;
+        if (a.ep_next0) a.ep_next0[0] = a.ep_cur0[0] + 1;
+        if (a.ep_next1) a.ep_next1[0] = a.ep_cur1[0] + 1;
+    }
+    const int F4 = a.F >> 2;                       // bodies
+    if (i4 >= a.B * (int64_t)a.Ltot * F4) return;
+    const int body = (int)(i4 % F4);
+    const int lx = (int)((i4 / F4) % a.Ltot);
+    const int64_t b = i4 / ((int64_t)F4 * a.Ltot);
+    const int64_t i = i4 * 4;
+    const uint64_t dseed = a.dyn ? (uint64_t)a.dyn[0] : a.seed;
+    const int64_t dsoff = a.dyn ? (int64_t)a.dyn[1] : a.sample_off;
+    const int j = u.t_hi - t;
+    const float4 co = *reinterpret_cast<const float4*>(u.tab + 4 * (size_t)j);
+    const float nsc = -co.x, ss = co.y, sd = co.z;
+    const float4 xv = *reinterpret_cast<const float4*>(a.x + i);
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int o = 0; o < a.nb; ++o) {
+        if (o == body) continue;
+        const int ii = min(body, o), jj = max(body, o);
+        const int64_t row = (int64_t)pair_index(ii, jj, a.nb) * a.B + b;         // (one window: kk = 0, P rows per design)
+        const float4 e = *reinterpret_cast<const float4*>(a.pair_eps + (row * a.T + lx) * 8 + (body == ii ? 0 : 4));
+        s[0] += e.x; s[1] += e.y; s[2] += e.z; s[3] += e.w;
+    }
+    const float4 un = *reinterpret_cast<const float4*>(a.single_eps + (((int64_t)body * a.B + b) * a.T + lx) * 4);
+    const float uu[4] = {un.x, un.y, un.z, un.w};
+    float z[4];
+    if (a.noise) {
+        const float4 zv = *reinterpret_cast<const float4*>(a.noise + ((size_t)j * u.L + l) * u.noise_it_stride + i);
+        z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
+    } else {
+        counter_normal4(dseed, (uint64_t)(dsoff + b), 0x80000000u + (uint32_t)l * 65536u + (uint32_t)t, (uint32_t)(lx * F4 + body), z);
+    }
+    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float eps = s[k] - a.uncond_coef * uu[k];
+        const float g = __fmul_rn(nsc, eps);
+        v[k] = __fadd_rn(__fadd_rn(xs[k], __fmul_rn(g, ss)), __fmul_rn(z[k], sd));
+    }
+    *reinterpret_cast<float4*>(a.x_out + i) = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// the Langevin loop's counter when the step state is not ping-ponged: the inner index advances every iteration, the timestep
+// once per L iterations (t_dev[0] = t, t_dev[1] = l); e0 / e1 as step_counter_kernel
+__global__ void ula_counter_kernel(int* t_dev, int L, int* e0, int* e1) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const int l = t_dev[1] + 1;
+        if (l >= L) { t_dev[1] = 0; t_dev[0] -= 1; } else t_dev[1] = l;
+        if (e0) e0[0] = max(e0[0], e0[8]) + 1;
+        if (e1) e1[0] = max(e1[0], e1[8]) + 1;
+    }
+}
+
 // Advances the device-side step counter after the update kernel of a step (its own graph node: every reader of t in this
 // step has finished).  A "last block done" atomic inside the update kernel cost one same-address device-scope atomic
 // and one release fence per block: 46 ns each, 282 us per step for the 6144 blocks of the 2-D update.

@@ -14,8 +14,11 @@ What runs where
   * autoregressive time composition (``autoregress_time_compose_sample`` :2240-2327): the whole rollout -- every segment's
     DDIM chain and the hand-over of its tail to the next segment -- is ONE library call (``cindm_ddpm1d_sample_autoregress``,
     the DDIM step's captured graph replayed for every segment).
-Training (``forward`` / ``p_losses``) and the unreachable ULA/UHMC samplers of the reference are out of this build's
-scope and raise NotImplementedError.
+  * the Langevin (ULA) phase of ``sample_compose_multibodies`` for N > 401 (:2002-2022, ``sample_step_ULA`` :2048-2073): ONE library
+    call for the whole phase (``cindm_ddpm1d_sample_ula``: one captured Langevin iteration replayed (N - 401) * L times, timestep and
+    inner index advancing on the device), then the DDPM loop above from t = 400 on the drifted conditioning rows.
+Training (``forward`` / ``p_losses``) and the UHMC samplers of the reference (dead code there: undefined names) are out of this
+build's scope and raise NotImplementedError.
 """
 import ctypes as C
 from collections import namedtuple
@@ -25,7 +28,7 @@ from torch import nn
 
 from . import _ffi
 from .objectives import PointObjective
-from .schedule import ddim_schedule, make_schedule
+from .schedule import ddim_schedule, make_schedule, ula_schedule
 
 ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"])
 
@@ -35,14 +38,16 @@ class NoiseTape:
     ``init`` [B,L,F] (x_T, :1673 / :1987); ``step`` [T,B,L,F] indexed by timestep (:1281 / :1118);
     ``recur`` [T,R,B,L,F] relaxation draws (:1365); ``cond`` [T,B,Lc,F] inpainting draws (:1717).
     ``autoregress_time_compose_sample`` reads a leading SEGMENT index: ``init`` [K,B,R,F] (each segment's x_T, :2299 /
-    :2264) and ``step`` [K,S,B,R,F] (segment k's draw of DDIM step i, :2315 / :2280)."""
+    :2264) and ``step`` [K,S,B,R,F] (segment k's draw of DDIM step i, :2315 / :2280).
+    ``ula`` [n_t,L,B,Lc+R,F]: the Langevin draws of ``sample_compose_multibodies`` with N > 401 (:2056), on the WHOLE state, in
+    the order they are drawn: row 0 of the first axis is timestep N - 1."""
 
-    def __init__(self, init, step, recur=None, cond=None):
-        self.init, self.step, self.recur, self.cond = init, step, recur, cond
+    def __init__(self, init, step, recur=None, cond=None, ula=None):
+        self.init, self.step, self.recur, self.cond, self.ula = init, step, recur, cond, ula
 
     def to(self, device):
         f = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
-        return NoiseTape(f(self.init), f(self.step), f(self.recur), f(self.cond))
+        return NoiseTape(f(self.init), f(self.step), f(self.recur), f(self.cond), f(self.ula))
 
 
 def _exists(x):
@@ -357,7 +362,8 @@ class GaussianDiffusion1D(nn.Module):
 
     @torch.no_grad()
     def gradient(self, x_t, t, n_bodies, scalar_for_gradient=None):
-        """:1857-1982 (t <= 400): pair + unconditioned composition of eps.  ``n_bodies == 4`` (:1865-1926): six pairs, the single-body
+        """:1857-1982: pair + unconditioned composition of eps; for t > 400 the Langevin score -scalar_for_gradient[t] * eps (:1924 /
+        :1980; ``scalar_for_gradient`` = ``schedule.ula_schedule(betas_inference)[0]``, required there as in the reference).  ``n_bodies == 4`` (:1865-1926): six pairs, the single-body
         predictions weighted by 1.4 -- what ``model_predictions`` calls (:1004).  ``n_bodies == 3`` (:1927-1982, reached only by a direct
         call): three pairs, weight 1; the reference slices its batched pair output with the literal bounds 0:20 / 20:40 / 40:60, so its
         branch is defined for a batch of 20 only -- here any batch gives what batch 20 gives there (golden at 20:
@@ -367,12 +373,15 @@ class GaussianDiffusion1D(nn.Module):
         if x_t.shape[-1] != 4 * n_bodies:
             raise ValueError(f"gradient(): x_t has {x_t.shape[-1]} features, n_bodies = {n_bodies} needs {4 * n_bodies}")
         ti = self._t_int(t)
-        if ti > 400:
-            raise NotImplementedError("gradient(): t > 400 dereferences scalar_for_gradient (unreachable for N <= 401)")
+        if ti > 400 and scalar_for_gradient is None:
+            raise NotImplementedError("gradient(): t > 400 dereferences scalar_for_gradient (unreachable for N <= 401): pass "
+                                      "scalar_for_gradient (schedule.ula_schedule(betas_inference)[0]), as sample_step_ULA does")
         desc = self._compose_desc(_ffi.COMPOSE_MULTIBODY, 0, 0, self.model.horizon, n_bodies, clip=False,
                                   uncond_coef=1.4 if n_bodies == 4 else 1.0)
         desc.cond_steps = 0                             # x_t here already is cat(cond, x)
         _, _, eps = self._predict(x_t, None, ti, desc)
+        if ti > 400:                                    # (-1 * scalar[t]) * eps: the zero-dim factor is rounded to fp32 once
+            return eps * (-float(torch.as_tensor(scalar_for_gradient)[ti].to(torch.float32)))
         return eps
 
     # ------------------------------------------------------------------ one reverse step
@@ -601,13 +610,94 @@ class GaussianDiffusion1D(nn.Module):
                                   initialization_mode=initialization_mode, initialization_img=initialization_img,
                                   **build_kw)
 
+    # ------------------------------------------------------------------ Langevin (ULA) phase
+    def _ula_refusals(self, N, L, n_bodies):
+        """What the Langevin phase cannot run, with the reason (before any device work)."""
+        if n_bodies != 4:
+            raise NotImplementedError(f"the Langevin phase with n_bodies = {n_bodies}: p_sample calls gradient(x, t, 4) whatever was passed "
+                                      "(model/diffusion_1d.py:1004), so only n_bodies = 4 can finish in the reference either")
+        if self.model_unconditioned is None:
+            raise NotImplementedError("the Langevin phase needs model_unconditioned: its score is gradient()'s pair + single-body composition")
+        if self.objective != "pred_noise":
+            raise NotImplementedError(f"the Langevin phase with objective {self.objective!r}: its score is the composed noise prediction")
+        if int(L) < 0:
+            raise ValueError(f"L (Langevin iterations per timestep) must be >= 0, got {L}")
+        if int(N) > self.num_timesteps:
+            raise ValueError(f"N = {N} > num_timesteps = {self.num_timesteps}: the U-Net has no timestep {int(N) - 1}")
+        bi = self.betas_inference
+        if bi is None:
+            raise ValueError("the Langevin phase (N > 401) needs betas_inference (the script passes linear_beta_schedule(N)): it is None")
+        if len(bi) < int(N):
+            raise ValueError(f"betas_inference has {len(bi)} entries, shorter than N = {N}: the Langevin phase indexes it by the timestep")
+
+    @torch.no_grad()
+    def _run_ula(self, x, t_hi, t_lo, L, *, scalar=None, tape=None, seed=0, sample_offset=0, use_graph=True):
+        """Langevin iterations for t = t_hi .. t_lo, L per timestep, in place on the whole state x [B, Lc + R, 16] as one library
+        chain (cindm_ddpm1d_sample_ula).  ``scalar``: gradient()'s factor table indexed by t (default: from betas_inference);
+        ``tape`` [n_t, L, B, Lc + R, 16] explicit draws in processing order."""
+        device, B = x.device, x.shape[0]
+        if tuple(x.shape[1:]) != (self.conditioned_steps + self.rollout_steps, 16) or not x.is_contiguous():
+            raise ValueError(f"the Langevin state must be a contiguous [B, {self.conditioned_steps + self.rollout_steps}, 16] tensor "
+                             f"(cat(cond, x) of 4 bodies), got {tuple(x.shape)}")
+        n_t = t_hi - t_lo + 1
+        if L == 0 or n_t <= 0:
+            return x
+        sc, ss, sd = ula_schedule(self.betas_inference)
+        if scalar is not None:
+            sc = torch.as_tensor(scalar).detach().to("cpu", torch.float32)
+        idx = torch.arange(t_hi, t_lo - 1, -1)
+        sc, ss, sd = sc[idx].contiguous(), ss[idx].contiguous(), sd[idx].contiguous()
+        if tape is not None:
+            if tape.dim() != 5 or tape.shape[0] < n_t or tuple(tape.shape[1:]) != (L,) + tuple(x.shape):
+                raise ValueError(f"Langevin noise must be [>= {n_t}, {L}, {B}, {x.shape[1]}, 16] (timestep-major, first timestep first), "
+                                 f"got {tuple(tape.shape)}")
+            tape = self._f32(tape, device)[:n_t].contiguous()
+        desc = self._compose_desc(_ffi.COMPOSE_MULTIBODY, 0, 0, self.model.horizon, 4, clip=False, uncond_coef=1.4)
+        desc.cond_steps = 0                             # the conditioning rows are rows of the state here
+        tab = torch.empty(n_t * 16, dtype=torch.uint8, device=device)
+
+        def call(h, un, ws):
+            with torch.cuda.device(device):
+                _ffi.check(_ffi.lib().cindm_ddpm1d_sample_ula(
+                    h, self.model._h, un, C.byref(desc), _ffi.ptr(x), int(t_hi), int(t_lo), int(L), _ffi.ptr(sc), _ffi.ptr(ss),
+                    _ffi.ptr(sd), _ffi.ptr(tab), tab.numel(), _ffi.ptr(tape), C.c_uint64(seed), sample_offset, B,
+                    _ffi.ptr(ws), ws.numel(), _ffi.current_stream(device), int(use_graph)))
+        return self._chain(x, desc, call)
+
+    @torch.no_grad()
+    def sample_step_ULA(self, x, ts, num_samples_per_step, n_bodies, N, scalar_for_gradient, *, noise=None, seed=None,
+                        sample_offset=0, use_graph=True):
+        """:2048-2073: ``num_samples_per_step`` Langevin iterations at timestep ts[0] on the whole state x [B, Lc + R, 16]:
+        x <- x + gradient(x, t, n_bodies, scalar_for_gradient) * ss_t + randn_like(x) * std_t with ss = betas_inference * 0.035,
+        std = (2 ss) ** .5.  Returns the new state (x is not modified).  The one-timestep form of the library's Langevin chain.
+        Build-only keywords: ``noise`` [num_samples_per_step, B, Lc + R, 16] explicit draws, ``seed`` / ``sample_offset``
+        (counter-based draws keyed by (seed, sample_offset + b, t, l)), ``use_graph``."""
+        t = self._t_int(ts)
+        L = int(num_samples_per_step)
+        self._ula_refusals(t + 1, L, n_bodies)
+        if scalar_for_gradient is None or len(scalar_for_gradient) <= t:
+            raise ValueError(f"scalar_for_gradient must cover timestep {t}")
+        if not x.is_cuda:
+            raise _ffi.CindmError("sampling needs ROCm device tensors; there is no CPU execution path")
+        if seed is None and noise is None:
+            seed = self._draw_seed()
+        out = self._f32(x).clone()
+        tape = None if noise is None else noise.reshape((1,) + tuple(noise.shape))
+        return self._run_ula(out, t, t, L, scalar=scalar_for_gradient, tape=tape, seed=0 if seed is None else int(seed),
+                             sample_offset=sample_offset, use_graph=use_graph)
+
     @torch.no_grad()
     def sample_compose_multibodies(self, cond, N, L, n_bodies, *, noise=None, seed=None, sample_offset=0,
-                                   use_graph=True, t_stop=0):
-        """:1986-2042 for N <= 401 (ULA branch unreachable): x = cat(cond, noise);
-        for i = N-1..0: x[:, cs:] = p_sample(x[:, cs:], cond, i).  Returns [B, rollout_steps, 4*n_bodies]."""
-        if N > 401:
-            raise NotImplementedError("sample_step_ULA (:2048) is out of scope; use N <= 401")
+                                   use_graph=True, t_stop=0, full_state=False):
+        """:1986-2042: x = cat(cond, noise); for i = N-1 .. 401: L Langevin iterations on the whole x (``sample_step_ULA``, the
+        conditioning rows drift too); for i = 400 .. 0: x[:, cs:] = p_sample(x[:, cs:], x[:, :cs], i).  Returns
+        [B, rollout_steps, 4*n_bodies].  N <= 401 has no Langevin phase (L and n_bodies are not looked at, as before).
+        Build-only keywords: ``noise`` (NoiseTape; ``ula`` feeds the Langevin draws), ``seed`` / ``sample_offset``, ``use_graph``,
+        ``t_stop`` (truncate; > 400 stops inside the Langevin phase, after timestep t_stop), ``full_state`` (return the whole
+        [B, conditioned_steps + rollout_steps, F] state, drifted conditioning rows first)."""
+        ula = N > 401
+        if ula:
+            self._ula_refusals(N, L, n_bodies)
         if not cond.is_cuda:
             raise _ffi.CindmError("sampling needs ROCm device tensors; there is no CPU execution path")
         device = cond.device
@@ -620,9 +710,22 @@ class GaussianDiffusion1D(nn.Module):
         shape = (B, self.rollout_steps, cond.shape[2])
         img = self._init_state(shape, device, noise, seed, sample_offset, self.num_timesteps)
         desc = self._desc_for(shape, None)
-        return self._run_loop(img, cond, desc, N - 1, t_stop, noise_steps=None if noise is None else noise.step,
-                              seed=seed, sample_offset=sample_offset, inpaint_cond=None, inpaint_noise_steps=None,
-                              use_graph=use_graph)
+        t_first, cs = N - 1, self.conditioned_steps
+        if ula:
+            L = int(L)
+            if noise is not None and noise.ula is None and L > 0:
+                raise ValueError("noise.ula is required with N > 401 and L > 0 (the Langevin draws, [n_t, L, B, Lc + R, F])")
+            x = torch.cat([self._f32(cond, device), img], dim=1).contiguous()
+            self._run_ula(x, N - 1, max(401, t_stop), L, tape=None if noise is None else noise.ula, seed=seed,
+                          sample_offset=sample_offset, use_graph=use_graph)
+            if t_stop > 400:
+                return x if full_state else x[:, cs:].contiguous()
+            # the DDPM phase is conditioned on the DRIFTED rows, not on the caller's cond (:2033)
+            img, cond, t_first = x[:, cs:].contiguous(), x[:, :cs].contiguous(), 400
+        out = self._run_loop(img, cond, desc, t_first, t_stop, noise_steps=None if noise is None else noise.step,
+                             seed=seed, sample_offset=sample_offset, inpaint_cond=None, inpaint_noise_steps=None,
+                             use_graph=use_graph)
+        return torch.cat([self._f32(cond, device), out], dim=1) if full_state else out
 
     # ------------------------------------------------------------------ out of scope
     def forward(self, *a, **k):

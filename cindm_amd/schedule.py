@@ -70,3 +70,23 @@ def ddim_schedule(diffusion):
     coefs = torch.nan_to_num(coefs, nan=0.0)
     d._ddim_cache = (key, list(times), coefs.clone())
     return times, coefs
+
+
+ULA_STEP_SCALE = 0.035          # sample_step_ULA's step size: betas_inference * 0.035 (model/diffusion_1d.py:2050)
+
+
+def ula_schedule(betas_inference):
+    """(scalar, ss, std), each fp32 [len(betas_inference)] indexed by the timestep i, of the Langevin phase of
+    sample_compose_multibodies (model/diffusion_1d.py:1998-1999, :2050, :2054) in the reference's tensor arithmetic at the
+    dtype of ``betas_inference`` (fp64 for linear_beta_schedule):
+        scalar = sqrt(1 / (1 - cumprod(1 - betas_inference)))     the factor of gradient()'s -scalar[i] * eps (:1924)
+        ss     = betas_inference * 0.035                          the step size
+        std    = (2 * ss) ** .5                                   the noise scale
+    cast to fp32 last: the reference multiplies them as zero-dim tensors into fp32 tensors, which rounds each to fp32 once."""
+    b = torch.as_tensor(betas_inference).detach().to("cpu")
+    if b.dim() != 1 or not b.is_floating_point():
+        raise ValueError("betas_inference must be a 1-D floating-point tensor")
+    scalar = torch.sqrt(1 / (1 - torch.cumprod(1. - b, dim=0)))
+    ss = b * ULA_STEP_SCALE
+    std = (2 * ss) ** .5
+    return scalar.to(torch.float32), ss.to(torch.float32), std.to(torch.float32)

@@ -167,8 +167,8 @@ int  cindm_unet1d_launches_per_forward(const cindm_unet1d* h);
 /* ------------------------------------------------------------------ GaussianDiffusion1D (sampling half)
  * Replaces GaussianDiffusion1D.model_predictions :951, gradient :1857, p_mean_variance :1033,
  * q_posterior :938, predict_start_from_noise :914, p_sample :1047, p_sample_compose_inside :1190,
- * p_sample_compose_outside :1380, p_sample_loop :1656, sample_compose_multibodies :1986,
- * q_sample :2399 of model/diffusion_1d.py. */
+ * p_sample_compose_outside :1380, p_sample_loop :1656, sample_compose_multibodies :1986 (both phases),
+ * sample_step_ULA :2048, q_sample :2399 of model/diffusion_1d.py. */
 typedef struct {
     int32_t timesteps;
     /* the 13 fp32 buffers registered at :873-910, host pointers, each [timesteps] */
@@ -323,6 +323,35 @@ int  cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_
                                      const float* init_tape, const float* noise_steps,
                                      int64_t sample_offset, int64_t B, void* ws, size_t ws_bytes,
                                      void* stream, int32_t use_graph);
+
+/* Langevin (ULA) phase of sample_compose_multibodies (model/diffusion_1d.py:2002-2022 -> sample_step_ULA :2048-2073 on the
+ * composed score of gradient() :1865-1926): for t = t_start, t_start-1, ..., t_end, L times
+ *   eps = composed noise of gradient(x, t)       (CINDM_COMPOSE_MULTIBODY with c->uncond_coef; both U-Nets see timestep t)
+ *   x   = (x + (fl(-scalar_t) * eps) * fl(ss_t)) + z * fl(std_t)      (:1924, :2056, :2059, each product and sum rounded once)
+ * in place on x [B, L_tot, F], which is the WHOLE state cat(cond, x) of the reference (:1988): c->cond_steps must be 0 and
+ * L_tot = the models' horizon, so the conditioning rows are rows of x and move too.  c->objective must be CINDM_OBJ_PRED_NOISE,
+ * c->clip_denoised is not used.  That the reference only runs this above t = 400 is the caller's business: any range inside
+ * [0, timesteps) is accepted.  L == 0 returns at once.
+ * scalar / step_size / noise_std: HOST arrays [t_start - t_end + 1], entry j for timestep t_start - j, computed by the caller
+ * in the reference's fp64 tensor arithmetic and cast to fp32 (scalar_t = sqrt(1 / (1 - cumprod(1 - betas_inference)_t)) :1998-1999,
+ * ss_t = betas_inference_t * 0.035 :2050, std_t = (2 ss_t) ** .5 :2054); the library copies them to tab, a caller-owned DEVICE
+ * buffer of at least (t_start - t_end + 1) * 16 bytes, 16-byte aligned, that must stay alive until the call's work has finished.
+ * noise_tape: NULL or a device tensor [t_start - t_end + 1, L, B, L_tot, F] in processing order (row j of the first axis is
+ * timestep t_start - j), 16-byte aligned like x.  Without it z is the counter-based Gaussian keyed by
+ * (seed, sample_offset + b, step word 0x80000000 + l * 65536 + t, element of [L_tot, F]) for inner iteration l of timestep t
+ * (L <= 32767, timesteps <= 65536): the step words of x_T (= timesteps) and of the DDPM / DDIM steps (= t) are below 2^31, so
+ * the draws are disjoint from theirs, and they depend neither on B nor on how a range of timesteps is split over calls.
+ * One captured HIP graph per Langevin iteration (gather, both U-Nets, one element-wise update), replayed
+ * (t_start - t_end + 1) * L times when use_graph; the timestep and the inner index live in device memory and advance there (the
+ * timestep once per L replays).  A chain like the others: exchange time-outs are read at its end and the chain is re-run once
+ * from its initial x on the exchange-free kernels; cindm_ddpm1d_last_chain_info answers for it.  ws as cindm_ddpm1d_sample
+ * (cindm_ddpm1d_workspace_bytes for c). */
+int  cindm_ddpm1d_sample_ula(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond,
+                             const cindm_compose_desc* c, float* x, int32_t t_start, int32_t t_end, int32_t L,
+                             const float* scalar, const float* step_size, const float* noise_std,
+                             void* tab, size_t tab_bytes, const float* noise_tape, uint64_t seed,
+                             int64_t sample_offset, int64_t B, void* ws, size_t ws_bytes, void* stream,
+                             int32_t use_graph);
 
 /* out[n] ~ N(0,1): the library's counter-based Gaussian (Philox4x32-10 + Box-Muller) for the
  * initial state x_T (:1673), keyed by (seed, sample_offset + b, step_tag, element);
