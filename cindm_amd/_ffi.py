@@ -117,6 +117,8 @@ SIGNATURES = {
                                           _u64, _i64, _i64, _vp, _sz, _vp, _i32]),
     "cindm_ddpm1d_sample_guided": (C.c_int, [_vp, _vp, _vp, C.POINTER(ComposeDesc), C.POINTER(DesignDesc), _vp, _vp, _vp, _vp,
                                              _u64, _i64, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _sz, _vp, _i32]),
+    "cindm_ddpm1d_sample_ddim_guided": (C.c_int, [_vp, _vp, _vp, C.POINTER(ComposeDesc), C.POINTER(DesignDesc), _vp, _vp, _i32, _vp, _vp,
+                                                  _vp, _vp, _u64, _i64, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _sz, _vp, _i32]),
     "cindm_fill_normal": (C.c_int, [_vp, _i64, _i64, _u64, _i64, _i32, _vp]),
     "cindm_ddpm1d_launches_per_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(ComposeDesc)]),
     "cindm_ddpm1d_last_step_info": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),

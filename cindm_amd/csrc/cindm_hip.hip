@@ -2085,7 +2085,7 @@ static int step_layout(const cindm_unet1d* pair, const cindm_unet1d* uncond, con
     s.off_single_eps = o; o += al((size_t)s.single_rows * s.Tw * 4 * 4);
     s.off_ws_pair = o; o += al(cindm_unet1d_workspace_bytes(pair, s.pair_rows));
     s.off_ws_single = o; if (s.single_rows) o += al(cindm_unet1d_workspace_bytes(uncond, s.single_rows));
-    s.off_tmp = o; o += al((size_t)B * Ltot * c->n_bodies * 4 * 4);       // guided steps: x_out staging (the gradient reads neighbours of x)
+    s.off_tmp = o; o += al((size_t)B * Ltot * c->n_bodies * 4 * 4);       // guided steps: x_out staging (the gradient reads neighbours of x); guided DDIM: the second state buffer
     // the sample loops keep the chain's initial state for the exchange-free re-run and the DDIM loop its per-step tables
     // ([T][4] floats + [T] ints): both live in the caller's workspace -- no allocation after *_create
     s.off_xT = o; o += al((size_t)B * Ltot * c->n_bodies * 4 * 4);
@@ -2139,6 +2139,7 @@ struct StepIO {
     int relax; const float* recur_noise; int64_t recur_t_stride; uint32_t recur_tag;
     const float* iso; int iso_steps;
     int pingpong, parity;   // plain sample loop: step state in two slots, advanced by the update itself (no step_counter launch)
+    int state_pp;           // guided DDIM loop: x_out is the OTHER of two state buffers -- the update writes it directly (no staging, no copy)
     const float* ula_tab; int ula_L, ula_t_hi;         // Langevin loop: per-timestep (scalar, ss, std, -) rows (device), inner count, first timestep
 };
 
@@ -2209,7 +2210,7 @@ static int run_step(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, c
         a.relax = io.relax; a.recur_noise = io.recur_noise; a.recur_t_stride = io.recur_t_stride; a.recur_tag = io.recur_tag;
         a.iso = io.iso; a.iso_steps = io.iso_steps;
         a.betas = tb; a.ac = tb + 1 * T; a.acp = tb + 2 * T;
-        a.x_out = (float*)(w + s.off_tmp);
+        a.x_out = io.state_pp ? io.x_out : (float*)(w + s.off_tmp);
     }
 
     const float* unet_in = io.x;
@@ -2272,7 +2273,7 @@ static int run_step(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, c
         if (s.single_rows && uncond) uncond->epoch_prebumped = true;
     }
     HIPCHK(hipGetLastError());
-    if (guided) HIPCHK(hipMemcpyAsync(io.x_out, a.x_out, (size_t)ne * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    if (guided && !io.state_pp) HIPCHK(hipMemcpyAsync(io.x_out, a.x_out, (size_t)ne * sizeof(float), hipMemcpyDeviceToDevice, stream));
     return 0;
 }
 
@@ -2372,13 +2373,14 @@ static int replay_steps(cindm_ddpm1d* h, const std::vector<unsigned char>& key, 
 // against them the bounded spin + recovery below remains.)  Concurrent chains need their own U-Net handles.
 // the chain-level slices of a step workspace: the x_T snapshot of the recovery and the DDIM loop's per-step tables (step_layout)
 static int chain_slices(const cindm_unet1d* pair, const cindm_unet1d* uncond, const cindm_compose_desc* c, int64_t B, void* ws,
-                        size_t ws_bytes, float** xT, float** ddim) {
+                        size_t ws_bytes, float** xT, float** ddim, float** state2 = nullptr) {
     REQUIRE(pair && c && ws, "null argument");
     StepLayout s;
     if (step_layout(pair, uncond, c, B, state_len(pair, c), s) != 0) return -1;
     REQUIRE(ws_bytes >= s.total, "workspace too small (cindm_ddpm1d_workspace_bytes)");
     *xT = reinterpret_cast<float*>((char*)ws + s.off_xT);
     if (ddim) *ddim = reinterpret_cast<float*>((char*)ws + s.off_ddim);
+    if (state2) *state2 = reinterpret_cast<float*>((char*)ws + s.off_tmp);      // (the guided steps' staging slice: one state)
     return 0;
 }
 
@@ -2481,7 +2483,8 @@ static StepIO chain_io(const Chain1D& ch, float* x, const float* cond, const flo
 // One unguided loop inside a chain body: start at t0 with (seed, sample_offset) in the device counter, then replay the step
 // nsteps times.  The step decrements the counter; with option "pingpong" the step state lives in two slots and the step's own
 // update advances it (no step_counter_kernel launch, and a plain single-model step runs its update inside the last U-Net kernel).
-// kind: 0 DDPM, 1 DDIM and the rollout's segments (whose keys are equal, so that one graph serves them all), 3 Langevin (2: the guided loop).
+// kind: 0 DDPM, 1 DDIM and the rollout's segments (whose keys are equal, so that one graph serves them all), 3 Langevin (2: the guided loop,
+// 4: the guided DDIM loop).
 static int loop_steps(const Chain1D& ch, StepIO io, int kind, int t0, int nsteps, uint64_t seed, int64_t sample_offset) {
     const bool pp = ch.pair->O("pingpong") != 0;
     io.dec_t = 1; io.pingpong = pp ? 1 : 0;
@@ -2672,6 +2675,71 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
         key_common(K, 2, pair, uncond, c, io, B, ws, ws_bytes);
         K(*dz)(recur_noise_steps)(R);
         return replay_steps(h, K.k, stream, t_start - t_end + 1, use_graph, step, pair, ch.un());
+    });
+}
+
+// Guided DDIM (ddim_sample :1724-1804 with design_fn = the built-in objective and "-recurrence-N" guidance, i.e. through the DDIM
+// return of p_sample_compose_inside :1284-1376).  One DDIM step = R iterations of [U-Net(s), one compose_update_kernel launch]:
+// iterations 0 .. R-2 relax (x <- a_t (mean - g | overwrite) + b_t z'), iteration R-1 is the DDIM update on (eps + g, x_start).
+// The gradient reads neighbours of its input, so the state alternates between the caller's x and one workspace slice (the guided
+// DDPM step's staging slice, unused here): iteration k of the chain reads buffer k & 1 and writes the other -- no staging copy.
+// The step state (t, step index, exchange epochs) alternates between its two slots per ITERATION as well, written by the update
+// itself (compose_advance: a relaxation iteration hands t and the step index on unchanged), so there is no counter launch either.
+// A graph holds two steps (2 R iterations: both parities return to 0); when n_steps * R is odd the result is copied to x once, after the chain.
+extern "C" int cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, const cindm_compose_desc* c,
+                                               const cindm_design_desc* dz, float* x, const float* cond, int32_t n_steps,
+                                               const int32_t* times, const float* coefs, const float* noise_steps,
+                                               const float* recur_noise_steps, uint64_t seed, int64_t sample_offset,
+                                               const float* inpaint_cond, int32_t inpaint_steps, const float* inpaint_noise_steps,
+                                               const float* initial_state_overwrite, int32_t overwrite_steps, int64_t B,
+                                               void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
+    REQUIRE(h && pair && c && dz && x && times && coefs, "null argument");
+    REQUIRE(dz->mode == 1 || dz->mode == 2, "design objective mode must be 1 (L2) or 2 (L2square)");
+    REQUIRE(dz->recurrence >= 1 && dz->recurrence <= 64,
+            "guided DDIM needs a recurrence count in 1 .. 64 (without recurrence the reference returns no noise prediction)");
+    const int Ltot = state_len(pair, c);
+    REQUIRE(dz->last_n_step >= 1 && dz->last_n_step <= Ltot, "last_n_step out of range");
+    REQUIRE(!initial_state_overwrite || (overwrite_steps >= 1 && overwrite_steps <= Ltot), "bad overwrite_steps");
+    REQUIRE(!inpaint_cond || (inpaint_steps >= 1 && inpaint_steps <= Ltot), "bad inpaint_steps");
+    hipStream_t stream = nullptr;
+    if (chain_stream(h, stream_, use_graph, &stream) != 0) return -1;
+    const Chain1D ch{h, pair, uncond, c, B, ws, ws_bytes, stream, use_graph};
+    float* xT = nullptr; float* ddim_buf = nullptr; float* x2 = nullptr; int* tn_dev = nullptr;
+    if (chain_slices(pair, uncond, c, B, ws, ws_bytes, &xT, &ddim_buf, &x2) != 0) return -1;
+    REQUIRE(n_steps <= pair->d.timesteps, "more DDIM steps than the U-Net's timesteps");
+    if (upload_ddim_tables(h->T, n_steps, times, coefs, ddim_buf, stream, &tn_dev) != 0) return -1;
+    const int64_t n_state = ch.n_state();
+    const int R = dz->recurrence;
+    StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
+    io.ddim_tab = ddim_buf; io.ddim_tnext = tn_dev;
+    io.dz = dz; io.iso = initial_state_overwrite; io.iso_steps = initial_state_overwrite ? overwrite_steps : 0;
+    io.recur_t_stride = (int64_t)R * n_state;
+    io.pingpong = 1; io.state_pp = 1;
+    float* const buf[2] = {x, x2};
+    auto step = [&](int q) -> int {
+        for (int r = 0; r < R; ++r) {
+            StepIO it = io;
+            const int p = (q * R + r) & 1;          // parity of the chain's iteration: after two steps it is 0 again
+            it.parity = p; it.x = buf[p]; it.x_out = buf[1 - p];
+            it.relax = (r < R - 1) ? 1 : 0;
+            it.recur_noise = recur_noise_steps ? recur_noise_steps + (size_t)r * n_state : nullptr;
+            it.recur_tag = 0x10000u * (uint32_t)(r + 1);
+            if (run_step(h, pair, uncond, c, it, 0, h->t_dev, B, ws, ws_bytes, stream) != 0) return -1;
+        }
+        return 0;
+    };
+    return run_chain_with_recovery(h, pair, ch.un(), x, xT, (size_t)n_state, stream, [&]() -> int {
+        if (prepare_step_ws(pair, uncond, c, B, ws, ws_bytes, stream) != 0) return -1;
+        start_loop(h, pair, uncond, c, (int)times[0], stream, seed, sample_offset);
+        KeyBuilder K;
+        key_common(K, 4, pair, uncond, c, io, B, ws, ws_bytes);
+        K(*dz)(recur_noise_steps)(R);
+        const int rc = replay_steps(h, K.k, stream, n_steps, use_graph, step, pair, ch.un(), true);
+        if (rc == 0 && (((int64_t)n_steps * R) & 1)) {        // the last iteration wrote the workspace buffer
+            HIPCHK(hipMemcpyAsync(x, x2, (size_t)n_state * sizeof(float), hipMemcpyDeviceToDevice, stream));
+            if (use_graph) HIPCHK(hipStreamSynchronize(stream));
+        }
+        return rc;
     });
 }
 

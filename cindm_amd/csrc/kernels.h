@@ -2434,7 +2434,7 @@ struct ComposeArgs {
     int dz_mode;                 // 0 off, 1 "L2", 2 "L2square"
     int dz_alpha;                // 1: scale the gradient by eta_t = beta_t / sqrt(alphas_cumprod_prev_t) (standard-alpha)
     int dz_last_n; float dz_coef, dz_tc, dz_tx, dz_ty;
-    int relax;                   // this launch is a relaxation iteration (:1365-1367): x <- a_t pred + b_t z'
+    int relax;                   // this launch is a relaxation iteration (:1365-1367): x <- a_t pred + b_t z' (guided DDIM: and the step state stays)
     const float* recur_noise;    // explicit z' of this iteration (+ t * recur_t_stride), or null (counter-based, tag below)
     int64_t recur_t_stride; uint32_t recur_tag;
     const float* iso; int iso_steps;     // initial_state_overwrite [B, iso_steps, F] (:1352-1361) or null
@@ -2447,7 +2447,8 @@ struct ComposeArgs {
 };
 __device__ __forceinline__ void compose_advance(const ComposeArgs& a, int t) {
     if (!a.t_next) return;
-    if (a.ddim_tab) { const int sidx = a.step_idx[0]; a.t_next[0] = max(a.ddim_tnext[sidx], 0); a.sidx_next[0] = sidx + 1; }   // (step_counter_kernel's rule)
+    if (a.ddim_tab && a.relax) { a.t_next[0] = t; a.sidx_next[0] = a.step_idx[0]; }      // guided DDIM: a relaxation iteration stays on its step
+    else if (a.ddim_tab) { const int sidx = a.step_idx[0]; a.t_next[0] = max(a.ddim_tnext[sidx], 0); a.sidx_next[0] = sidx + 1; }   // (step_counter_kernel's rule)
     else a.t_next[0] = t - 1;
     if (a.ep_next0) a.ep_next0[0] = a.ep_cur0[0] + 1;
     if (a.ep_next1) a.ep_next1[0] = a.ep_cur1[0] + 1;
@@ -3379,7 +3380,8 @@ __device__ void compose_update_element(const ComposeArgs& a, int64_t i) {
     if (a.x0_out) a.x0_out[i] = x0;
     if (a.eps_out) a.eps_out[i] = eps;
     if (a.x_out && a.dz_mode) {
-        // guided update with the built-in objective (x_out never aliases x here: the gradient reads neighbours)
+        // guided update with the built-in objective (x_out never aliases x here: the gradient reads neighbours).  With ddim_tab set
+        // too this is the guided DDIM loop: relaxation iterations as below, the last iteration is the DDIM update on (eps + g, x0).
         float g = 0.f;
         if (comp < 2) {
             if (lx >= a.Ltot - a.dz_last_n) {
@@ -3406,9 +3408,28 @@ __device__ void compose_update_element(const ComposeArgs& a, int64_t i) {
         float v;
         if (a.relax) {
             const float ratio = a.ac[t] / a.acp[t];
-            const float z = a.recur_noise ? a.recur_noise[(size_t)t * a.recur_t_stride + i]
+            // (the guided DDIM loop's tapes are indexed by the step index, the DDPM loop's by t)
+            const float z = a.recur_noise ? a.recur_noise[(size_t)(a.ddim_tab ? sidx : t) * a.recur_t_stride + i]
                                           : counter_normal(dseed ^ 0x7f4a7c15u, (uint64_t)(dsoff + b), a.recur_tag + (uint32_t)t, el);
             v = sqrtf(ratio) * pred + sqrtf(1.0f - ratio) * z;
+        } else if (a.ddim_tab) {
+            // guided DDIM (ddim_sample :1772-1793 on p_sample_compose_inside's DDIM return :1375-1376): the last iteration hands
+            // (eps + g, x_start) to the DDIM update; its own pred / relaxed state is never used.  Roundings as the unguided branch below.
+            const int tn = a.ddim_tnext[sidx];
+            v = x0;
+            if (tn >= 0) {
+                const float epsd = __fadd_rn(eps, g);
+                const float san = a.ddim_tab[4 * sidx], cc = a.ddim_tab[4 * sidx + 1], sg = a.ddim_tab[4 * sidx + 2];
+                const float z = a.noise ? a.noise[(size_t)sidx * a.noise_t_stride + i]
+                                : (sg != 0.f ? counter_normal(dseed, (uint64_t)(dsoff + b), (uint32_t)t, el) : 0.f);
+                v = __fadd_rn(__fadd_rn(__fmul_rn(x0, san), __fmul_rn(cc, epsd)), __fmul_rn(sg, z));
+                if (a.inp_cond && lx < a.inp_steps) {      // inpainting overwrite with q_sample(cond, time) (:1790-1793)
+                    const size_t ci = ((size_t)b * a.inp_steps + lx) * a.F + f;
+                    const float z2 = a.inp_noise ? a.inp_noise[(size_t)sidx * a.inp_noise_t_stride + ci]
+                                                 : counter_normal(dseed ^ 0x5bd1e995u, (uint64_t)(dsoff + b), (uint32_t)t, el);
+                    v = a.sqrt_ac[t] * a.inp_cond[ci] + a.sqrt_1mac[t] * z2;
+                }
+            }
         } else {
             v = pred;
             if (a.add_noise && t > 0) {

@@ -9,8 +9,10 @@ What runs where
   * ``design_fn`` guidance is a user Python callable: its gradient is taken by PyTorch autograd
     between two library calls per step, exactly where the reference takes it.
   * DDIM (``sampling_timesteps < timesteps``, ``ddim_sample`` :1724-1804): unguided = ONE library call
-    (``cindm_ddpm1d_sample_ddim``, same captured-step replay with per-step coefficient tables); guided (recurrence
-    guidance) = library predictions + the user's gradient per step.
+    (``cindm_ddpm1d_sample_ddim``, same captured-step replay with per-step coefficient tables); guided by a ``PointObjective``
+    ("standard" / "standard-alpha" with ``-recurrence-N``) = ONE library call too (``cindm_ddpm1d_sample_ddim_guided``: relaxation
+    iterations and the DDIM update of (eps + grad, x_start) inside the captured step, state and step state ping-ponged); guided by
+    any other callable or guidance (recurrence guidance) = library predictions + the user's gradient per step.
   * autoregressive time composition (``autoregress_time_compose_sample`` :2240-2327): the whole rollout -- every segment's
     DDIM chain and the hand-over of its tail to the next segment -- is ONE library call (``cindm_ddpm1d_sample_autoregress``,
     the DDIM step's captured graph replayed for every segment).
@@ -517,6 +519,29 @@ class GaussianDiffusion1D(nn.Module):
                     int(t_start), int(t_end), B, _ffi.ptr(ws), ws.numel(), _ffi.current_stream(device), int(use_graph)))
         return self._chain(img, desc, call)
 
+    @torch.no_grad()
+    def _run_guided_ddim(self, img, cond, desc, dz, times, coefs, *, noise, seed, sample_offset, inpaint_cond,
+                         initial_state_overwrite, use_graph=True):
+        """DDIM steps ``times[0] .. times[-2]`` guided by the built-in objective as one library call
+        (cindm_ddpm1d_sample_ddim_guided); ``noise`` rows (step / recur / cond) are indexed by the position in ``times``."""
+        device, B = img.device, img.shape[0]
+        S = len(times) - 1
+        cond_d = self._f32(cond, device) if (cond is not None and self.conditioned_steps != 0) else None
+        inp = self._f32(inpaint_cond, device)
+        iso = self._f32(initial_state_overwrite, device)
+        tarr = (C.c_int32 * (S + 1))(*times)
+        carr = coefs.contiguous()
+
+        def call(h, un, ws):
+            with torch.cuda.device(device):
+                _ffi.check(_ffi.lib().cindm_ddpm1d_sample_ddim_guided(
+                    h, self.model._h, un, C.byref(desc), C.byref(dz), _ffi.ptr(img), _ffi.ptr(cond_d), S, tarr, _ffi.ptr(carr),
+                    _ffi.ptr(None if noise is None else noise.step), _ffi.ptr(None if noise is None else noise.recur),
+                    C.c_uint64(seed), sample_offset, _ffi.ptr(inp), 0 if inp is None else inp.shape[1],
+                    _ffi.ptr(None if noise is None else noise.cond), _ffi.ptr(iso), 0 if iso is None else iso.shape[1],
+                    B, _ffi.ptr(ws), ws.numel(), _ffi.current_stream(device), int(use_graph)))
+        return self._chain(img, desc, call)
+
     def _init_state(self, shape, device, noise, seed, sample_offset, tag):
         if noise is not None:
             return self._f32(noise.init, device).clone()
@@ -748,8 +773,11 @@ class GaussianDiffusion1D(nn.Module):
         ``noise``: a NoiseTape whose ``step`` / ``recur`` / ``cond`` rows are indexed by the DDIM STEP index.
         Without ``design_fn`` the whole loop is one library call (``cindm_ddpm1d_sample_ddim``); as in the reference the
         prediction then ignores the compose keywords (:1755).  With ``design_fn`` (recurrence guidance only -- the
-        reference's non-recurrence branch does not return a noise prediction, :1283) each step is ``recurrence``
-        library predictions + the user's autograd gradient, and the DDIM update of the tiny state runs in torch."""
+        reference's non-recurrence branch does not return a noise prediction, :1283) the prediction honours them.  A
+        ``PointObjective`` under "standard" / "standard-alpha" ``-recurrence-N`` (N >= 1, last_n_step <= L) runs as one library
+        chain (``cindm_ddpm1d_sample_ddim_guided``; counter-based draws keyed by (seed, sample_offset + b, t, element) when there
+        is no tape); any other callable or guidance: each step is ``recurrence`` library predictions + the user's autograd
+        gradient, and the DDIM update of the tiny state runs in torch."""
         device = self.betas.device
         if device.type != "cuda":
             raise _ffi.CindmError("GaussianDiffusion1D is on the CPU: move it to a ROCm device; there is no CPU execution path")
@@ -792,6 +820,12 @@ class GaussianDiffusion1D(nn.Module):
         n_composed = 0 if n_composed is None else n_composed
         desc = self._desc_for(shape, compose_mode, n_composed, compose_start_step, shape[1], compose_n_bodies,
                               clip=True)     # p_sample_compose_inside's own default: clip_denoised is not forwarded (:1758-1770)
+        dz = design_fn.descriptor(design_guidance) if isinstance(design_fn, PointObjective) else None
+        if dz is not None and dz.recurrence >= 1 and design_fn.last_n_step <= shape[1]:
+            # built-in objective: relaxations, gradient, overwrite and the DDIM update stay inside the captured step
+            return self._run_guided_ddim(img, cond, desc, dz, times, coefs, noise=noise, seed=seed, sample_offset=sample_offset,
+                                         inpaint_cond=inpaint, initial_state_overwrite=initial_state_overwrite,
+                                         use_graph=use_graph)
         coefs = coefs.to(device)
         img_T = img
 

@@ -6,7 +6,8 @@ It is an ordinary ``design_fn`` callable (``Tensor[B, L, 4*n_bodies] -> scalar``
 path; in addition ``GaussianDiffusion1D`` recognises it and, for "standard" / "standard-alpha" guidance (with or
 without ``-recurrence-N``), evaluates its closed-form gradient inside the library's update kernel so that the whole
 guided reverse loop stays one captured-graph replay (``cindm_ddpm1d_sample_guided``) -- no autograd, no host code in
-the loop."""
+the loop.  With ``sampling_timesteps < timesteps`` and a ``-recurrence-N`` guidance (N >= 1) the guided DDIM loop is one
+library chain in the same way (``cindm_ddpm1d_sample_ddim_guided``)."""
 import torch
 
 from . import _ffi

@@ -303,6 +303,34 @@ int  cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d*
                               const float* inpaint_noise_steps, int64_t B,
                               void* ws, size_t ws_bytes, void* stream, int32_t use_graph);
 
+/* Guided DDIM loop (ddim_sample :1724-1804 with design_fn = the built-in objective and "standard" / "standard-alpha"
+ * "-recurrence-N" guidance, N = dz->recurrence >= 1; every step goes through the DDIM return of p_sample_compose_inside,
+ * :1284-1376).  Per DDIM step i, (t, t_next) = (times[i], times[i+1]), on the state x [B, L_tot, F]:
+ *   y = x; for r = 0 .. N-1: (mean, x_start, eps) = p_mean_variance(y, t) under c (the compose descriptor IS honoured here,
+ *   unlike cindm_ddpm1d_sample_ddim; x_start clamped when c->clip_denoised -- the reference always clamps on this path);
+ *   g = [eta_t] grad objective(y), eta_t = betas[t] / sqrt(alphas_cumprod_prev[t]) when dz->alpha;
+ *   pred = mean - g, rows < overwrite_steps replaced by initial_state_overwrite [B, overwrite_steps, F] if given;
+ *   y = sqrt(abar_t/abar_{t-1}) pred + sqrt(1 - abar_t/abar_{t-1}) z'_{i,r}        (not computed for r = N-1: never used);
+ *   x = x_start * sqrt(alpha_next) + c * (eps + g) + sigma * z_i with (x_start, eps, g) of iteration N-1, each product and
+ *   sum rounded once; x = x_start when t_next < 0; otherwise, when inpaint_cond is given,
+ *   x[:, :inpaint_steps] = q_sample(inpaint_cond, t, z^c_i).
+ * times / coefs as cindm_ddpm1d_sample_ddim.  Tapes, when given, are indexed by the STEP index: noise_steps [n_steps, B, L_tot, F],
+ * recur_noise_steps [n_steps, N, B, L_tot, F], inpaint_noise_steps [n_steps, B, inpaint_steps, F].  Without them the draws are
+ * the counter-based Gaussians of cindm_ddpm1d_sample_guided (relaxation r of timestep t) and cindm_ddpm1d_sample_ddim (step and
+ * inpainting draws), keyed by (seed, sample_offset + b, t, element): a design's result does not depend on the batch partition.
+ * One relaxation iteration = the U-Net launches + one update launch: the state alternates between x and a slice of ws, the step
+ * state between its two device slots, both advanced by the update itself (no copy, no counter launch in the captured step; two
+ * DDIM steps per graph).  A chain like the others (recovery, range rule, graph cache, use_graph = 0 streams the same launches);
+ * ws as cindm_ddpm1d_sample (cindm_ddpm1d_workspace_bytes for c already holds the second state buffer). */
+int  cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond,
+                                     const cindm_compose_desc* c, const cindm_design_desc* dz, float* x,
+                                     const float* cond, int32_t n_steps, const int32_t* times, const float* coefs,
+                                     const float* noise_steps, const float* recur_noise_steps, uint64_t seed,
+                                     int64_t sample_offset, const float* inpaint_cond, int32_t inpaint_steps,
+                                     const float* inpaint_noise_steps, const float* initial_state_overwrite,
+                                     int32_t overwrite_steps, int64_t B, void* ws, size_t ws_bytes, void* stream,
+                                     int32_t use_graph);
+
 /* Autoregressive time composition (autoregress_time_compose_sample, model/diffusion_1d.py:2240-2327):
  * n_seg segments of the unguided DDIM loop above, each on a fresh x_T [B, R, F] (R = the state length
  * the descriptor implies, c->cond_steps = Lc >= 1, R >= Lc) and conditioned on cond_buf [B, Lc, F]:
