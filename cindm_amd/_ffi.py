@@ -163,6 +163,9 @@ SIGNATURES = {
     "cindm_ddpm2d_sample_force": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _u64, _i64, _i32, _i32, _i32,
                                             C.c_float, C.c_float, C.c_float, C.c_float, _i32, _i32, _vp, _vp, _vp, _sz, _vp, _sz,
                                             _vp, _i32]),
+    "cindm_ddpm2d_sample_ddim_force": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _u64,
+                                                 _i64, _i32, C.c_float, C.c_float, C.c_float, C.c_float, _i32, _i32, _vp, _vp, _sz,
+                                                 _vp, _sz, _vp, _i32]),
 }
 
 

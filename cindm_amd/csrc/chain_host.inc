@@ -70,16 +70,17 @@ static int replay_once(hipStream_t stream, int nsteps, int use_graph, StepFn ste
 }
 
 // The DDIM loops' schedule (times[0 .. n_steps], strictly decreasing inside [0, T), the last may be -1) and their per-step device
-// tables: [n_steps][4] floats (3 coefficients + pad) at dst, then [n_steps] next-times (*tn_out).  dst holds n_steps * 5 words: the
-// caller checks that (and whatever else bounds n_steps for it) before the call.
+// tables: [n_steps][4] floats (3 coefficients + the step's guidance weight, 0 without `weights`) at dst, then [n_steps] next-times
+// (*tn_out).  dst holds n_steps * 5 words: the caller checks that (and whatever else bounds n_steps for it) before the call.
 static int upload_ddim_tables(int T, int32_t n_steps, const int32_t* times, const float* coefs, float* dst, hipStream_t stream,
-                              int** tn_out) {
+                              int** tn_out, const float* weights = nullptr) {
     REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     for (int i = 0; i < n_steps; ++i) REQUIRE(times[i] >= 0 && times[i] < T && times[i + 1] < times[i] && times[i + 1] >= -1, "bad DDIM time schedule");
     std::vector<float> tabv((size_t)n_steps * 4, 0.f);
     std::vector<int> tnv(n_steps);
     for (int i = 0; i < n_steps; ++i) {
         tabv[4 * i] = coefs[3 * i]; tabv[4 * i + 1] = coefs[3 * i + 1]; tabv[4 * i + 2] = coefs[3 * i + 2];
+        if (weights) tabv[4 * i + 3] = weights[i];
         tnv[i] = times[i + 1];
     }
     int* tn_dev = reinterpret_cast<int*>(dst + (size_t)n_steps * 4);

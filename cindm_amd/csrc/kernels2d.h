@@ -2936,6 +2936,87 @@ __global__ __launch_bounds__(256) void ddim2d_update_kernel(const Ddim2dArgs a) 
     }
 }
 
+// The guided form of ddim2d_update_kernel: the same update, and the "standard-alpha" guidance shift in the same
+// pass -- x = x' - w g, with g = the design gradient taken at this step's INPUT state (a buffer shaped like x, written before
+// the U-Net ran) and w = the 4th word of the step's table row (the eta of the DDPM steps this DDIM step skips, summed by the
+// caller).  Applied on the last pair (time_next < 0) too, as p_sample applies it at t = 0.  The product and the difference
+// round separately, as `x' - w * g` does in torch: the chain equals the per-step loop bit for bit.  One more 16-byte load per
+// element and no second pass over the state; threads, draws and the in-place argument are those of ddim2d_update_kernel.
+__global__ __launch_bounds__(256) void ddim2d_guided_update_kernel(const Ddim2dArgs a, const float* __restrict__ grad) {
+    const int G = a.CP >> 2;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int t = uniform_word(a.t_dev);
+    const int sidx = uniform_word(a.t_dev + 2);
+    const int total = a.B * a.HW * G;
+    if (i >= total) return;
+    const int g = i % G;
+    const int bp = i / G;
+    const int pix = bp % a.HW;
+    const int b = bp / a.HW;
+    const int c0 = 4 * g, Cs = a.C - 3;
+    const int tn = uniform_word(a.tnext + sidx);
+    const float san = uniform_float(a.tab + 4 * sidx), cc = uniform_float(a.tab + 4 * sidx + 1), sg = uniform_float(a.tab + 4 * sidx + 2);
+    const float wg = uniform_float(a.tab + 4 * sidx + 3);
+    const float ra = a.sqrt_recip[t], rb = a.sqrt_recipm1[t];
+    const int obj = (a.use_avg >> 4) & 3;
+    const float sa = obj == 2 ? a.sqrt_ac[t] : 0.f, sm = obj == 2 ? a.sqrt_1mac[t] : 0.f;
+    const bool avg = (a.use_avg & 1) != 0;
+    const bool draws = tn >= 0 && (a.noise_state != nullptr || sg != 0.f);
+    float es[4] = {0.f, 0.f, 0.f, 0.f};
+    if (obj == 0 && c0 < Cs) {
+        for (int k = 0; k < a.nb; ++k) {
+            const float4 e = *reinterpret_cast<const float4*>(a.eps + (((size_t)(b * a.nb + k) * a.HW) + pix) * a.CP + c0);
+            es[0] += e.x; es[1] += e.y; es[2] += e.z; es[3] += e.w;
+        }
+        if (avg) { const float inv = (float)a.nb; es[0] /= inv; es[1] /= inv; es[2] /= inv; es[3] /= inv; }
+    }
+    float zs[4] = {0.f, 0.f, 0.f, 0.f};
+    if (draws && c0 < Cs) {
+        if (a.noise_state) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (c0 + j < Cs) zs[j] = a.noise_state[(size_t)sidx * a.ns_t_stride + ((size_t)b * a.HW + pix) * Cs + c0 + j];
+        } else {
+            noise2d_state4(a.seed, a.sample_off + b, (uint32_t)t, (uint32_t)pix, G, g, zs);
+        }
+    }
+    for (int k = 0; k < a.nb; ++k) {
+        const int im = b * a.nb + k;
+        const size_t o = (((size_t)im * a.HW) + pix) * a.CP + c0;
+        const float4 e4 = *reinterpret_cast<const float4*>(a.eps + o);
+        const float4 x4 = *reinterpret_cast<const float4*>(a.x + o);
+        const float4 g4 = *reinterpret_cast<const float4*>(grad + o);
+        const float ev[4] = {e4.x, e4.y, e4.z, e4.w}, xv[4] = {x4.x, x4.y, x4.z, x4.w}, gv[4] = {g4.x, g4.y, g4.z, g4.w};
+        float zb[4] = {0.f, 0.f, 0.f, 0.f};
+        if (draws && c0 + 3 >= Cs && c0 < a.C) {
+            if (a.noise_bound) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (c0 + j >= Cs && c0 + j < a.C)
+                        zb[j] = a.noise_bound[(size_t)sidx * a.nb_t_stride + ((size_t)im * a.HW + pix) * 3 + (c0 + j - Cs)];
+            } else {
+                noise2d_bound4(a.seed, (a.sample_off + b) * a.nb + k, (uint32_t)t, (uint32_t)pix, G, g, zb);
+            }
+        }
+        float r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j;
+            const float e = (obj == 0 && c < Cs) ? es[j] : ev[j];
+            const float x0 = clamp_pm1(obj == 0 ? __fsub_rn(__fmul_rn(ra, xv[j]), __fmul_rn(rb, e)) : obj == 1 ? e
+                                                : __fsub_rn(__fmul_rn(sa, xv[j]), __fmul_rn(sm, e)));
+            const float er = __fsub_rn(__fmul_rn(ra, xv[j]), x0) / rb;
+            float v = x0;
+            if (tn >= 0) {
+                v = __fadd_rn(__fmul_rn(x0, san), __fmul_rn(cc, er));
+                if (draws) v = __fadd_rn(v, __fmul_rn(sg, c < Cs ? zs[j] : zb[j]));
+            }
+            r[j] = c < a.C ? __fsub_rn(v, __fmul_rn(wg, gv[j])) : 0.f;
+        }
+        *reinterpret_cast<float4*>(a.x_out + o) = make_float4(r[0], r[1], r[2], r[3]);
+    }
+}
+
 // x_T for the 2-D path from the counter-based generator (state channels shared over the boundaries of a design)
 __global__ void fill_noise2d_kernel(float* x, int B, int nb, int HW, int C, int CP, uint64_t seed, int64_t off, uint32_t tag) {
     const int G = CP >> 2;

@@ -11,8 +11,10 @@ What runs where
   * DDIM (``sampling_timesteps < timesteps``, ``ddim_sample``) without ``design_fn`` is ONE call too
     (``cindm_ddpm2d_sample_ddim``: U-Net + one element-wise DDIM update per captured step, t and the step index
     advanced on the device).  The reference's own 2-D DDIM cannot run; the semantics are defined in ``ddim_sample``.
-Training, self-conditioning, guided DDIM, DDIM with share_noise=False and return_all_timesteps are outside this
-build's scope and raise NotImplementedError.
+  * DDIM with ``design_fn=ForceObjective`` under ``"standard-alpha"`` is ONE call as well (``cindm_ddpm2d_sample_ddim_force``:
+    surrogate gradient + U-Net + one update that carries the guidance shift, per captured step).
+Training, self-conditioning, DDIM with any other ``design_fn`` / guidance, DDIM with share_noise=False and
+return_all_timesteps are outside this build's scope and raise NotImplementedError.
 """
 import ctypes as C
 from collections import namedtuple
@@ -372,24 +374,38 @@ class GaussianDiffusion(nn.Module):
         tensor arithmetic -- the 1-D path's schedule (schedule.ddim_schedule)."""
         return ddim_schedule(self)
 
+    def ddim_guidance_weights(self):
+        """fp32 [S]: the "standard-alpha" guidance weight of every DDIM step -- for the pair (t, t_next) of ddim_schedule() the sum
+        (in float64, rounded once) of eta = coeff_ratio * betas.flip(0) over the DDPM steps t_next+1 .. t that the step stands for,
+        i.e. the guidance ``p_sample`` would have applied on the way.  Strides of one step give eta[t] itself."""
+        times, _ = self.ddim_schedule()
+        eta = (self.coeff_ratio * self.betas.detach().to("cpu", torch.float32).flip(0)).double()
+        return torch.stack([eta[tn + 1:t + 1].sum() for t, tn in zip(times[:-1], times[1:])]).float()
+
     @torch.no_grad()
     def ddim_sample(self, shape, design_fn=None, design_guidance="standard", return_all_timesteps=False, *, noise=None, seed=0,
-                    sample_offset=0, use_graph=True, init_img=None, step_range=None, device=None):
+                    sample_offset=0, use_graph=True, init_img=None, step_range=None, device=None, fused=True):
         """DDIM sampling of the 2-D path (:910-949; the reference's own body cannot run, so this build defines it from its
         working pieces).  Returns [B, nb, C, H, W].  With (times, coefs) = ddim_schedule(), for each pair (t, t_next):
         (pred_noise, x_start) = model_predictions(x, t, clip_x_start=True, rederive_pred_noise=True, share_noise=True);
         x = x_start if t_next < 0, else x_start * sqrt(alpha_next) + c * pred_noise + sigma * z, with z = sample_noise (state
         channels shared over the boundary copies of a design, boundary channels per image).  x_T is sample_noise too.
         The whole loop is one library call (``cindm_ddpm2d_sample_ddim``: one captured HIP graph step replayed per DDIM step).
+        Guided: ``design_fn`` = a ``ForceObjective`` with ``design_guidance="standard-alpha"`` subtracts, at every step (the last
+        pair included), ``ddim_guidance_weights()[i] * design_fn(x_t)`` -- the gradient at the step's INPUT state, as p_sample's
+        "standard-alpha" branch takes it -- from that update; x_T and z are the unguided chain's.  One library call too
+        (``cindm_ddpm2d_sample_ddim_force``); ``fused=False`` runs the same definition step by step from Python.
         Build-only keywords: ``noise`` = a NoiseTape2D whose ``step_*`` rows are indexed by the DDIM STEP index; otherwise x_T
         and z come from the library's counter-based generator keyed by (seed, sample_offset + design); ``init_img`` +
         ``step_range=(i0, i1)`` run DDIM steps i0 .. i1-1 from a given state (teacher-forced segments for parity tests: the
         deterministic sampler amplifies a 1e-6 difference of the U-Net to 1e-3 over long chains).
-        Refused (NotImplementedError): ``design_fn`` (the reference has no working guided 2-D DDIM), share_noise False and
-        ``return_all_timesteps``."""
-        if design_fn is not None:
-            raise NotImplementedError("DDIM with design_fn: the reference has no working guided 2-D DDIM (its ddim_sample takes no "
-                                      "design_fn); sample with sampling_timesteps == timesteps for guidance")
+        Refused (NotImplementedError): any other ``design_fn`` or guidance (the reference has no working guided 2-D DDIM),
+        share_noise False and ``return_all_timesteps``."""
+        from .forceunet import ForceObjective
+        if design_fn is not None and not (isinstance(design_fn, ForceObjective) and design_guidance == "standard-alpha"):
+            raise NotImplementedError("DDIM with design_fn: only a ForceObjective under design_guidance='standard-alpha' has a DDIM form "
+                                      "(the reference has no working guided 2-D DDIM; its ddim_sample takes no design_fn); sample with "
+                                      "sampling_timesteps == timesteps for any other design_fn or guidance")
         if not self.share_noise:
             raise NotImplementedError("DDIM with share_noise=False: the reference's 2-D DDIM shares the predicted noise "
                                       "(model_predictions share_noise=True); there is no DDIM form of the shared posterior mean")
@@ -399,23 +415,36 @@ class GaussianDiffusion(nn.Module):
         device = device or self.betas.device
         if device.type != "cuda":
             raise _ffi.CindmError("sampling needs a ROCm device; there is no CPU execution path")
+        fo = design_fn
+        if fo is not None and ((fo.B, fo.nb) != (B, nb) or Cc != 3 * fo.frames + 3):
+            raise ValueError("ForceObjective was built for another batch / boundary / frame count")
         cp = self.model.padded_channels
         L = _ffi.lib()
         times, coefs = self.ddim_schedule()
         i0, i1 = (0, len(times) - 1) if step_range is None else step_range
         if not 0 <= i0 < i1 <= len(times) - 1:
             raise ValueError(f"step_range must satisfy 0 <= i0 < i1 <= {len(times) - 1}")
-        times, coefs = times[i0:i1 + 1], coefs[i0:i1].contiguous()
-        S = len(times) - 1
-        if init_img is not None:
-            x = to_device_layout(init_img.reshape(B * nb, Cc, H, W).to(device, torch.float32), cp)
-        else:
-            x = self._x_T(shape, noise, seed, sample_offset, device)
         if noise is not None:
             if (noise.step_state.shape[0] < i1 or noise.step_boundary.shape[0] < i1 or tuple(noise.step_state.shape[1:]) != (B, 1, Cc - 3, H, W)
                     or tuple(noise.step_boundary.shape[1:]) != (B, nb, 3, H, W)):
                 raise ValueError(f"the noise tape needs step_state [>= {i1}, {B}, 1, {Cc - 3}, {H}, {W}] and step_boundary "
                                  f"[>= {i1}, {B}, {nb}, 3, {H}, {W}] (rows indexed by the DDIM step)")
+        if init_img is not None:
+            x = to_device_layout(init_img.reshape(B * nb, Cc, H, W).to(device, torch.float32), cp)
+        else:
+            x = self._x_T(shape, noise, seed, sample_offset, device)
+        if fo is not None and not fused:
+            # the same definition from existing calls: the objective, one unguided DDIM step, the shift in torch
+            w = self.ddim_guidance_weights()
+            img = from_device_layout(x, Cc, H, W)
+            for i in range(i0, i1):
+                g = fo(img)
+                img = self.ddim_sample(shape, noise=noise, seed=seed, sample_offset=sample_offset, use_graph=use_graph, init_img=img,
+                                       step_range=(i, i + 1), device=device).reshape(B * nb, Cc, H, W)
+                img = img - w[i] * g
+            return img.reshape(B, nb, Cc, H, W)
+        times, coefs = times[i0:i1 + 1], coefs[i0:i1].contiguous()
+        S = len(times) - 1
         ns, nbnd = self._tape_cl(noise, device, slice(i0, i1))
         h, ws = self._prepare(B * nb, device)
         # the per-step device tables live in a caller tensor (the library allocates nothing): [S][4] coefficients + [S] time_next
@@ -423,6 +452,22 @@ class GaussianDiffusion(nn.Module):
             self._ddim_tab = torch.empty(5 * max(S, self.sampling_timesteps), dtype=torch.float32, device=device)
         tab = self._ddim_tab
         tarr = (C.c_int32 * (S + 1))(*times)
+        if fo is not None:
+            # the library's own objective: surrogate gradient, U-Net and the update that carries the shift are ONE captured graph
+            # per DDIM step (cindm_ddpm2d_sample_ddim_force); the weights ride in the 4th word of the table rows
+            fo.model.sync_weights()
+            w = self.ddim_guidance_weights()[i0:i1].contiguous()
+            nfb = L.cindm_airfoil_design_workspace_bytes(fo.model._h, B, nb, fo.frames_per_pass)
+            wsf = torch.empty(nfb, dtype=torch.uint8, device=device)
+            g = torch.empty_like(x)
+            with torch.cuda.device(device):
+                _ffi.check(L.cindm_ddpm2d_sample_ddim_force(h, self.model._h, fo.model._h, _ffi.ptr(x), B, nb, self._share_mode(), S, tarr,
+                                                            _ffi.ptr(coefs), _ffi.ptr(w), _ffi.ptr(tab), tab.numel() * 4, _ffi.ptr(ns),
+                                                            _ffi.ptr(nbnd), seed, sample_offset, fo.frames, fo.p_min, fo.p_max,
+                                                            fo.lambda_force, fo.lambda_overlap, fo.factor, int(fo.sum_boundary), _ffi.ptr(g),
+                                                            _ffi.ptr(ws), ws.numel(), _ffi.ptr(wsf), wsf.numel(),
+                                                            _ffi.current_stream(device), int(use_graph)))
+            return from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W)
         with torch.cuda.device(device):
             _ffi.check(L.cindm_ddpm2d_sample_ddim(h, self.model._h, _ffi.ptr(x), B, nb, self._share_mode(), S, tarr, _ffi.ptr(coefs),
                                                   _ffi.ptr(tab), tab.numel() * 4, _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset,

@@ -599,6 +599,25 @@ int  cindm_ddpm2d_sample_force(cindm_ddpm1d* sched, cindm_unet2d* u, cindm_force
                                float lambda_force, float lambda_overlap, int32_t down_factor, int32_t sum_boundary,
                                const float* eta, float* grad, void* ws, size_t ws_bytes, void* ws_force,
                                size_t ws_force_bytes, void* stream, int32_t use_graph);
+/* Guided DDIM of the 2-D path with the airfoil objective inside the captured step (GaussianDiffusion.ddim_sample with
+ * design_fn = ForceObjective, design_guidance = "standard-alpha"; the reference has no working 2-D DDIM, INTEGRATION.md defines it):
+ * per DDIM step i, pair (t, t_next) = (times[i], times[i+1]),
+ *   g = cindm_airfoil_design_grad(x_t);  x' = the update of cindm_ddpm2d_sample_ddim (same model_predictions, same draws);
+ *   x_next = x' - weights[i] * g      (on the last pair, t_next = -1, too -- as p_sample shifts at t = 0)
+ * with the update and the shift ONE element-wise launch.  weights [n_steps] is a HOST array like coefs (the caller sums
+ * coeff_ratio * betas.flip(0) over the DDPM steps t_next+1 .. t that the DDIM step skips); it is copied into the 4th word of the
+ * step's row of tab.  times / coefs / tab / noise_*_steps / use_average_share as cindm_ddpm2d_sample_ddim; frames .. sum_boundary,
+ * grad (a device buffer shaped like x) and ws_force as cindm_ddpm2d_sample_force; ws as cindm_ddpm2d_step (its last slice keeps
+ * x_T: nothing is allocated).  One hipGraph per call (surrogate gradient, U-Net, guided update, step counter), replayed n_steps
+ * times.  SYNCHRONISES `stream` before it returns and re-runs a chain whose surrogate exchange timed out ONCE from x_T on the
+ * exchange-free derivative, as cindm_ddpm2d_sample_force.  Every argument check precedes the first launch or copy. */
+int  cindm_ddpm2d_sample_ddim_force(cindm_ddpm1d* sched, cindm_unet2d* u, cindm_forceunet* f, float* x, int64_t B, int32_t nb,
+                                    int32_t use_average_share, int32_t n_steps, const int32_t* times, const float* coefs,
+                                    const float* weights, void* tab, size_t tab_bytes, const float* noise_state_steps,
+                                    const float* noise_boundary_steps, uint64_t seed, int64_t sample_offset,
+                                    int32_t frames, float p_min, float p_max, float lambda_force, float lambda_overlap,
+                                    int32_t down_factor, int32_t sum_boundary, float* grad, void* ws, size_t ws_bytes,
+                                    void* ws_force, size_t ws_force_bytes, void* stream, int32_t use_graph);
 
 /* ------------------------------------------------------------------ multi-GPU: the one collective of the path
  * the design batch is sharded over the ranks with no communication inside the reverse loop;
