@@ -183,6 +183,7 @@ static const OptDef kUnet1dOpts[] = {
     {"level1", 1, "CINDM_LEVEL1", OPT_PACK},     // level1_down_kernel: samples per workgroup (0 = off, 1, 2)
     {"ups_last", 1, "CINDM_UPS_LAST", OPT_PACK},
     {"ups_tail", 1, "CINDM_UPS_TAIL", OPT_PACK},
+    {"level_pairs", 1, "CINDM_LEVEL_PAIRS", OPT_PACK},   // up to 320 rows: level0_down + level1_down and ups_tail128 + ups_last as one launch each (level01_down_kernel, ups_tail_last_kernel)
     {"attn_head", 1, "CINDM_ATTN_HEAD", OPT_PACK},   // deep attention sites with the heads split over workgroups (attn1d_head_kernel)
     {"dconv", 1, "CINDM_DCONV", OPT_PACK},       // deep-level k=5 convolutions on dconv_kernel (LDS-resident activation planes)
     {"ws_alias", 1, "CINDM_WS_ALIAS", OPT_PACK}, // sampling path (taps = 0): dead intermediates' workspace blocks are recycled: 0 never, 1 above 320 rows, 2 always
@@ -1356,6 +1357,23 @@ static int emit_forward(Emitter& E, const float* x, float* eps) {
     auto move_to = [&](const Ten& next, bool next_is_skip = false) { if (!cur_is_skip) E.drop(cur); cur = next; cur_is_skip = next_is_skip; };
     // LayerNorm row partials from the producer are only needed where the attention site is not one fused launch
     auto need_ln = [&](const std::string& ap, int L) { return att && !(h->packed.count(ap + ".fn.fn.to_qkv#site") && L <= 32); };
+    // Level pairs (option "level_pairs"): the two launch boundaries of the step with ONE sample per workgroup on both sides -- level0_down ->
+    // level1_down and ups_tail128 -> ups_last -- are fused when BOTH stand-alone kernels would run and a workgroup has a CU to itself (at most
+    // 320 rows; above, level0 / level1 run two workgroups per CU and the pair's LDS would not allow that).  The first stage's branch fills its
+    // arguments and leaves them pending; the second stage's branch launches the pair.  Decided here and nowhere else: the launch count of a
+    // forward changes by the same amount whatever the step driver does around it.
+    const bool pairs = h->O("level_pairs") != 0 && E.rows <= 320;
+    auto level1_serves = [&](int L, int C, int ld) {
+        return h->O("level1") && h->level1_ok && att && L <= 16 && (L & 1) == 0 && C == 64 && ld == 64 &&
+               h->packed.count("downs.1.2.fn.fn.to_qkv#site") && h->packed.at("downs.1.2.fn.fn.to_qkv#site").h3;
+    };
+    auto ups_last_serves = [&](int ind, int L, int C, int ld, const Ten& skip) {
+        const std::string p = "ups." + std::to_string(ind);
+        return h->O("ups_last") && ind == nres - 2 && h->ups_last_ok && att && L <= 16 && C == 128 && ld == 128 && skip.C == 128 && skip.ld == 128 &&
+               h->packed.count(p + ".2.fn.fn.to_qkv#site") && h->packed.at(p + ".2.fn.fn.to_qkv#site").h3 && h->packed.count(p + ".3.conv");
+    };
+    bool pend01 = false, pend_ul = false;
+    Level01Args a01; UpsTailLastArgs aul;
     for (int ind = 0; ind < nres; ++ind) {
         const int co = h->dims[ind + 1];
         const std::string p = "downs." + std::to_string(ind);
@@ -1366,6 +1384,7 @@ static int emit_forward(Emitter& E, const float* x, float* eps) {
             Ten h1, h2;
             if (taps) { h1 = E.ten(L, 64); h2 = E.ten(L, 64); }
             Ten sk = E.ten(L, 64), dn = E.ten(L / 2, 64);
+            pend01 = pairs && nres > 1 && h->O("level1") == 1 && level1_serves(dn.L, dn.C, dn.ld);
             ++E.launches;
             Pf pfl;
             E.pf_all(pfl, {&h->packed.at("downs.0.0.blocks.0.block.0#lvl"), &h->packed.at("downs.0.0.blocks.1.block.0#lvl"),
@@ -1376,7 +1395,7 @@ static int emit_forward(Emitter& E, const float* x, float* eps) {
                 Level0Args l;
                 std::memset(&l, 0, sizeof(l));
                 l.pf = pfl;
-                l.x = cur.p; l.F = cur.C; l.h1 = taps ? h1.p : nullptr; l.h2 = taps ? h2.p : nullptr; l.skip = sk.p; l.down = dn.p;
+                l.x = cur.p; l.F = cur.C; l.h1 = taps ? h1.p : nullptr; l.h2 = taps ? h2.p : nullptr; l.skip = sk.p; l.down = (pend01 && !taps) ? nullptr : dn.p;
                 l.gB = h->gatherB; l.gcs = h->gather_cs; l.gLtot = h->gather_Ltot;
                 const char* cv[4] = {"downs.0.0.blocks.0", "downs.0.0.blocks.1", "downs.0.1.blocks.0", "downs.0.1.blocks.1"};
                 for (int i = 0; i < 4; ++i) {
@@ -1391,6 +1410,8 @@ static int emit_forward(Emitter& E, const float* x, float* eps) {
                 l.Wd = E.W(h->packed.at("downs.0.3.conv#lvl")); l.bd = E.B(h->packed.at("downs.0.3.conv"));
                 l.t_ptr = E.t_ptr; l.t_imm = E.t_imm; l.L = L;
                 l.ph = E.ph_next("level0_down downs.0");
+                if (pend01) a01.l0 = l;
+                else {
                 E.prof_begin(5, 0.0);
                 for (int rep = 0; rep < (E.prof ? Emitter::prof_reps : 1); ++rep) {
                     if (L > 16 && E.rows > 320) KLAUNCH(E, (level0_down_kernel<2, 2>), dim3((unsigned)E.rows), dim3(256), 0, l);
@@ -1398,6 +1419,7 @@ static int emit_forward(Emitter& E, const float* x, float* eps) {
                     else KLAUNCH(E, level0_down_kernel<1>, dim3((unsigned)E.rows), dim3(256), 0, l);
                 }
                 E.prof_end();
+                }
             }
             if (taps) { E.tap("downs.0.0", h1); E.tap("downs.0.1", h2); }
             E.tap("downs.0.2", sk); E.tap("downs.0.3", dn);
@@ -1406,13 +1428,12 @@ static int emit_forward(Emitter& E, const float* x, float* eps) {
             continue;
         }
         const int lvl1 = h->O("level1");      // samples per workgroup: 1 (default) or 2; 0 = off
-        if (ind == 1 && lvl1 && h->level1_ok && att && cur.L <= 16 && (cur.L & 1) == 0 && cur.C == 64 && cur.ld == 64 &&
-            h->packed.count("downs.1.2.fn.fn.to_qkv#site") && h->packed.at("downs.1.2.fn.fn.to_qkv#site").h3) {
+        if (ind == 1 && level1_serves(cur.L, cur.C, cur.ld)) {
             const int L = cur.L;
             Ten h1, h2;
             if (taps) { h1 = E.ten(L, 128); h2 = E.ten(L, 128); }
             Ten sk = E.ten(L, 128), dn = E.ten(L / 2, 128);
-            ++E.launches;
+            if (!pend01) ++E.launches;                  // (the pair is the launch counted by its first stage)
             Pf pfl;
             E.pf_all(pfl, {&h->packed.at("downs.1.0.blocks.0.block.0#lvl"), &h->packed.at("downs.1.0.blocks.1.block.0#lvl"),
                            &h->packed.at("downs.1.1.blocks.0.block.0#lvl"), &h->packed.at("downs.1.1.blocks.1.block.0#lvl"),
@@ -1441,12 +1462,18 @@ static int emit_forward(Emitter& E, const float* x, float* eps) {
                 const dim3 grid((unsigned)((E.rows + S - 1) / S));
                 E.prof_begin(5, 0.0);
                 for (int rep = 0; rep < (E.prof ? Emitter::prof_reps : 1); ++rep) {
-                    if (S == 1 && E.rows > 320) KLAUNCH(E, (level1_down_kernel<1, 2>), grid, dim3(256), 0, l);
+                    if (pend01) {
+                        a01.l1 = l;
+                        if (a01.l0.L > 16) KLAUNCH(E, level01_down_kernel<2>, grid, dim3(256), 0, a01);
+                        else KLAUNCH(E, level01_down_kernel<1>, grid, dim3(256), 0, a01);
+                    }
+                    else if (S == 1 && E.rows > 320) KLAUNCH(E, (level1_down_kernel<1, 2>), grid, dim3(256), 0, l);
                     else if (S == 1) KLAUNCH(E, level1_down_kernel<1>, grid, dim3(256), 0, l);
                     else KLAUNCH(E, level1_down_kernel<2>, grid, dim3(256), 0, l);
                 }
                 E.prof_end();
             }
+            pend01 = false;
             if (taps) { E.tap("downs.1.0", h1); E.tap("downs.1.1", h2); }
             E.tap("downs.1.2", sk); E.tap("downs.1.3", dn);
             skips.push_back(sk);
@@ -1470,13 +1497,12 @@ static int emit_forward(Emitter& E, const float* x, float* eps) {
         Ten skip = skips.back(); skips.pop_back();
         const int upl = h->O("ups_last");
         if (getenv("CINDM_VERBOSE") && E.dry) fprintf(stderr, "[cindm] ups ind %d nres %d ok %d att %d L %d C %d ld %d sC %d sld %d\n", ind, nres, (int)h->ups_last_ok, (int)att, cur.L, cur.C, cur.ld, skip.C, skip.ld);
-        if (upl && ind == nres - 2 && h->ups_last_ok && att && cur.L <= 16 && cur.C == 128 && cur.ld == 128 && skip.C == 128 && skip.ld == 128 &&
-            h->packed.count(p + ".2.fn.fn.to_qkv#site") && h->packed.at(p + ".2.fn.fn.to_qkv#site").h3 && h->packed.count(p + ".3.conv")) {
+        if (upl && ups_last_serves(ind, cur.L, cur.C, cur.ld, skip)) {
             // the level and the output head in one launch (ups_last_kernel)
             const int L = cur.L;
             Ten h1, h2, h3, up, ypre;
             if (taps) { h1 = E.ten(L, 128); h2 = E.ten(L, 64); h3 = E.ten(L, 64); up = E.ten(2 * L, 64); ypre = E.ten(2 * L, 64); }
-            ++E.launches;
+            if (!pend_ul) ++E.launches;                 // (the pair is the launch counted by its first stage)
             Pf pfl;
             E.pf_all(pfl, {&h->packed.at(p + ".0.blocks.0.block.0#lvl"), &h->packed.at(p + ".0.blocks.1.block.0#lvl"), &h->packed.at(p + ".0.residual_conv#lvl"),
                            &h->packed.at(p + ".1.blocks.0.block.0#lvl"), &h->packed.at(p + ".1.blocks.1.block.0#lvl"), &h->packed.at(p + ".1.residual_conv#lvl"),
@@ -1504,8 +1530,10 @@ static int emit_forward(Emitter& E, const float* x, float* eps) {
                 l.t_ptr = E.t_ptr; l.t_imm = E.t_imm; l.L = L;
                 l.ph = E.ph_next("ups_last " + p + " + final_conv");
                 E.prof_begin(5, 0.0);
-                for (int rep = 0; rep < (E.prof ? Emitter::prof_reps : 1); ++rep)
-                    KLAUNCH(E, ups_last_kernel, dim3((unsigned)E.rows), dim3(256), 0, l);
+                for (int rep = 0; rep < (E.prof ? Emitter::prof_reps : 1); ++rep) {
+                    if (pend_ul) { aul.l1 = l; KLAUNCH(E, ups_tail_last_kernel, dim3((unsigned)E.rows), dim3(256), 0, aul); }
+                    else KLAUNCH(E, ups_last_kernel, dim3((unsigned)E.rows), dim3(256), 0, l);
+                }
                 E.prof_end();
             }
             if (taps) { E.tap(p + ".0", h1); E.tap(p + ".1", h2); E.tap(p + ".2", h3); E.tap(p + ".3", up); E.tap("final_conv.0.pre", ypre); }
@@ -1521,6 +1549,7 @@ static int emit_forward(Emitter& E, const float* x, float* eps) {
             Ten h2, h3;
             if (taps) { h2 = E.ten(L, 128); h3 = E.ten(L, 128); }
             Ten up = E.ten(2 * L, 128);
+            pend_ul = pairs && !skips.empty() && ups_last_serves(ind + 1, up.L, up.C, up.ld, skips.back());
             ++E.launches;
             Pf pfl;
             E.pf_all(pfl, {&h->packed.at(p + ".1.blocks.0.block.0#lvl"), &h->packed.at(p + ".1.blocks.1.block.0#lvl"),
@@ -1530,7 +1559,7 @@ static int emit_forward(Emitter& E, const float* x, float* eps) {
                 UpsTailArgs l;
                 std::memset(&l, 0, sizeof(l));
                 l.pf = pfl;
-                l.x = cur.p; l.h2 = taps ? h2.p : nullptr; l.h3 = taps ? h3.p : nullptr; l.up = up.p;
+                l.x = cur.p; l.h2 = taps ? h2.p : nullptr; l.h3 = taps ? h3.p : nullptr; l.up = (pend_ul && !taps) ? nullptr : up.p;
                 const std::string cv[2] = {p + ".1.blocks.0", p + ".1.blocks.1"};
                 for (int i = 0; i < 2; ++i) {
                     l.Wc[i] = E.W(h->packed.at(cv[i] + ".block.0#lvl")); l.bc[i] = E.B(h->packed.at(cv[i] + ".block.0"));
@@ -1543,10 +1572,13 @@ static int emit_forward(Emitter& E, const float* x, float* eps) {
                 l.Wu = E.W(h->packed.at(p + ".3.conv#lvl")); l.bu = E.B(h->packed.at(p + ".3.conv"));
                 l.t_ptr = E.t_ptr; l.t_imm = E.t_imm; l.L = L;
                 l.ph = E.ph_next("ups_tail128 " + p);
-                E.prof_begin(5, 0.0);
-                for (int rep = 0; rep < (E.prof ? Emitter::prof_reps : 1); ++rep)
-                    KLAUNCH(E, ups_tail128_kernel, dim3((unsigned)E.rows), dim3(256), 0, l);
-                E.prof_end();
+                if (pend_ul) aul.l0 = l;
+                else {
+                    E.prof_begin(5, 0.0);
+                    for (int rep = 0; rep < (E.prof ? Emitter::prof_reps : 1); ++rep)
+                        KLAUNCH(E, ups_tail128_kernel, dim3((unsigned)E.rows), dim3(256), 0, l);
+                    E.prof_end();
+                }
             }
             if (taps) { E.tap(p + ".1", h2); E.tap(p + ".2", h3); }
             E.tap(p + ".3", up);

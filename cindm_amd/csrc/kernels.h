@@ -123,6 +123,11 @@ struct PhaseBuf { unsigned long long* buf; int slot; };
 #ifdef CINDM_PHASE_PROF
 #define PH_DECL unsigned long long ph_[cindm::PH_NST] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull}
 #define PH(i) do { __builtin_amdgcn_sched_barrier(0); ph_[i] = wall_clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
+// a kernel body that is a __device__ stage function (the level pairs below) takes the caller's stamps: PH_PARAM in its parameter list,
+// PH_ARG at the call; PH_RESET clears them between the two stages of a fused launch (one record slot per stage)
+#define PH_PARAM , unsigned long long (&ph_)[cindm::PH_NST]
+#define PH_ARG , ph_
+#define PH_RESET do { _Pragma("unroll") for (int i_ = 0; i_ < cindm::PH_NST; ++i_) ph_[i_] = 0ull; } while (0)
 #define PH_FLUSH(pb) do { \
         if ((pb).buf && (threadIdx.x & 63) == 0) { \
             const unsigned wg_ = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x; \
@@ -135,6 +140,9 @@ struct PhaseBuf { unsigned long long* buf; int slot; };
 #else
 #define PH_DECL do { } while (0)
 #define PH(i) do { } while (0)
+#define PH_PARAM
+#define PH_ARG
+#define PH_RESET do { } while (0)
 #define PH_FLUSH(pb) do { } while (0)
 #endif
 
@@ -1751,10 +1759,25 @@ __device__ __forceinline__ void lvl_store(const f32x4 (&v)[NT], float* dst, int 
     }
 }
 
-// MINB = 2 (more rows than CUs: configs 3 / 4): registers capped at 256 so that two workgroups share a CU (52 KB of LDS each)
-template <int NT, int MINB = 1>
-__global__ __launch_bounds__(256, MINB) void level0_down_kernel(const Level0Args a) {
-    PH_DECL;
+// The argument struct of the running kernel (its ONLY parameter), read in place in the kernarg segment.  A kernel whose body is a stage
+// function hands the struct on by reference; done with the parameter object itself, the compiler copies it to a private object first and,
+// when it takes that copy apart again, loads EVERY member at the top of the kernel -- ~100 scalar registers live from the first
+// instruction on (level1_down_kernel<1, 2>: 51 -> 63 spilled registers).  Through this reference the members are scalar loads where they are used,
+// as they are in a kernel that names its parameter directly.
+template <typename T>
+__device__ __forceinline__ const T& kernarg() { return *reinterpret_cast<const T*>((const void*)__builtin_amdgcn_kernarg_segment_ptr()); }
+
+// The body of level0_down_kernel as a stage function: the stand-alone kernel (FUSED = false) and level01_down_kernel (FUSED = true,
+// followed by level1_down_stage for the same sample) run the same code.  What FUSED adds is what the NEXT stage can already know while
+// this one runs: its LDS zero fill goes where this stage waits for its first loads, its first weight fragments and parameter vectors
+// (`hd`) are requested in front of this stage's last two phases, and the Downsample1d tile is handed over in registers (`dout`) --
+// it goes to memory only when a.down is set (taps).
+struct Level1Args;
+struct Level1Head;
+template <int NT> __device__ __forceinline__ void level1_zero_fill(int tid);
+__device__ __forceinline__ void level1_request(const Level1Args& a1, int t_now, int tid, int lane, int w, Level1Head& hd);
+template <int NT, bool FUSED>
+__device__ __forceinline__ void level0_down_stage(const Level0Args& a, const int t_in, const Level1Args* a1, Level1Head* hd, f32x4* dout PH_PARAM) {
     PH(0);        // phase clocks (profiling builds, kernels.h PhaseBuf): mark k follows the k-th workgroup barrier, the last one the final stores
     constexpr int C = 64, NP = NT * 16, ROWS = NP + 4;               // two halo positions on each side
     constexpr int XPB = 2 * 32 + 16, PPB = 2 * C + 16, APB = 2 * 128 + 16, HP = C + 4;
@@ -1764,7 +1787,7 @@ __global__ __launch_bounds__(256, MINB) void level0_down_kernel(const Level0Args
     __shared__ __attribute__((aligned(16))) float H[NP * HP];                          // h2 in fp32 for the LayerNorm
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
     const int L = a.L, b = blockIdx.x;
-    const int t_now = step_scalar(a.t_ptr, a.t_imm);
+    const int t_now = FUSED ? t_in : step_scalar(a.t_ptr, a.t_imm);      // (the pair reads t once, at the top of the launch)
     const int c0 = w * 16;                                               // this wave's channels
     PfRegs pfr;
     l2_prefetch_early(a.pf, pfr);
@@ -1792,6 +1815,7 @@ __global__ __launch_bounds__(256, MINB) void level0_down_kernel(const Level0Args
     for (int i = 0; i < 4; ++i) { pbc[i] = ld4(a.bc[i]); pga[i] = ld4(a.gam[i]); pbe[i] = ld4(a.bet[i]); }
     const float4 pbr = ld4(a.br), pbo = ld4(a.bo), pbd = ld4(a.bd);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (FUSED) level1_zero_fill<1>(tid);                       // the next stage's planes, while this one's first loads are on their way
     // ---- stage x (zero halo, zero pad channels / positions); clear the halos of the activation planes ----
     {
         const int r = xr, c4 = xc4;
@@ -1947,6 +1971,7 @@ __global__ __launch_bounds__(256, MINB) void level0_down_kernel(const Level0Args
     float4 wo4[4][2], wd6[6][2];                             // out projection and Downsample1d fragments: in flight during the core
     lvl_wload<4>(reinterpret_cast<const float4*>(a.Wo) + (size_t)w * (4 * 2 * 64), lane, wo4);
     lvl_wload<6>(Wd4, lane, wd6);
+    if constexpr (FUSED) level1_request(*a1, t_now, tid, lane, w, *hd);      // the next stage's head: in flight through the core, the out projection and the Downsample1d
     l2_prefetch_late(a.pf, pfr);                         // (behind the kernel's LAST load request: vector loads return in order, nothing younger can queue behind the touches)
     f32x4 att[2][NT];
     attn_site_core<NT>(qa, ka, va, att, 1, NP, NP, L, lq, lr);
@@ -1983,11 +2008,19 @@ __global__ __launch_bounds__(256, MINB) void level0_down_kernel(const Level0Args
         lvl_conv<1, 3, 2, PPB>(wd6, P[0][0], P[0][1], 2, 1, ROWS - 1, lane, d);
         const float4 bd = pbd;
         d[0][0] += bd.x; d[0][1] += bd.y; d[0][2] += bd.z; d[0][3] += bd.w;
-        lvl_store<1>(d, a.down + (size_t)b * (L / 2) * C, c0, L / 2, lane, a.pf.wt);
+        if (!FUSED || a.down) lvl_store<1>(d, a.down + (size_t)b * (L / 2) * C, c0, L / 2, lane, a.pf.wt);
+        if constexpr (FUSED) *dout = d[0];
     }
     PH(9);
     l2_prefetch_done(a.pf, pfr);
     PH_FLUSH(a.ph);
+}
+
+// MINB = 2 (more rows than CUs: configs 3 / 4): registers capped at 256 so that two workgroups share a CU (52 KB of LDS each)
+template <int NT, int MINB = 1>
+__global__ __launch_bounds__(256, MINB) void level0_down_kernel(const Level0Args) {
+    PH_DECL;
+    level0_down_stage<NT, false>(kernarg<Level0Args>(), 0, nullptr, nullptr, nullptr PH_ARG);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2100,34 +2133,85 @@ __device__ __forceinline__ void lvlm_gn_mish(f32x4& v, const float4 bias, const 
     for (int i = 0; i < 4; ++i) v[i] = mish_f((v[i] - mean) * rstd * gg[i] + be[i]);
 }
 
-template <int NT, int MINB = 1>
-__global__ __launch_bounds__(256, MINB) void level1_down_kernel(const Level1Args a) {
-    PH_DECL;
-    PH(0);        // phase clocks (profiling builds, kernels.h PhaseBuf): mark k follows the k-th workgroup barrier, the last one the final stores
-    constexpr int C = 128, CI = 64, RS = 20, ROWS = NT * RS, NP = NT * 16;
-    constexpr int XPB = 2 * CI + 16, PPB = 2 * C + 16, APB = 2 * 128 + 16, HP = C + 4;
-    constexpr int RBYTES = (2 * ROWS * XPB > 2 * NP * APB) ? 2 * ROWS * XPB : 2 * NP * APB;
+// level1_down_kernel's LDS arrays (one set per NT and kernel), its head requests and its zero fill as functions of their own: the fused
+// pair (level01_down_kernel) runs the last two inside the PREVIOUS stage
+template <int NT> struct Level1Lds {
+    static constexpr int C = 128, CI = 64, RS = 20, ROWS = NT * RS, NP = NT * 16;
+    static constexpr int XPB = 2 * CI + 16, PPB = 2 * C + 16, APB = 2 * 128 + 16, HP = C + 4;
+    static constexpr int RBYTES = (2 * ROWS * XPB > 2 * NP * APB) ? 2 * ROWS * XPB : 2 * NP * APB;
     static_assert(NP * HP * 4 <= RBYTES, "H fits the shared region");
-    __shared__ __attribute__((aligned(16))) unsigned char P[2][2][ROWS * PPB];        // ping-pong activation planes
-    __shared__ __attribute__((aligned(16))) unsigned char R[RBYTES];                  // x planes, then h2 (fp32), then att planes
+    unsigned char* P;         // [2][2][ROWS * PPB]  ping-pong activation planes
+    unsigned char* R;         // [RBYTES]            x planes, then h2 (fp32), then att planes
+    float* PV;                // [17][C]             parameter vectors
+};
+template <int NT>
+__device__ __forceinline__ Level1Lds<NT> level1_lds() {
+    typedef Level1Lds<NT> T;
+    __shared__ __attribute__((aligned(16))) unsigned char P[2][2][T::ROWS * T::PPB];
+    __shared__ __attribute__((aligned(16))) unsigned char R[T::RBYTES];
+    __shared__ __attribute__((aligned(16))) float PV[17][T::C];
+    return T{&P[0][0][0], R, &PV[0][0]};
+}
+template <int NT>
+__device__ __forceinline__ void level1_zero_fill(int tid) {
+    typedef Level1Lds<NT> T;
+    const T s = level1_lds<NT>();
+    for (int i = tid; i < 2 * T::ROWS * T::XPB / 16; i += 256) reinterpret_cast<float4*>(s.R)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = tid; i < 4 * T::ROWS * T::PPB / 16; i += 256) reinterpret_cast<float4*>(s.P)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+struct Level1Head {
+    LvlRing<2, 4> ring;                                                  // convolution fragments
+    LvlRing<2, 2> ring_r;                                                // residual_conv fragments (one tap)
+    float pvr[17];                                                       // parameter vectors (threads < 128)
+};
+__device__ __forceinline__ void level1_request_rings(const Level1Args& a, int lane, int w, Level1Head& hd) {
+    const int t0 = 2 * w;
+    lvlm_prefetch<2, 5, 2, 4>(hd.ring, reinterpret_cast<const float4*>(a.Wc[0]) + (size_t)t0 * 5 * 2 * 2 * 64, lane);
+    lvlm_prefetch<2, 1, 2, 2>(hd.ring_r, reinterpret_cast<const float4*>(a.Wr) + (size_t)t0 * 1 * 2 * 2 * 64, lane);
+}
+__device__ __forceinline__ void level1_request_pv(const Level1Args& a, int t_now, int tid, Level1Head& hd) {
+    if (tid < 128) {
+        const float* src[17] = {a.bc[0], a.bc[1], a.bc[2], a.bc[3], a.gam[0], a.gam[1], a.gam[2], a.gam[3], a.bet[0], a.bet[1], a.bet[2], a.bet[3],
+                                a.tb0 + (size_t)t_now * a.tb_ld, a.tb1 + (size_t)t_now * a.tb_ld, a.br, a.bo, a.bd};
+#pragma unroll
+        for (int i = 0; i < 17; ++i) hd.pvr[i] = src[i][tid];
+    }
+}
+__device__ __forceinline__ void level1_request(const Level1Args& a1, int t_now, int tid, int lane, int w, Level1Head& hd) {
+    level1_request_rings(a1, lane, w, hd);
+    level1_request_pv(a1, t_now, tid, hd);
+}
+
+// The body of level1_down_kernel as a stage function.  FUSED (level01_down_kernel, NT = 1, the sample of the workgroup): the planes are
+// zero, `hd` is on its way and `din` is the previous stage's Downsample1d tile (rows = channels 16 w + 4 lq + i, column = position lr);
+// it goes to the x planes with the split the stand-alone kernel applies to the rows it reads back from memory.
+template <int NT, bool FUSED>
+__device__ __forceinline__ void level1_down_stage(const Level1Args& a, const int t_in, Level1Head& hd, const f32x4 din PH_PARAM) {
+    PH(0);        // phase clocks (profiling builds, kernels.h PhaseBuf): mark k follows the k-th workgroup barrier, the last one the final stores
+    typedef Level1Lds<NT> LDS;
+    constexpr int C = LDS::C, CI = LDS::CI, RS = LDS::RS, ROWS = LDS::ROWS, NP = LDS::NP;
+    constexpr int XPB = LDS::XPB, PPB = LDS::PPB, APB = LDS::APB, HP = LDS::HP;
+    const LDS lds = level1_lds<NT>();
+    unsigned char (*P)[2][ROWS * PPB] = reinterpret_cast<unsigned char (*)[2][ROWS * PPB]>(lds.P);
+    unsigned char* R = lds.R;
+    float (*PV)[C] = reinterpret_cast<float (*)[C]>(lds.PV);
     unsigned char* X0h = R; unsigned char* X0l = R + ROWS * XPB;
     float* H = reinterpret_cast<float*>(R);
     unsigned char* Aph = R; unsigned char* Apl = R + NP * APB;
     // per-channel parameter vectors, fetched once: 0-3 conv bias, 4-7 GroupNorm weight, 8-11 GroupNorm bias, 12 / 13 time bias
     // of the two blocks (row t), 14 residual_conv bias, 15 to_out bias, 16 downsample bias
-    __shared__ __attribute__((aligned(16))) float PV[17][C];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
     const int L = a.L;
     const int s0 = blockIdx.x * NT, s_here = min(NT, a.Bp - s0);
-    const int t_now = step_scalar(a.t_ptr, a.t_imm);
+    const int t_now = FUSED ? t_in : step_scalar(a.t_ptr, a.t_imm);
     const int t0 = 2 * w;                                                // this wave's first 16-channel tile
     auto wbase = [&](const float* W, int taps, int ks) { return reinterpret_cast<const float4*>(W) + (size_t)t0 * taps * ks * 2 * 64; };
-    LvlRing<2, 4> ring;                                                  // convolution fragments
-    LvlRing<2, 2> ring_r;                                                // residual_conv fragments (one tap)
-    lvlm_prefetch<2, 5, 2, 4>(ring, wbase(a.Wc[0], 5, 2), lane);
-    lvlm_prefetch<2, 1, 2, 2>(ring_r, wbase(a.Wr, 1, 2), lane);
+    LvlRing<2, 4>& ring = hd.ring;
+    LvlRing<2, 2>& ring_r = hd.ring_r;
+    if constexpr (!FUSED) level1_request_rings(a, lane, w, hd);
     PfRegs pfr;
     l2_prefetch_early(a.pf, pfr);
+    if constexpr (!FUSED) {
     // (round 4) the input rows are requested BEFORE the parameter vectors go to LDS: `PV[i][tid] = src[i][tid]` waits for its loads,
     // and rows requested after that wait were a second serial round trip at the head of the launch
     float4 xin[NT];
@@ -2136,21 +2220,14 @@ __global__ __launch_bounds__(256, MINB) void level1_down_kernel(const Level1Args
         xin[nt] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (nt < s_here && (tid >> 4) < L) xin[nt] = *reinterpret_cast<const float4*>(a.x + ((size_t)(s0 + nt) * L + (tid >> 4)) * CI + 4 * (tid & 15));
     }
-    float pvr[17];                                                       // requested now, written to LDS after the zero fill
-    if (tid < C) {
-        const float* src[17] = {a.bc[0], a.bc[1], a.bc[2], a.bc[3], a.gam[0], a.gam[1], a.gam[2], a.gam[3], a.bet[0], a.bet[1], a.bet[2], a.bet[3],
-                                a.tb0 + (size_t)t_now * a.tb_ld, a.tb1 + (size_t)t_now * a.tb_ld, a.br, a.bo, a.bd};
-#pragma unroll
-        for (int i = 0; i < 17; ++i) pvr[i] = src[i][tid];
-    }
+    level1_request_pv(a, t_now, tid, hd);                                // requested now, written to LDS after the zero fill
     __builtin_amdgcn_sched_barrier(0);
     // ---- stage x: sample tile nt at rows nt*RS + 2 + position; everything else zero.  The rows are requested BEFORE the zero
     // fill and its barrier (after them, their round trip opened every launch) ----
-    for (int i = tid; i < 2 * ROWS * XPB / 16; i += 256) reinterpret_cast<float4*>(R)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = tid; i < 4 * ROWS * PPB / 16; i += 256) reinterpret_cast<float4*>(&P[0][0][0])[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    level1_zero_fill<NT>(tid);
     if (tid < C) {
 #pragma unroll
-        for (int i = 0; i < 17; ++i) PV[i][tid] = pvr[i];
+        for (int i = 0; i < 17; ++i) PV[i][tid] = hd.pvr[i];
     }
     __syncthreads();
     PH(1);
@@ -2168,6 +2245,21 @@ __global__ __launch_bounds__(256, MINB) void level1_down_kernel(const Level1Args
                 *reinterpret_cast<half4v*>(X0h + (nt * RS + 2 + p) * XPB + 8 * c4) = hi;
                 *reinterpret_cast<half4v*>(X0l + (nt * RS + 2 + p) * XPB + 8 * c4) = lo;
             }
+        }
+    }
+    } else {
+        static_assert(!FUSED || NT == 1, "the fused pair is one sample per workgroup");
+        if (lr < L) {
+            half4v hi, lo;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { hi[i] = (_Float16)din[i]; lo[i] = (_Float16)((din[i] - (float)hi[i]) * H3_SCALE); }
+            const int off = (2 + lr) * XPB + 2 * (w * 16 + lq * 4);
+            *reinterpret_cast<half4v*>(X0h + off) = hi;
+            *reinterpret_cast<half4v*>(X0l + off) = lo;
+        }
+        if (tid < C) {
+#pragma unroll
+            for (int i = 0; i < 17; ++i) PV[i][tid] = hd.pvr[i];
         }
     }
     auto cl = [&](int mt) { return (t0 + mt) * 16 + lq * 4; };           // the lane's four channels of tile mt
@@ -2214,7 +2306,8 @@ __global__ __launch_bounds__(256, MINB) void level1_down_kernel(const Level1Args
             for (int nt = 0; nt < NT; ++nt) { v[mt][nt][0] += t.x; v[mt][nt][1] += t.y; v[mt][nt][2] += t.z; v[mt][nt][3] += t.w; }
         }
     };
-    __syncthreads();
+    __syncthreads();               // (FUSED: the ONE barrier between the two stages)
+    if constexpr (FUSED) PH(1);
     PH(2);
     if (a.dbg == 1) return;
 
@@ -2393,6 +2486,30 @@ __global__ __launch_bounds__(256, MINB) void level1_down_kernel(const Level1Args
     PH_FLUSH(a.ph);
 }
 
+template <int NT, int MINB = 1>
+__global__ __launch_bounds__(256, MINB) void level1_down_kernel(const Level1Args) {
+    PH_DECL;
+    Level1Head hd;
+    level1_down_stage<NT, false>(kernarg<Level1Args>(), 0, hd, f32x4{0.f, 0.f, 0.f, 0.f} PH_ARG);
+}
+
+// level01_down_kernel: level0_down_kernel<NT> and level1_down_kernel<1> of the sample blockIdx.x as ONE launch (at most 320 rows: one
+// workgroup per CU; the two stages' LDS arrays are disjoint, 92 KB together).  Both sides of that launch boundary are workgroup-local,
+// so nothing is handed between workgroups: the Downsample1d tile stays in registers and the second stage's zero fill, first weight
+// fragments and parameter vectors overlap the first stage instead of opening a launch of their own.  One phase-clock slot per stage.
+struct Level01Args { Level0Args l0; Level1Args l1; };
+template <int NT>
+__global__ __launch_bounds__(256) void level01_down_kernel(const Level01Args) {
+    PH_DECL;
+    const Level01Args& a = kernarg<Level01Args>();
+    const int t_now = step_scalar(a.l0.t_ptr, a.l0.t_imm);
+    Level1Head hd;
+    f32x4 d;
+    level0_down_stage<NT, true>(a.l0, t_now, &a.l1, &hd, &d PH_ARG);
+    PH_RESET;
+    level1_down_stage<1, true>(a.l1, t_now, hd, d PH_ARG);
+}
+
 // ---------------------------------------------------------------------------------------------
 // ups_last_kernel: the finest up level and the output head in one launch, one sample per workgroup:
 //   cat(x, skip) [L, 256] -> ResidualTemporalBlock(256 -> 128) -> ResidualTemporalBlock(128 -> 64) -> attention site(64)
@@ -2523,74 +2640,146 @@ struct UpsLastArgs {
     int fuse_upd; ComposeArgs upd;                       // plain single-model step: x_{t-1} from this kernel's eps rows, in place
 };
 
-// (Round 4 also compiled this kernel and ups_tail128_kernel for two workgroups per CU above 320 rows -- 89 / 60 spilled registers, config 3
-// 833 -> 841 / 838 us per step --: removed in round 6; level0_down / level1_down keep their two-workgroup instantiations.)
-__global__ __launch_bounds__(256) void ups_last_kernel(const UpsLastArgs a) {
-    PH_DECL;
-    PH(0);        // phase clocks (profiling builds, kernels.h PhaseBuf): mark k follows the k-th workgroup barrier, the last one the final stores
-    constexpr int C = 64, CB = 128, CI = 256, NP1 = 16, NP2 = 32, ROWS1 = NP1 + 4, ROWS2 = NP2 + 4;
-    constexpr int XPB = 2 * CI + 16, QPB = 2 * CB + 16, PPB = 2 * C + 16, APB = 2 * 128 + 16, HP = C + 4;
-    __shared__ __attribute__((aligned(16))) unsigned char XI[2][ROWS1 * XPB];
-    __shared__ __attribute__((aligned(16))) unsigned char Q[2][2][ROWS1 * QPB];         // 128-channel planes of the first block
-    __shared__ __attribute__((aligned(16))) unsigned char P[2][2][ROWS2 * PPB];         // 64-channel planes
-    __shared__ __attribute__((aligned(16))) unsigned char R[2 * NP1 * APB];            // h2 in fp32 for the LayerNorm, then the att planes
+// ups_last_kernel's LDS arrays, zero fill and head requests as functions of their own: the fused pair (ups_tail_last_kernel) runs the
+// last two inside the PREVIOUS stage
+struct UpsLastLds {
+    static constexpr int C = 64, CB = 128, CI = 256, NP1 = 16, NP2 = 32, ROWS1 = NP1 + 4, ROWS2 = NP2 + 4;
+    static constexpr int XPB = 2 * CI + 16, QPB = 2 * CB + 16, PPB = 2 * C + 16, APB = 2 * 128 + 16, HP = C + 4;
+    static_assert(NP1 * HP * 4 <= 2 * NP1 * APB, "H fits the shared region");
+    unsigned char* XI;        // [2][ROWS1 * XPB]
+    unsigned char* Q;         // [2][2][ROWS1 * QPB]   128-channel planes of the first block
+    unsigned char* P;         // [2][2][ROWS2 * PPB]   64-channel planes
+    unsigned char* R;         // [2 * NP1 * APB]       h2 in fp32 for the LayerNorm, then the att planes
+    float* PVB;               // [8][CB]
+    float* PV;                // [14][C]
+};
+__device__ __forceinline__ UpsLastLds ups_last_lds() {
+    typedef UpsLastLds T;
+    __shared__ __attribute__((aligned(16))) unsigned char XI[2][T::ROWS1 * T::XPB];
+    __shared__ __attribute__((aligned(16))) unsigned char Q[2][2][T::ROWS1 * T::QPB];
+    __shared__ __attribute__((aligned(16))) unsigned char P[2][2][T::ROWS2 * T::PPB];
+    __shared__ __attribute__((aligned(16))) unsigned char R[2 * T::NP1 * T::APB];
     // parameter vectors: 128-wide 0-2 conv1 (bias, GN weight, GN bias), 3-5 conv2, 6 time bias, 7 residual bias;
     // 64-wide 0-2 conv3, 3-5 conv4, 6-8 final conv, 9 time bias, 10 residual bias, 11 to_out, 12 upsample, 13 final 1x1
-    __shared__ __attribute__((aligned(16))) float PVB[8][CB];
-    __shared__ __attribute__((aligned(16))) float PV[14][C];
-    static_assert(NP1 * HP * 4 <= 2 * NP1 * APB, "H fits the shared region");
-    float* H = reinterpret_cast<float*>(R);
-    unsigned char* Aph = R; unsigned char* Apl = R + NP1 * APB;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
-    const int L = a.L, L2 = 2 * a.L, b = blockIdx.x;
-    const int t_now = step_scalar(a.t_ptr, a.t_imm);
-    const int c0 = w * 16, cl = c0 + lq * 4;
-    auto clb = [&](int mt) { return (2 * w + mt) * 16 + lq * 4; };       // the lane's channels in the 128-channel block
-    auto wbase = [&](const float* W, int taps, int ks) { return reinterpret_cast<const float4*>(W) + (size_t)w * taps * ks * 2 * 64; };
-    LvlRing<1, 8> ring, ring_r;                                          // weight rings (one 16-channel tile at a time)
-    LvlRing<1, 8, 2> ring8;                                              // ... of the 256-input-channel block: two taps deep (see LvlRing)
-    auto wtile = [&](const float* W, int tile, int taps, int ks) { return reinterpret_cast<const float4*>(W) + (size_t)tile * taps * ks * 2 * 64; };
-    lvlm_prefetch<1, 5, 8, 8>(ring8, wtile(a.Wc[0], 2 * w, 5, 8), lane);
-    lvlm_prefetch<1, 1, 8, 8>(ring_r, wtile(a.Wr0, 2 * w, 1, 8), lane);
-    PfRegs pfr;
-    l2_prefetch_early(a.pf, pfr);
-    // (round 4) the input rows are requested BEFORE the parameter vectors go to LDS: `PV[i][tid] = src[i][tid]` waits for its loads,
-    // and rows requested after that wait were a second serial round trip at the head of the launch
-    float4 xin[4];                                                       // cat(x, skip) rows, requested before the zero fill and its barrier
+    __shared__ __attribute__((aligned(16))) float PVB[8][T::CB];
+    __shared__ __attribute__((aligned(16))) float PV[14][T::C];
+    return T{&XI[0][0], &Q[0][0][0], &P[0][0][0], R, &PVB[0][0], &PV[0][0]};
+}
+__device__ __forceinline__ void ups_last_zero_fill(int tid) {
+    typedef UpsLastLds T;
+    const T s = ups_last_lds();
+    for (int i = tid; i < 2 * T::ROWS1 * T::XPB / 16; i += 256) reinterpret_cast<float4*>(s.XI)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = tid; i < 4 * T::ROWS1 * T::QPB / 16; i += 256) reinterpret_cast<float4*>(s.Q)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = tid; i < 4 * T::ROWS2 * T::PPB / 16; i += 256) reinterpret_cast<float4*>(s.P)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+struct UpsLastHead {
+    LvlRing<1, 8> ring_r;                                                // residual_conv fragments
+    LvlRing<1, 8, 2> ring8;                                              // the 256-input-channel block's: two taps deep (see LvlRing)
+    float4 xin[4];                                                       // cat(x, skip) rows of thread (position tid >> 4, float4 (tid & 15) + 16 q)
+    float pvr[14];                                                       // parameter vectors
+    float scv[5];                                                        // DDPM schedule values of the fused update (vector loads)
+};
+__device__ __forceinline__ void ups_last_request_rings(const UpsLastArgs& a, int lane, int w, UpsLastHead& hd) {
+    lvlm_prefetch<1, 5, 8, 8>(hd.ring8, reinterpret_cast<const float4*>(a.Wc[0]) + (size_t)(2 * w) * 5 * 8 * 2 * 64, lane);
+    lvlm_prefetch<1, 1, 8, 8>(hd.ring_r, reinterpret_cast<const float4*>(a.Wr0) + (size_t)(2 * w) * 1 * 8 * 2 * 64, lane);
+}
+// rows of cat(x, skip): quarters [Q0, Q1) of the 256 channels (0, 1 = x; 2, 3 = skip)
+template <int Q0, int Q1>
+__device__ __forceinline__ void ups_last_request_rows(const UpsLastArgs& a, int tid, UpsLastHead& hd) {
+    const int L = a.L, b = blockIdx.x;
     if ((tid >> 4) < L) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = Q0; q < Q1; ++q) {
             const int p = tid >> 4, cf = (tid & 15) + 16 * q;            // float4 index over the 256 channels
             const float* src = cf < 32 ? a.x + ((size_t)b * L + p) * 128 + 4 * cf : a.skip + ((size_t)b * L + p) * 128 + 4 * (cf - 32);
-            xin[q] = *reinterpret_cast<const float4*>(src);
+            hd.xin[q] = *reinterpret_cast<const float4*>(src);
         }
     }
-    // (round 6) the LDS zero fill HERE, while the scalar load of t is on its way: the parameter loads below need t for the time-bias row and
-    // the wave stalls in front of them until it arrives (in-order issue) -- behind them the zero fill was 0.5 us in front of the first barrier
-    __builtin_amdgcn_sched_barrier(0);
-    for (int i = tid; i < 2 * ROWS1 * XPB / 16; i += 256) reinterpret_cast<float4*>(&XI[0][0])[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = tid; i < 4 * ROWS1 * QPB / 16; i += 256) reinterpret_cast<float4*>(&Q[0][0][0])[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = tid; i < 4 * ROWS2 * PPB / 16; i += 256) reinterpret_cast<float4*>(&P[0][0][0])[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    __builtin_amdgcn_sched_barrier(0);
-    float pvr[14];                                                       // requested now, written to LDS after the noise generation
+}
+__device__ __forceinline__ void ups_last_request_pv(const UpsLastArgs& a, int t_now, int tid, UpsLastHead& hd) {
+    constexpr int CB = 128, C = 64;
+    float v[14] = {};                    // (a local array, copied out once: stores to hd in both branches end up as ONE store through a selected address -- private memory)
     if (tid < CB) {
         const float* src[8] = {a.bc[0], a.gam[0], a.bet[0], a.bc[1], a.gam[1], a.bet[1], a.tb0 + (size_t)t_now * a.tb_ld, a.br0};
 #pragma unroll
-        for (int i = 0; i < 8; ++i) pvr[i] = src[i][tid];
+        for (int i = 0; i < 8; ++i) v[i] = src[i][tid];
     } else if (tid < CB + C) {
         const int c = tid - CB;
         const float* src[13] = {a.bc[2], a.gam[2], a.bet[2], a.bc[3], a.gam[3], a.bet[3], a.bc[4], a.gam[4], a.bet[4],
                                 a.tb1 + (size_t)t_now * a.tb_ld, a.br1, a.bo, a.bu};
 #pragma unroll
-        for (int i = 0; i < 13; ++i) pvr[i] = src[i][c];
-        pvr[13] = a.bf[c < a.F ? c : 0];
+        for (int i = 0; i < 13; ++i) v[i] = src[i][c];
+        v[13] = a.bf[c < a.F ? c : 0];
     }
-    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 14; ++i) hd.pvr[i] = v[i];
+}
+__device__ __forceinline__ void ups_last_request_sched(const UpsLastArgs& a, bool sc_vec, int tu_z, UpsLastHead& hd) {
+    // EVERY wave issues exactly five loads, whatever the launch does (no update fused / DDIM: five reads of the final weights' first word):
+    // behind a branch with an unknown number of requests the compiler waits for every OLDER load with a count that covers these too
+    const ComposeArgs& u = a.upd;
+    const float* tab[5] = {u.objective == 2 ? u.sqrt_ac : u.sqrt_recip, u.objective == 2 ? u.sqrt_1mac : u.sqrt_recipm1, u.coef1, u.coef2, u.logvar};
+#pragma unroll
+    for (int i = 0; i < 5; ++i)         // (buffer loads: a uniform address would be turned back into a scalar load)
+        hd.scv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sc_vec ? tab[i] : a.Wf), 0, 0x7ffffff0u, 0x00020000), sc_vec ? (unsigned)tu_z * 4u : 0u, 0, 0));
+}
+
+// (Round 4 also compiled this kernel and ups_tail128_kernel for two workgroups per CU above 320 rows -- 89 / 60 spilled registers, config 3
+// 833 -> 841 / 838 us per step --: removed in round 6; level0_down / level1_down keep their two-workgroup instantiations.)
+// The body of ups_last_kernel as a stage function.  FUSED (ups_tail_last_kernel): the planes are zero, the skip rows (hd.xin[2..3]), the
+// parameter vectors and the schedule values are on their way or here, `uin` is the previous stage's transposed-convolution tile
+// (tile mt: channels (2 w + mt) 16 + 4 lq + i, column = position lr) and goes to channels [0, 128) of XI with the stand-alone
+// kernel's split; tu_in is the update's t (read at the top of the launch).
+template <bool FUSED>
+__device__ __forceinline__ void ups_last_stage(const UpsLastArgs& a, const int t_in, const int tu_in, UpsLastHead& hd, const f32x4 (&uin)[2] PH_PARAM) {
+    PH(0);        // phase clocks (profiling builds, kernels.h PhaseBuf): mark k follows the k-th workgroup barrier, the last one the final stores
+    typedef UpsLastLds LDS;
+    constexpr int C = LDS::C, CB = LDS::CB, NP1 = LDS::NP1, ROWS1 = LDS::ROWS1, ROWS2 = LDS::ROWS2;
+    constexpr int XPB = LDS::XPB, QPB = LDS::QPB, PPB = LDS::PPB, APB = LDS::APB, HP = LDS::HP;
+    const LDS lds = ups_last_lds();
+    unsigned char (*XI)[ROWS1 * XPB] = reinterpret_cast<unsigned char (*)[ROWS1 * XPB]>(lds.XI);
+    unsigned char (*Q)[2][ROWS1 * QPB] = reinterpret_cast<unsigned char (*)[2][ROWS1 * QPB]>(lds.Q);
+    unsigned char (*P)[2][ROWS2 * PPB] = reinterpret_cast<unsigned char (*)[2][ROWS2 * PPB]>(lds.P);
+    unsigned char* R = lds.R;
+    float (*PVB)[CB] = reinterpret_cast<float (*)[CB]>(lds.PVB);
+    float (*PV)[C] = reinterpret_cast<float (*)[C]>(lds.PV);
+    float* H = reinterpret_cast<float*>(R);
+    unsigned char* Aph = R; unsigned char* Apl = R + NP1 * APB;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+    const int L = a.L, L2 = 2 * a.L, b = blockIdx.x;
+    const int t_now = FUSED ? t_in : step_scalar(a.t_ptr, a.t_imm);
+    const int c0 = w * 16, cl = c0 + lq * 4;
+    auto clb = [&](int mt) { return (2 * w + mt) * 16 + lq * 4; };       // the lane's channels in the 128-channel block
+    auto wbase = [&](const float* W, int taps, int ks) { return reinterpret_cast<const float4*>(W) + (size_t)w * taps * ks * 2 * 64; };
+    LvlRing<1, 8> ring;                                                  // weight rings (one 16-channel tile at a time)
+    LvlRing<1, 8>& ring_r = hd.ring_r;
+    LvlRing<1, 8, 2>& ring8 = hd.ring8;                                  // ... of the 256-input-channel block: two taps deep (see LvlRing)
+    auto wtile = [&](const float* W, int tile, int taps, int ks) { return reinterpret_cast<const float4*>(W) + (size_t)tile * taps * ks * 2 * 64; };
+    if constexpr (!FUSED) ups_last_request_rings(a, lane, w, hd);
+    PfRegs pfr;
+    l2_prefetch_early(a.pf, pfr);
+    float4 (&xin)[4] = hd.xin;                                           // cat(x, skip) rows, requested before the zero fill and its barrier
+    float (&pvr)[14] = hd.pvr;                                           // requested now, written to LDS after the noise generation
+    float (&scv)[5] = hd.scv;
+    // (round 4) the input rows are requested BEFORE the parameter vectors go to LDS: `PV[i][tid] = src[i][tid]` waits for its loads,
+    // and rows requested after that wait were a second serial round trip at the head of the launch
+    if constexpr (!FUSED) {
+        ups_last_request_rows<0, 4>(a, tid, hd);
+        // (round 6) the LDS zero fill HERE, while the scalar load of t is on its way: the parameter loads below need t for the time-bias row and
+        // the wave stalls in front of them until it arrives (in-order issue) -- behind them the zero fill was 0.5 us in front of the first barrier
+        __builtin_amdgcn_sched_barrier(0);
+        ups_last_zero_fill(tid);
+        __builtin_amdgcn_sched_barrier(0);
+        ups_last_request_pv(a, t_now, tid, hd);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     // Fused update (UpsLastArgs::upd): the noise of this sample's state elements depends on nothing this kernel computes, so it is
     // generated HERE, while the first loads are in flight, by all four waves (slot s = nt * 64 + lane of the final stage's wave 0;
     // wave w takes slots 32 w ..), parked in R -- free until block 1's output goes there -- and picked up by wave 0 after barrier 4.
     // At the kernel's tail (one wave, after the last barrier) Philox + Box-Muller were 2.5 us of a 3 us phase (phase clocks, round 4).
-    const int tu_z = a.fuse_upd ? step_scalar(a.upd.t_ptr, a.upd.t_imm) : 0;
+    int tu_z;
+    if constexpr (FUSED) tu_z = tu_in; else tu_z = a.fuse_upd ? step_scalar(a.upd.t_ptr, a.upd.t_imm) : 0;
     StepCoefs sc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, -1, 0};      // the step's schedule values (DDIM: its table row, scalar loads)
     // DDPM: the five schedule values of step t are VECTOR loads of wave 0, consumed where the update is applied.  As scalar loads at this
     // point (through round 6) they sat behind the scalar load of t -- two serial round trips to memory, lines nobody has read for 32 steps --
@@ -2598,16 +2787,11 @@ __global__ __launch_bounds__(256) void ups_last_kernel(const UpsLastArgs a) {
     // lgkmcnt(0): scalar loads included): this phase measured 4.2 - 4.6 us with the update fused against 2.7 - 3.0 us without
     // (3.9 us now; same-box with the zero fill moved up as well: 313.7 -> 311.9 us per step).
     const bool sc_vec = a.fuse_upd && !a.upd.ddim_tab;
-    float scv[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     if (a.fuse_upd && !sc_vec) sc = plain_step_coefs(a.upd, tu_z);
-    {   // EVERY wave issues exactly five loads, whatever the launch does (no update fused / DDIM: five reads of the final weights' first word):
-        // behind a branch with an unknown number of requests the compiler waits for every OLDER load with a count that covers these too
-        const ComposeArgs& u = a.upd;
-        const float* tab[5] = {u.objective == 2 ? u.sqrt_ac : u.sqrt_recip, u.objective == 2 ? u.sqrt_1mac : u.sqrt_recipm1, u.coef1, u.coef2, u.logvar};
+    if constexpr (!FUSED) {
 #pragma unroll
-        for (int i = 0; i < 5; ++i)         // (buffer loads: a uniform address would be turned back into a scalar load)
-            scv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sc_vec ? tab[i] : a.Wf), 0, 0x7ffffff0u, 0x00020000), sc_vec ? (unsigned)tu_z * 4u : 0u, 0, 0));
+        for (int i = 0; i < 5; ++i) scv[i] = 0.f;
+        ups_last_request_sched(a, sc_vec, tu_z, hd);
     }
     // (seed, sample offset) of the sample loops: SCALAR loads, requested here with t.  As `u.dyn ? u.dyn[0] : u.seed` inside the noise
     // block they were vector loads waited for with vmcnt(0) -- i.e. behind the 160 KB of weight fragments, the input rows and the
@@ -2640,13 +2824,15 @@ __global__ __launch_bounds__(256) void ups_last_kernel(const UpsLastArgs a) {
         for (int i = 0; i < 13; ++i) PV[i][c] = pvr[i];
         PV[13][c] = c < a.F ? pvr[13] : 0.f;
     }
-    __syncthreads();
-    PH(1);
+    if constexpr (!FUSED) {
+        __syncthreads();
+        PH(1);
+    }
     {
         const int p = tid >> 4, c4 = tid & 15;                           // 16 positions x 16 float4, four channel quarters
         if (p < L) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
+            for (int q = FUSED ? 2 : 0; q < 4; ++q) {
                 const int cf = c4 + 16 * q;
                 const float4 v = xin[q];
                 half4v hi, lo;
@@ -2655,6 +2841,19 @@ __global__ __launch_bounds__(256) void ups_last_kernel(const UpsLastArgs a) {
                 lo[2] = (_Float16)((v.z - (float)hi[2]) * H3_SCALE); lo[3] = (_Float16)((v.w - (float)hi[3]) * H3_SCALE);
                 *reinterpret_cast<half4v*>(&XI[0][(p + 2) * XPB + 8 * cf]) = hi;
                 *reinterpret_cast<half4v*>(&XI[1][(p + 2) * XPB + 8 * cf]) = lo;
+            }
+        }
+        if constexpr (FUSED) {
+            if (lr < L) {
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) {
+                    half4v hi, lo;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) { hi[i] = (_Float16)uin[mt][i]; lo[i] = (_Float16)((uin[mt][i] - (float)hi[i]) * H3_SCALE); }
+                    const int off = (lr + 2) * XPB + 2 * clb(mt);
+                    *reinterpret_cast<half4v*>(&XI[0][off]) = hi;
+                    *reinterpret_cast<half4v*>(&XI[1][off]) = lo;
+                }
             }
         }
     }
@@ -2676,7 +2875,8 @@ __global__ __launch_bounds__(256) void ups_last_kernel(const UpsLastArgs a) {
         }
     };
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    __syncthreads();
+    __syncthreads();               // (FUSED: the ONE barrier between the two stages)
+    if constexpr (FUSED) PH(1);
     PH(2);
 
     // ---- block 0 (256 -> 128, residual_conv): the wave's two 16-channel tiles one after the other ----
@@ -2892,6 +3092,13 @@ __global__ __launch_bounds__(256) void ups_last_kernel(const UpsLastArgs a) {
     PH_FLUSH(a.ph);
 }
 
+__global__ __launch_bounds__(256) void ups_last_kernel(const UpsLastArgs) {
+    PH_DECL;
+    UpsLastHead hd;
+    const f32x4 none[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+    ups_last_stage<false>(kernarg<UpsLastArgs>(), 0, 0, hd, none PH_ARG);
+}
+
 // ---------------------------------------------------------------------------------------------
 // ups_tail128_kernel: the second half of the second-finest up level in one launch, one sample per workgroup:
 //   ResidualTemporalBlock(256 -> 128) -> attention site(128) -> Upsample1d(128) (ConvTranspose1d k4 s2 p1, L -> 2L <= 16)
@@ -2911,8 +3118,14 @@ struct UpsTailArgs {
     Pf pf; PhaseBuf ph;                                 // L2 warm-up for the next launch
 };
 
-__global__ __launch_bounds__(256) void ups_tail128_kernel(const UpsTailArgs a) {
-    PH_DECL;
+// The body of ups_tail128_kernel as a stage function.  FUSED (ups_tail_last_kernel, followed by ups_last_stage for the same sample):
+// the next stage's LDS zero fill rides on this one's, its skip rows, parameter vectors and schedule values are requested a phase ahead,
+// its first weight fragments behind this stage's LAST fragment request (vector loads return in order: 128 KB of them in front of a tap
+// of the transposed convolution would stall it), and the transposed convolution's tile is handed over in registers (`uout`) -- it goes
+// to memory only when a.up is set (taps).  The L2 touches of the next stage's weights move in front of the attention core: the next
+// request of this stage is a whole core away, and the next stage's own requests no longer queue behind them.
+template <bool FUSED>
+__device__ __forceinline__ void ups_tail128_stage(const UpsTailArgs& a, const int t_in, const UpsLastArgs* a1, const int tu_z, UpsLastHead* hd, f32x4 (*uout)[2] PH_PARAM) {
     PH(0);        // phase clocks (profiling builds, kernels.h PhaseBuf): mark k follows the k-th workgroup barrier, the last one the final stores
     constexpr int C = 128, CI = 256, NP = 16, ROWS = NP + 4;
     constexpr int XPB = 2 * CI + 16, PPB = 2 * C + 16, APB = 2 * 128 + 16, HP = C + 4;
@@ -2926,7 +3139,7 @@ __global__ __launch_bounds__(256) void ups_tail128_kernel(const UpsTailArgs a) {
     unsigned char* Aph = R; unsigned char* Apl = R + NP * APB;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
     const int L = a.L, L2 = 2 * a.L, b = blockIdx.x;
-    const int t_now = step_scalar(a.t_ptr, a.t_imm);
+    const int t_now = FUSED ? t_in : step_scalar(a.t_ptr, a.t_imm);
     auto cl = [&](int mt) { return (2 * w + mt) * 16 + lq * 4; };
     auto wtile = [&](const float* W, int tile, int taps, int ks) { return reinterpret_cast<const float4*>(W) + (size_t)tile * taps * ks * 2 * 64; };
     LvlRing<1, 8> ring, ring_r;
@@ -2951,6 +3164,7 @@ __global__ __launch_bounds__(256) void ups_tail128_kernel(const UpsTailArgs a) {
     __builtin_amdgcn_sched_barrier(0);
     for (int i = tid; i < 2 * ROWS * XPB / 16; i += 256) reinterpret_cast<float4*>(&XI[0][0])[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int i = tid; i < 4 * ROWS * PPB / 16; i += 256) reinterpret_cast<float4*>(&P[0][0][0])[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (FUSED) ups_last_zero_fill(tid);                        // the next stage's planes, while this one's first loads are on their way
     if (tid < C) {
 #pragma unroll
         for (int i = 0; i < 10; ++i) PV[i][tid] = pvr[i];
@@ -3104,6 +3318,7 @@ __global__ __launch_bounds__(256) void ups_tail128_kernel(const UpsTailArgs a) {
             va[0][i] = M[4 + i] + Lo[4 + i] * H3_INV;
         }
     }
+    if constexpr (FUSED) l2_prefetch_late(a.pf, pfr);
     f32x4 att[2][1];
     attn_site_core<1>(qa, ka, va, att, 1, NP, NP, L, lq, lr);
     __syncthreads();                                          // every wave is done with H (the att planes alias it)
@@ -3139,14 +3354,41 @@ __global__ __launch_bounds__(256) void ups_tail128_kernel(const UpsTailArgs a) {
         f32x4 t[1][1];
         lvlm_conv<1, 1, 4, 4, PPB, 8, 1>(ring, wtile(a.Wu, 2 * w, 4, 4), P[0][0], P[0][1], 0, 0, 0, ROWS - 1, lane, t); u[0] = t[0][0];
         lvlm_prefetch<1, 4, 4, 8>(ring, wtile(a.Wu, 2 * w + 1, 4, 4), lane);
-        l2_prefetch_late(a.pf, pfr);
+        if constexpr (FUSED) {
+            ups_last_request_rows<2, 4>(*a1, tid, *hd);
+            ups_last_request_pv(*a1, t_now, tid, *hd);
+            ups_last_request_sched(*a1, a1->fuse_upd && !a1->upd.ddim_tab, tu_z, *hd);
+        } else l2_prefetch_late(a.pf, pfr);
         lvlm_conv<1, 1, 4, 4, PPB, 8, 1>(ring, wtile(a.Wu, 2 * w + 1, 4, 4), P[0][0], P[0][1], 0, 0, 0, ROWS - 1, lane, t); u[1] = t[0][0];
+        if constexpr (FUSED) ups_last_request_rings(*a1, lane, w, *hd);
         add4(u[0], pv4(9, 0)); add4(u[1], pv4(9, 1));
-        store(u, a.up, L2);
+        if (!FUSED || a.up) store(u, a.up, L2);
+        if constexpr (FUSED) { (*uout)[0] = u[0]; (*uout)[1] = u[1]; }
     }
     PH(9);
     l2_prefetch_done(a.pf, pfr);
     PH_FLUSH(a.ph);
+}
+
+__global__ __launch_bounds__(256) void ups_tail128_kernel(const UpsTailArgs) {
+    PH_DECL;
+    ups_tail128_stage<false>(kernarg<UpsTailArgs>(), 0, nullptr, 0, nullptr, nullptr PH_ARG);
+}
+
+// ups_tail_last_kernel: ups_tail128_kernel and ups_last_kernel of the sample blockIdx.x as ONE launch (at most 320 rows; the two
+// stages' LDS arrays are disjoint, 137 KB together).  Like level01_down_kernel: nothing crosses workgroups, one barrier at the seam,
+// one phase-clock slot per stage.  The fused update of ups_last_kernel is unchanged.
+struct UpsTailLastArgs { UpsTailArgs l0; UpsLastArgs l1; };
+__global__ __launch_bounds__(256) void ups_tail_last_kernel(const UpsTailLastArgs) {
+    PH_DECL;
+    const UpsTailLastArgs& a = kernarg<UpsTailLastArgs>();
+    const int t_now = step_scalar(a.l0.t_ptr, a.l0.t_imm);
+    const int tu_z = a.l1.fuse_upd ? step_scalar(a.l1.upd.t_ptr, a.l1.upd.t_imm) : 0;
+    UpsLastHead hd;
+    f32x4 u[2];
+    ups_tail128_stage<true>(a.l0, t_now, &a.l1, tu_z, &hd, &u PH_ARG);
+    PH_RESET;
+    ups_last_stage<true>(a.l1, t_now, tu_z, hd, u PH_ARG);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -93,9 +93,11 @@ int  cindm_unet1d_finalize(cindm_unet1d* h, void* stream);
  *   run-time options select among kernels whose operands are packed already: the handle stays finalized --
  *     cindm_unet1d: "no_exchange", "recover", "tune";  cindm_unet2d: none;  cindm_forceunet: "no_exchange", "recover", "dbg", "stress";
  *   "range_fallback" is read-only: *_set_option refuses it as an unknown key ("unknown option: range_fallback").
- * Every alternative path computes the same function (the parity suite runs all of them); defaults are the fast path.  Keys (round 6: 24; DESIGN.md section 4.6 lists what was removed and why):
+ * Every alternative path computes the same function (the parity suite runs all of them); defaults are the fast path.  Keys (25; DESIGN.md section 4.6 lists what round 6 removed and why):
  *   "mfma_f32" (1 = exact fp32 MFMA kernels instead of the split-fp16 ones), "local_gn", "attn_site", "attn_head" (0 / 1 / 2),
- *   "level0" (master switch of the level kernels), "level1" (0 / 1 / 2 samples per workgroup), "ups_last", "ups_tail", "dconv", "dconv2",
+ *   "level0" (master switch of the level kernels), "level1" (0 / 1 / 2 samples per workgroup), "ups_last", "ups_tail",
+ *   "level_pairs" (1 = up to 320 rows the two finest down levels run as one launch and so do the two finest up levels, when both stand-alone
+ *   level kernels of a pair would run: two launches fewer per forward, bit-identical results), "dconv", "dconv2",
  *   "dresample" (0 / 1 / 2: general kernel / 32 / 16-or-32 columns per workgroup), "l2_prefetch" (launches touch their successor's weights), "ws_alias", "pingpong" (the sample loops keep t / step index /
  *   epochs in two slots advanced by the step's update), "fuse_update" (plain single-model steps apply the update inside the last U-Net
  *   kernel), "fuse_gather" (time composition of two-body states: the first U-Net kernel reads the state's windows in place),
