@@ -90,3 +90,101 @@ static int upload_ddim_tables(int T, int32_t n_steps, const int32_t* times, cons
     *tn_out = tn_dev;
     return 0;
 }
+
+// ---- the chain recorder (DESIGN 4.5l) --------------------------------------------------------------------------------------------------
+// cindm_ddpm1d_set_recorder arms the handle; the next chain entry takes the recorder with RecScope as its first statement -- so the
+// call consumes it however it ends -- and either refuses it or runs with it:
+//   rec_begin   checks it against the chain (steps, floats per record) before the entry's first launch or copy
+//   rec_arm     writes the device descriptor; part of what a chain body does after it has set the step state, so a re-run re-arms
+//   rec_node    the step's chain_record_kernel launch (captured with the step)
+//   rec_done    what cindm_ddpm1d_recorder_info reports
+struct RecScope {
+    cindm_ddpm1d* h; RecSpec r;
+    explicit RecScope(cindm_ddpm1d* h_) : h(h_) {
+        if (!h) return;
+        r = h->rec_armed; h->rec_armed = RecSpec();
+        for (int& v : h->rec_info) v = 0;
+    }
+    ~RecScope() { if (h) h->rec = nullptr; }
+    bool on() const { return r.buf != nullptr; }
+};
+
+static int64_t rec_records(int64_t n, int every) { return (n + every - 1) / every; }
+
+static int rec_begin(RecScope& rs, const float* x, int n_steps, int64_t fpr, const char* x0_refusal = nullptr) {
+    if (!rs.on()) return 0;
+    RecSpec& r = rs.r;
+    REQUIRE(n_steps >= 1 && fpr > 0, "recorder: empty chain");
+    REQUIRE(((uintptr_t)x & 15) == 0, "recorder: the state x must be 16-byte aligned (the record node reads it 16 bytes per lane)");
+    r.every = std::min(r.every, n_steps);      // the same records (every >= n: the result alone), and the kernel's step arithmetic stays small
+    if ((r.streams & 2) && x0_refusal) return fail(x0_refusal);
+    REQUIRE((fpr & 3) == 0, "recorder: the state's float count must be a multiple of 4");
+    const int ns = (r.streams & 1) + ((r.streams >> 1) & 1);
+    const int64_t need = (rec_records(n_steps, r.every) * ns + ((r.streams & 2) ? 1 : 0)) * fpr;
+    if (r.buf_floats < need)
+        return fail("recorder: buffer too small: " + std::to_string(r.buf_floats) + " floats, this chain needs " + std::to_string(need) +
+                    " (ceil(steps / every) records x streams x floats per record, plus one staging record for x0)");
+    r.n = n_steps; r.fpr = fpr;
+    r.x0_stage = (r.streams & 2) ? r.buf + rec_records(n_steps, r.every) * ns * fpr : nullptr;
+    rs.h->rec = &rs.r;
+    return 0;
+}
+
+// chain_record_kernel's store flavour: nt (1), the lowest of the three in both measured sessions, all three inside the spread of a 2-D
+// step (DESIGN 4.5l).  Only the profiling build reads CINDM_RECORD_STORE = 0 (plain) / 1 / 2 (sc1), so that tools/bench_record.py
+// can take that measurement again; the production library has no such switch.
+static int rec_store_policy() {
+#ifdef CINDM_PHASE_PROF
+    const char* e = getenv("CINDM_RECORD_STORE");
+    const int v = e ? atoi(e) : 1;
+    if (v >= 0 && v <= 2) return v;
+#endif
+    return 1;
+}
+
+// t0 >= 0: a DDPM loop from that timestep (word = the timestep's word); -1: a DDIM loop (word = the step index's word)
+static void rec_arm(cindm_ddpm1d* h, int t0, int word, int slot_stride, hipStream_t stream) {
+    if (!h->rec) return;
+    const RecSpec& r = *h->rec;
+    RecordDesc d;
+    d.dst = r.buf; d.fpr = r.fpr; d.every = r.every; d.n = r.n; d.streams = r.streams; d.t0 = t0;
+    d.word = word; d.slot_stride = slot_stride; d.store = rec_store_policy(); d.pad = 0;
+    hipLaunchKernelGGL(record_arm_kernel, dim3(1), dim3(64), 0, stream, h->t_dev, d);
+}
+
+static int rec_node(cindm_ddpm1d* h, const float* state, int slot, hipStream_t stream) {
+    const RecSpec& r = *h->rec;
+    const int ns = (r.streams & 1) + ((r.streams >> 1) & 1);
+    const int64_t blocks = (r.fpr / 4 + kRecordThreads - 1) / kRecordThreads;
+    hipLaunchKernelGGL(chain_record_kernel, dim3((unsigned)std::min<int64_t>(blocks, 2048), ns), dim3(kRecordThreads), 0, stream,
+                       (const int*)h->t_dev, state, slot);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int rec_done(RecScope& rs, int rc) {
+    if (rs.on() && rc == 0) {
+        const RecSpec& r = rs.r;
+        rs.h->rec_info[0] = (int)rec_records(r.n, r.every); rs.h->rec_info[1] = (int)r.fpr; rs.h->rec_info[2] = r.n; rs.h->rec_info[3] = r.streams;
+    }
+    return rc;
+}
+
+extern "C" int cindm_ddpm1d_set_recorder(cindm_ddpm1d* h, float* buf, int64_t buf_floats, int32_t every, int32_t streams) {
+    if (h) h->rec_armed = RecSpec();      // (a refused call leaves the handle disarmed)
+    if (buf) {
+        REQUIRE(every >= 1, "recorder: every must be >= 1");
+        REQUIRE(streams >= 1 && (streams & ~3) == 0, "recorder: unknown stream bit (1 = x, 2 = x0)");
+        REQUIRE(buf_floats > 0 && ((uintptr_t)buf & 15) == 0, "recorder: the buffer must be 16-byte aligned and not empty");
+    }
+    REQUIRE(h, "null handle");
+    if (!buf) return 0;
+    h->rec_armed.buf = buf; h->rec_armed.buf_floats = buf_floats; h->rec_armed.every = every; h->rec_armed.streams = streams;
+    return 0;
+}
+
+extern "C" int cindm_ddpm1d_recorder_info(const cindm_ddpm1d* h, int32_t info[4]) {
+    REQUIRE(h && info, "null argument");
+    for (int i = 0; i < 4; ++i) info[i] = h->rec_info[i];
+    return 0;
+}

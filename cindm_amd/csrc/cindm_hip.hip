@@ -2018,6 +2018,12 @@ extern "C" int cindm_unet1d_tap(cindm_unet1d* h, const char* name, int64_t rows,
 
 // ============================================================================ GaussianDiffusion1D
 
+// A recorder as armed by the caller (buf .. streams) and as one chain runs it (the rest, filled by rec_begin)
+struct RecSpec {
+    float* buf = nullptr; int64_t buf_floats = 0; int every = 0, streams = 0;
+    int n = 0; int64_t fpr = 0; float* x0_stage = nullptr;
+};
+
 struct cindm_ddpm1d {
     int T = 0;
     float* tab = nullptr;        // 13 tables, each [T]
@@ -2029,6 +2035,9 @@ struct cindm_ddpm1d {
     int last_step_launches = 0, last_step_fused = 0;     // what the last emitted reverse step consisted of (cindm_ddpm1d_last_step_info)
     int last_chain_recovered = 0, last_chain_crowded = 0, last_chain_in_flight = 0, last_chain_range = 0;     // cindm_ddpm1d_last_chain_info
     hipGraph_t graph1 = nullptr; hipGraphExec_t gexec1 = nullptr;      // ping-pong loops: the one-step graph that ends an odd count
+    // the chain recorder (cindm_ddpm1d_set_recorder, chain_host.inc): what the next chain call will take, the one a running chain
+    // records with (null: none) and what the last chain wrote (cindm_ddpm1d_recorder_info)
+    RecSpec rec_armed; const RecSpec* rec = nullptr; int rec_info[4] = {0, 0, 0, 0};
     void drop_graph() {
         if (gexec) (void)hipGraphExecDestroy(gexec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -2173,6 +2182,7 @@ struct StepIO {
     int pingpong, parity;   // plain sample loop: step state in two slots, advanced by the update itself (no step_counter launch)
     int state_pp;           // guided DDIM loop: x_out is the OTHER of two state buffers -- the update writes it directly (no staging, no copy)
     const float* ula_tab; int ula_L, ula_t_hi;         // Langevin loop: per-timestep (scalar, ss, std, -) rows (device), inner count, first timestep
+    int rec;                // recorded chain: the recorder's stream mask on the call that ends a step (chain_record_kernel follows it), else 0
 };
 
 // clears the exchange regions of the U-Net workspaces inside a step workspace (before a step is captured into a graph)
@@ -2306,6 +2316,11 @@ static int run_step(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, c
     }
     HIPCHK(hipGetLastError());
     if (guided && !io.state_pp) HIPCHK(hipMemcpyAsync(io.x_out, a.x_out, (size_t)ne * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    if (io.rec && h->rec) {
+        // after the step's last writer of the state and of the step state: a ping-pong step has just advanced the OTHER slot
+        if (rec_node(h, io.x_out, io.pingpong ? 1 - q : 0, stream) != 0) return -1;
+        h->last_step_launches += 1;
+    }
     return 0;
 }
 
@@ -2489,7 +2504,10 @@ static void key_common(KeyBuilder& K, int kind, const cindm_unet1d* pair, const 
     K(kind)(pair)(pair->generation)(uncond)(uncond ? uncond->generation : 0)(*c)(B)(ws)(ws_bytes)(pair->NX())(uncond ? uncond->NX() : false);
     K(io.x)(io.cond)(io.x_out)(io.noise)(io.noise_t_stride)(io.add_noise)(io.inp_cond)(io.inp_steps)(io.inp_noise)(io.inp_noise_t_stride);
     K(io.ddim_tab)(io.ddim_tnext)(io.iso)(io.iso_steps)(io.recur_t_stride);
+    K(io.rec)(io.x0_out);      // recorder on, which streams; the x0 stream's staging record is an operand of the captured update
 }
+
+static int64_t state_floats(const cindm_unet1d* pair, const cindm_compose_desc* c, int64_t B) { return B * (int64_t)state_len(pair, c) * c->n_bodies * 4; }
 
 // What the 1-D sample loops hand unchanged to every helper below them.
 struct Chain1D {
@@ -2509,6 +2527,7 @@ static StepIO chain_io(const Chain1D& ch, float* x, const float* cond, const flo
     io.inp_cond = inpaint_cond; io.inp_steps = inpaint_steps; io.inp_noise = inpaint_noise_steps;
     io.inp_noise_t_stride = ch.B * inpaint_steps * ch.c->n_bodies * 4;
     io.dyn = reinterpret_cast<const unsigned long long*>(ch.h->t_dev + 16);
+    if (ch.h->rec) { io.rec = ch.h->rec->streams; io.x0_out = ch.h->rec->x0_stage; }      // (x0_out set: the update is not fused)
     return io;
 }
 
@@ -2521,6 +2540,7 @@ static int loop_steps(const Chain1D& ch, StepIO io, int kind, int t0, int nsteps
     const bool pp = ch.pair->O("pingpong") != 0;
     io.dec_t = 1; io.pingpong = pp ? 1 : 0;
     start_loop(ch.h, ch.pair, ch.uncond, ch.c, t0, ch.stream, seed, sample_offset);
+    rec_arm(ch.h, io.ddim_tab ? -1 : t0, io.ddim_tab ? 2 : 0, pp ? 4 : 0, ch.stream);
     KeyBuilder K;
     key_common(K, kind, ch.pair, ch.uncond, ch.c, io, ch.B, ch.ws, ch.ws_bytes);
     K(pp)(io.ula_tab)(io.ula_L)(io.ula_t_hi);
@@ -2542,15 +2562,17 @@ extern "C" int cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_un
                                    const float* inpaint_cond, int32_t inpaint_steps, const float* inpaint_noise_steps,
                                    int32_t t_start, int32_t t_end, int64_t B, void* ws, size_t ws_bytes, void* stream_,
                                    int32_t use_graph) {
+    RecScope rs(h);
     REQUIRE(h && pair && c && x, "null argument");
     REQUIRE(t_start < h->T && t_end >= 0 && t_end <= t_start, "bad timestep range");
+    if (rec_begin(rs, x, t_start - t_end + 1, state_floats(pair, c, B)) != 0) return -1;
     hipStream_t stream = nullptr;
     if (chain_stream(h, stream_, use_graph, &stream) != 0) return -1;
     const Chain1D ch{h, pair, uncond, c, B, ws, ws_bytes, stream, use_graph};
     const StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     float* xT = nullptr;
     if (chain_slices(pair, uncond, c, B, ws, ws_bytes, &xT, nullptr) != 0) return -1;
-    return loop_chain(ch, io, 0, (int)t_start, t_start - t_end + 1, x, xT, seed, sample_offset);
+    return rec_done(rs, loop_chain(ch, io, 0, (int)t_start, t_start - t_end + 1, x, xT, seed, sample_offset));
 }
 
 extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, const cindm_compose_desc* c,
@@ -2558,7 +2580,10 @@ extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cin
                                         const float* coefs, const float* noise_steps, uint64_t seed, int64_t sample_offset,
                                         const float* inpaint_cond, int32_t inpaint_steps, const float* inpaint_noise_steps,
                                         int64_t B, void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
+    RecScope rs(h);
     REQUIRE(h && pair && c && x && times && coefs, "null argument");
+    if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    if (rec_begin(rs, x, n_steps, state_floats(pair, c, B)) != 0) return -1;
     hipStream_t stream = nullptr;
     if (chain_stream(h, stream_, use_graph, &stream) != 0) return -1;
     const Chain1D ch{h, pair, uncond, c, B, ws, ws_bytes, stream, use_graph};
@@ -2569,7 +2594,7 @@ extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cin
     if (upload_ddim_tables(h->T, n_steps, times, coefs, ddim_buf, stream, &tn_dev) != 0) return -1;
     StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     io.ddim_tab = ddim_buf; io.ddim_tnext = tn_dev;
-    return loop_chain(ch, io, 1, (int)times[0], n_steps, x, xT, seed, sample_offset);
+    return rec_done(rs, loop_chain(ch, io, 1, (int)times[0], n_steps, x, xT, seed, sample_offset));
 }
 
 // Autoregressive time composition (autoregress_time_compose_sample, model/diffusion_1d.py:2240-2327): n_seg unguided DDIM chains, each
@@ -2583,6 +2608,8 @@ extern "C" int cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pa
                                                int32_t n_steps, const int32_t* times, const float* coefs, const uint64_t* seeds,
                                                const float* init_tape, const float* noise_steps, int64_t sample_offset, int64_t B,
                                                void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
+    RecScope rs(h);
+    REQUIRE(!rs.on(), "recorder: the autoregressive rollout is not recorded (its step index is (segment, step)); the recorder was dropped");
     REQUIRE(h && pair && c && x && cond && cond_buf && out && times && coefs && seeds, "null argument");
     REQUIRE(c->mode == CINDM_COMPOSE_PLAIN || c->mode == CINDM_COMPOSE_MULTIBODY, "the rollout runs the plain (or multibody) prediction");
     REQUIRE(c->cond_steps >= 1, "conditioned_steps == 0: the reference's img[:, -0:] hands over the whole state and its slice assignment fails");
@@ -2634,6 +2661,8 @@ extern "C" int cindm_ddpm1d_sample_ula(cindm_ddpm1d* h, cindm_unet1d* pair, cind
                                        const float* step_size, const float* noise_std, void* tab, size_t tab_bytes,
                                        const float* noise_tape, uint64_t seed, int64_t sample_offset, int64_t B,
                                        void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
+    RecScope rs(h);
+    REQUIRE(!rs.on(), "recorder: the Langevin chain is not recorded (its step index is (timestep, inner iteration)); the recorder was dropped");
     REQUIRE(h && pair && c && x && scalar && step_size && noise_std && tab, "null argument");
     REQUIRE(c->mode == CINDM_COMPOSE_MULTIBODY && uncond, "the Langevin phase runs the multibody composition (pair + unconditioned model)");
     REQUIRE(c->cond_steps == 0, "the Langevin phase moves the whole state: pass cat(cond, x) as x with cond_steps = 0");
@@ -2668,6 +2697,7 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
                                           const float* initial_state_overwrite, int32_t overwrite_steps,
                                           int32_t t_start, int32_t t_end, int64_t B, void* ws, size_t ws_bytes, void* stream_,
                                           int32_t use_graph) {
+    RecScope rs(h);
     REQUIRE(h && pair && c && dz && x, "null argument");
     REQUIRE(t_start < h->T && t_end >= 0 && t_end <= t_start, "bad timestep range");
     REQUIRE(dz->mode == 1 || dz->mode == 2, "design objective mode must be 1 (L2) or 2 (L2square)");
@@ -2675,6 +2705,7 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
     const int Ltot = state_len(pair, c);
     REQUIRE(dz->last_n_step >= 1 && dz->last_n_step <= Ltot, "last_n_step out of range");
     REQUIRE(!initial_state_overwrite || (overwrite_steps >= 1 && overwrite_steps <= Ltot), "bad overwrite_steps");
+    if (rec_begin(rs, x, t_start - t_end + 1, state_floats(pair, c, B)) != 0) return -1;
     hipStream_t stream = nullptr;
     if (chain_stream(h, stream_, use_graph, &stream) != 0) return -1;
     const Chain1D ch{h, pair, uncond, c, B, ws, ws_bytes, stream, use_graph};
@@ -2691,6 +2722,7 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
             StepIO it = io;
             it.relax = (r < iters - 1) ? 1 : 0;
             it.dec_t = it.relax ? 0 : 1;
+            if (it.relax) it.rec = 0;               // a relaxation iteration is not a step: the last iteration records
             it.recur_noise = recur_noise_steps ? recur_noise_steps + (size_t)r * n_state : nullptr;
             it.recur_tag = 0x10000u * (uint32_t)(r + 1);
             if (run_step(h, pair, uncond, c, it, 0, h->t_dev, B, ws, ws_bytes, stream) != 0) return -1;
@@ -2700,14 +2732,15 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
     float* xT = nullptr;
     if (chain_slices(pair, uncond, c, B, ws, ws_bytes, &xT, nullptr) != 0) return -1;
     // (its own tail rather than loop_steps: the step is the functor above, the key carries the objective, no ping-pong)
-    return run_chain_with_recovery(h, pair, ch.un(), x, xT, (size_t)n_state, stream, [&]() -> int {
+    return rec_done(rs, run_chain_with_recovery(h, pair, ch.un(), x, xT, (size_t)n_state, stream, [&]() -> int {
         if (prepare_step_ws(pair, uncond, c, B, ws, ws_bytes, stream) != 0) return -1;
         start_loop(h, pair, uncond, c, (int)t_start, stream, seed, sample_offset);
+        rec_arm(h, (int)t_start, 0, 0, stream);
         KeyBuilder K;
         key_common(K, 2, pair, uncond, c, io, B, ws, ws_bytes);
         K(*dz)(recur_noise_steps)(R);
         return replay_steps(h, K.k, stream, t_start - t_end + 1, use_graph, step, pair, ch.un());
-    });
+    }));
 }
 
 // Guided DDIM (ddim_sample :1724-1804 with design_fn = the built-in objective and "-recurrence-N" guidance, i.e. through the DDIM
@@ -2725,6 +2758,7 @@ extern "C" int cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pa
                                                const float* inpaint_cond, int32_t inpaint_steps, const float* inpaint_noise_steps,
                                                const float* initial_state_overwrite, int32_t overwrite_steps, int64_t B,
                                                void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
+    RecScope rs(h);
     REQUIRE(h && pair && c && dz && x && times && coefs, "null argument");
     REQUIRE(dz->mode == 1 || dz->mode == 2, "design objective mode must be 1 (L2) or 2 (L2square)");
     REQUIRE(dz->recurrence >= 1 && dz->recurrence <= 64,
@@ -2733,6 +2767,8 @@ extern "C" int cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pa
     REQUIRE(dz->last_n_step >= 1 && dz->last_n_step <= Ltot, "last_n_step out of range");
     REQUIRE(!initial_state_overwrite || (overwrite_steps >= 1 && overwrite_steps <= Ltot), "bad overwrite_steps");
     REQUIRE(!inpaint_cond || (inpaint_steps >= 1 && inpaint_steps <= Ltot), "bad inpaint_steps");
+    if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    if (rec_begin(rs, x, n_steps, state_floats(pair, c, B)) != 0) return -1;
     hipStream_t stream = nullptr;
     if (chain_stream(h, stream_, use_graph, &stream) != 0) return -1;
     const Chain1D ch{h, pair, uncond, c, B, ws, ws_bytes, stream, use_graph};
@@ -2754,15 +2790,17 @@ extern "C" int cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pa
             const int p = (q * R + r) & 1;          // parity of the chain's iteration: after two steps it is 0 again
             it.parity = p; it.x = buf[p]; it.x_out = buf[1 - p];
             it.relax = (r < R - 1) ? 1 : 0;
+            if (it.relax) it.rec = 0;               // the record node of a step follows its last iteration and reads the buffer that one wrote
             it.recur_noise = recur_noise_steps ? recur_noise_steps + (size_t)r * n_state : nullptr;
             it.recur_tag = 0x10000u * (uint32_t)(r + 1);
             if (run_step(h, pair, uncond, c, it, 0, h->t_dev, B, ws, ws_bytes, stream) != 0) return -1;
         }
         return 0;
     };
-    return run_chain_with_recovery(h, pair, ch.un(), x, xT, (size_t)n_state, stream, [&]() -> int {
+    return rec_done(rs, run_chain_with_recovery(h, pair, ch.un(), x, xT, (size_t)n_state, stream, [&]() -> int {
         if (prepare_step_ws(pair, uncond, c, B, ws, ws_bytes, stream) != 0) return -1;
         start_loop(h, pair, uncond, c, (int)times[0], stream, seed, sample_offset);
+        rec_arm(h, -1, 2, 4, stream);
         KeyBuilder K;
         key_common(K, 4, pair, uncond, c, io, B, ws, ws_bytes);
         K(*dz)(recur_noise_steps)(R);
@@ -2772,7 +2810,7 @@ extern "C" int cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pa
             if (use_graph) HIPCHK(hipStreamSynchronize(stream));
         }
         return rc;
-    });
+    }));
 }
 
 extern "C" int cindm_fill_normal(float* out, int64_t B, int64_t per_sample, uint64_t seed, int64_t sample_offset,

@@ -888,14 +888,17 @@ extern "C" int cindm_ddpm2d_sample_force(cindm_ddpm1d* s, cindm_unet2d* u, cindm
                                          float lambda_force, float lambda_overlap, int32_t down_factor, int32_t sum_boundary,
                                          const float* eta, float* grad, void* ws, size_t ws_bytes, void* ws_force,
                                          size_t ws_force_bytes, void* stream_, int32_t use_graph) {
+    RecScope rs(s);
     REQUIRE(s && u && f && x && eta && grad && ws && ws_force, "null argument");
     REQUIRE(t_start < s->T && t_end >= 0 && t_end <= t_start, "bad timestep range");
     REQUIRE(u->d.image_size == f->d.image_size, "Unet and ForceUnet image sizes differ");
+    REQUIRE(u->d.channels == 3 * frames + 3, "state channels must be 3 * frames + 3");
+    if (rec_begin2(rs, u, x, t_start - t_end + 1, B, nb) != 0) return -1;
     hipStream_t stream = nullptr;
     if (chain_stream(s, stream_, use_graph, &stream) != 0) return -1;
     const int HW = u->d.image_size * u->d.image_size, CP = u->CP();
-    REQUIRE(u->d.channels == 3 * frames + 3, "state channels must be 3 * frames + 3");
-    const Step2IO io = chain_io2(u, x, B, nb, noise_state_steps, noise_boundary_steps, seed, sample_offset);
+    Step2IO io = chain_io2(u, x, B, nb, noise_state_steps, noise_boundary_steps, seed, sample_offset);
+    if (s->rec) io.x0_out = s->rec->x0_stage;
     const int64_t n4 = B * nb * (int64_t)HW * (CP / 4);
     auto one_step = [&](int) -> int {
         if (cindm_airfoil_design_grad(f, x, B, nb, frames, CP, p_min, p_max, lambda_force, lambda_overlap, down_factor, sum_boundary,
@@ -903,13 +906,14 @@ extern "C" int cindm_ddpm2d_sample_force(cindm_ddpm1d* s, cindm_unet2d* u, cindm
         if (run_step2(s, u, io, B, nb, use_average_share, 1, 0, s->t_dev, ws, ws_bytes, stream) != 0) return -1;
         hipLaunchKernelGGL(guided_shift2d_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, x, grad, eta, s->t_dev, n4);
         HIPCHK(hipGetLastError());
-        return 0;
+        return s->rec ? rec_node(s, x, 0, stream) : 0;      // (the shift is the step's last writer of the state)
     };
     const int nsteps = t_start - t_end + 1;
-    return force_chain_with_recovery(u, f, x, B * nb, ws, ws_bytes, stream, [&]() -> int {
+    return rec_done(rs, force_chain_with_recovery(u, f, x, B * nb, ws, ws_bytes, stream, [&]() -> int {
         hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (int)t_start, 0ull, 0ll);
+        rec_arm(s, (int)t_start, 0, 0, stream);
         return replay_once(stream, nsteps, use_graph, one_step);
-    });
+    }));
 }
 
 // Guided DDIM of the 2-D path with the airfoil objective inside the captured step (DESIGN 4.5k): per DDIM step i, pair (t, t_next),
@@ -924,6 +928,7 @@ extern "C" int cindm_ddpm2d_sample_ddim_force(cindm_ddpm1d* s, cindm_unet2d* u, 
                                               float p_min, float p_max, float lambda_force, float lambda_overlap, int32_t down_factor,
                                               int32_t sum_boundary, float* grad, void* ws, size_t ws_bytes, void* ws_force,
                                               size_t ws_force_bytes, void* stream_, int32_t use_graph) {
+    RecScope rs(s);
     REQUIRE(s && u && f && x && times && coefs && weights && tab && grad && ws && ws_force, "null argument");
     REQUIRE(((use_average_share >> 4) & 3) <= 2 && (use_average_share & ~0x31) == 0,
             "bad use_average_share word (bit 0 mean / sum, bits 4-5 objective 0..2; DDIM has no share_noise False)");
@@ -943,6 +948,8 @@ extern "C" int cindm_ddpm2d_sample_ddim_force(cindm_ddpm1d* s, cindm_unet2d* u, 
     REQUIRE((((uintptr_t)x | (uintptr_t)grad | (uintptr_t)ws) & 15) == 0, "x, grad and ws must be 16-byte aligned");
     REQUIRE(((uintptr_t)ws_force & 255) == 0 && ws_force_bytes >= cindm_airfoil_design_workspace_bytes(f, B, nb, 1),
             "surrogate workspace too small (cindm_airfoil_design_workspace_bytes) or not 256-byte aligned");
+    if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    if (rec_begin2(rs, u, x, n_steps, B, nb, kNoX0Ddim2d) != 0) return -1;
     hipStream_t stream = nullptr;
     if (chain_stream(s, stream_, use_graph, &stream) != 0) return -1;
     float* tab_f = (float*)tab;
@@ -967,10 +974,11 @@ extern "C" int cindm_ddpm2d_sample_ddim_force(cindm_ddpm1d* s, cindm_unet2d* u, 
         hipLaunchKernelGGL(ddim2d_guided_update_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a, (const float*)grad);
         hipLaunchKernelGGL(step_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (const int*)tn_dev, (int*)nullptr, (int*)nullptr);
         HIPCHK(hipGetLastError());
-        return 0;
+        return s->rec ? rec_node(s, x, 0, stream) : 0;
     };
-    return force_chain_with_recovery(u, f, x, NI, ws, ws_bytes, stream, [&]() -> int {
+    return rec_done(rs, force_chain_with_recovery(u, f, x, NI, ws, ws_bytes, stream, [&]() -> int {
         hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (int)times[0], 0ull, 0ll);
+        rec_arm(s, -1, 2, 0, stream);
         return replay_once(stream, n_steps, use_graph, one_step);
-    });
+    }));
 }

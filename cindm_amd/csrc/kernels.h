@@ -3822,4 +3822,72 @@ __global__ void step_counter_kernel(int* t_dev, const int* ddim_tnext, int* e0, 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The chain recorder (cindm_ddpm1d_set_recorder): one more node of a captured step, after the step's last writer of the
+// state.  Everything that may differ between two calls served by one cached graph lives in device memory: the descriptor below sits in
+// words 32 .. 43 of the schedule handle's 256-byte step-state block (words 0 .. 7: the two step-state slots, 16 .. 19: seed and sample
+// offset; the rest was unused) and is written by record_arm_kernel at the start of a chain -- a recovery re-run writes it again.  The
+// launch arguments are what a capture fixes anyway: the block, the buffer this step wrote and the step-state slot it advanced.
+// Steps done s = t0 - word (DDPM: the word is the timestep the NEXT step reads) or s = word (DDIM: the step index, already advanced);
+// the step records iff s % every == 0 or s == n, as record ceil(s / every) - 1.  Every wave takes that decision from scalar loads and
+// a step that does not record returns before any vector memory access.
+// Buffer: [n_records][streams][fpr] floats, then one staging record when the x0 stream is on (the update kernel's x0_out operand points
+// there; blockIdx.y == 1, or == 0 when x0 is the only stream, copies it).  Offsets are 64-bit: record * fpr passes 2^31 floats at
+// forty 50 MB records; fpr is a multiple of 4 and the buffer 16-byte aligned (the host refuses anything else).  store (profiling build only; the production kernel stores nt): 0 plain, 1 nt, 2 sc1 (write-through) -- see DESIGN 4.5l for what was measured.
+struct RecordDesc {
+    float* dst; long long fpr;
+    int every, n, streams, t0;          // streams: bit 0 x, bit 1 x0; t0 >= 0: DDPM from that timestep, -1: the word is the step count
+    int word, slot_stride, store, pad;  // the step-state word of slot 0 and the distance to slot 1's (0: the loop has one slot)
+};
+static constexpr int kRecordDescWord = 32;
+static constexpr int kRecordThreads = 256;      // the block size chain_record_kernel is launched with
+
+__global__ void record_arm_kernel(int* t_dev, RecordDesc d) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *reinterpret_cast<RecordDesc*>(t_dev + kRecordDescWord) = d;
+}
+
+typedef float record_v4f __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) record_v4f record_gv4f;      // global address space: global_ rather than flat_ accesses
+
+template <int STORE>
+__device__ __forceinline__ void record_store16(record_gv4f* p, const record_v4f v) {
+    if (STORE == 1) __builtin_nontemporal_store(v, p);
+    else if (STORE == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(p), "v"(v) : "memory");
+    else *p = v;
+}
+
+// grid-stride copy of n floats, 16 bytes per lane, four loads in flight per lane
+template <int STORE>
+__device__ __forceinline__ void record_copy(float* dst, const float* src, long long n) {
+    const record_gv4f* s = (const record_gv4f*)src;
+    record_gv4f* d = (record_gv4f*)dst;
+    const long long n4 = n >> 2, stride = (long long)gridDim.x * kRecordThreads;
+    long long i = (long long)blockIdx.x * kRecordThreads + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        const record_v4f a = s[i], b = s[i + stride], c = s[i + 2 * stride], e = s[i + 3 * stride];
+        record_store16<STORE>(d + i, a); record_store16<STORE>(d + i + stride, b);
+        record_store16<STORE>(d + i + 2 * stride, c); record_store16<STORE>(d + i + 3 * stride, e);
+    }
+    for (; i < n4; i += stride) record_store16<STORE>(d + i, s[i]);
+}
+
+__global__ void __launch_bounds__(kRecordThreads) chain_record_kernel(const int* __restrict__ t_dev, const float* __restrict__ state, int slot) {
+    const RecordDesc d = *reinterpret_cast<const RecordDesc*>(t_dev + kRecordDescWord);
+    const int w = t_dev[d.word + slot * d.slot_stride];
+    const int s = d.t0 >= 0 ? d.t0 - w : w;
+    if (s < 1 || s > d.n || (s % d.every != 0 && s != d.n)) return;
+    // (64-bit: s + every - 1 must not wrap for an every near 2^31; the host also clamps every to n)
+    const long long rec = ((long long)s + d.every - 1) / d.every - 1, n_rec = ((long long)d.n + d.every - 1) / d.every;
+    const int ns = (d.streams & 1) + ((d.streams >> 1) & 1);
+    const bool x0 = blockIdx.y == 1 || !(d.streams & 1);
+    const float* src = x0 ? d.dst + n_rec * ns * d.fpr : state;
+    float* dst = d.dst + (rec * ns + blockIdx.y) * d.fpr;
+#ifdef CINDM_PHASE_PROF
+    // the profiling build keeps the two flavours nt was measured against (tools/bench_record.py store)
+    if (d.store == 0) { record_copy<0>(dst, src, d.fpr); return; }
+    if (d.store == 2) { record_copy<2>(dst, src, d.fpr); return; }
+#endif
+    record_copy<1>(dst, src, d.fpr);
+}
+
 }  // namespace cindm

@@ -1200,6 +1200,14 @@ extern "C" int cindm_ddpm2d_predict(cindm_ddpm1d* s, cindm_unet2d* u, const floa
                      (hipStream_t)stream);
 }
 
+// the recorder of a 2-D chain: one record is the whole state in the library's layout, [B * nb][H * W][padded channels]
+static const char* const kNoX0Ddim2d = "recorder: the 2-D DDIM update kernels have no x0 operand: the x0 stream is served by the DDPM entries only";
+static int rec_begin2(RecScope& rs, const cindm_unet2d* u, const float* x, int n_steps, int64_t B, int nb, const char* x0_refusal = nullptr) {
+    if (!rs.on()) return 0;
+    REQUIRE(u && B > 0 && nb >= 1, "bad batch");
+    return rec_begin(rs, x, n_steps, B * nb * (int64_t)u->d.image_size * u->d.image_size * u->CP(), x0_refusal);
+}
+
 // the Step2IO of a 2-D sample loop: in-place state, per-step tapes (or counter noise), the device counter decremented by the step
 static Step2IO chain_io2(const cindm_unet2d* u, float* x, int64_t B, int nb, const float* noise_state_steps,
                          const float* noise_boundary_steps, uint64_t seed, int64_t sample_offset) {
@@ -1216,14 +1224,20 @@ extern "C" int cindm_ddpm2d_sample(cindm_ddpm1d* s, cindm_unet2d* u, float* x, i
                                    const float* noise_state_steps, const float* noise_boundary_steps, uint64_t seed,
                                    int64_t sample_offset, int32_t t_start, int32_t t_end, void* ws, size_t ws_bytes,
                                    void* stream_, int32_t use_graph) {
+    RecScope rs(s);
     REQUIRE(s && u && x, "null argument");
     REQUIRE(t_start < s->T && t_end >= 0 && t_end <= t_start, "bad timestep range");
+    if (rec_begin2(rs, u, x, t_start - t_end + 1, B, nb) != 0) return -1;
     hipStream_t stream = nullptr;
     if (chain_stream(s, stream_, use_graph, &stream) != 0) return -1;
-    const Step2IO io = chain_io2(u, x, B, nb, noise_state_steps, noise_boundary_steps, seed, sample_offset);
+    Step2IO io = chain_io2(u, x, B, nb, noise_state_steps, noise_boundary_steps, seed, sample_offset);
+    if (s->rec) io.x0_out = s->rec->x0_stage;
     hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (int)t_start, 0ull, 0ll);
-    return replay_once(stream, t_start - t_end + 1, use_graph,
-                       [&](int) { return run_step2(s, u, io, B, nb, use_average_share, 1, 0, s->t_dev, ws, ws_bytes, stream); });
+    rec_arm(s, (int)t_start, 0, 0, stream);
+    return rec_done(rs, replay_once(stream, t_start - t_end + 1, use_graph, [&](int) {
+        if (run_step2(s, u, io, B, nb, use_average_share, 1, 0, s->t_dev, ws, ws_bytes, stream) != 0) return -1;
+        return s->rec ? rec_node(s, x, 0, stream) : 0;      // (after the step's counter launch: the word is the next timestep)
+    }));
 }
 
 // DDIM loop of the 2-D path (ddim_sample; DESIGN 4.5g): one step = the U-Net + ddim2d_update_kernel + step_counter_kernel
@@ -1249,6 +1263,7 @@ extern "C" int cindm_ddpm2d_sample_ddim(cindm_ddpm1d* s, cindm_unet2d* u, float*
                                         int32_t n_steps, const int32_t* times, const float* coefs, void* tab, size_t tab_bytes,
                                         const float* noise_state_steps, const float* noise_boundary_steps, uint64_t seed,
                                         int64_t sample_offset, void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
+    RecScope rs(s);
     REQUIRE(s && u && x && times && coefs && tab && ws, "null argument");
     REQUIRE(((use_average_share >> 4) & 3) <= 2 && (use_average_share & ~0x31) == 0,
             "bad use_average_share word (bit 0 mean / sum, bits 4-5 objective 0..2; DDIM has no share_noise False)");
@@ -1260,6 +1275,8 @@ extern "C" int cindm_ddpm2d_sample_ddim(cindm_ddpm1d* s, cindm_unet2d* u, float*
     const int HW = u->d.image_size * u->d.image_size, CP = u->CP(), Cs = u->d.channels - 3;
     REQUIRE(NI * (int64_t)HW * CP < (1ll << 31), "state too large for one launch");
     REQUIRE(ws_bytes >= cindm_ddpm2d_workspace_bytes(u, NI), "workspace too small");
+    if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    if (rec_begin2(rs, u, x, n_steps, B, nb, kNoX0Ddim2d) != 0) return -1;
     hipStream_t stream = nullptr;
     if (chain_stream(s, stream_, use_graph, &stream) != 0) return -1;
     // the per-step tables go to the caller's device buffer
@@ -1276,7 +1293,11 @@ extern "C" int cindm_ddpm2d_sample_ddim(cindm_ddpm1d* s, cindm_unet2d* u, float*
     a.noise_bound = noise_boundary_steps; a.nb_t_stride = NI * (int64_t)HW * 3;
     a.seed = seed; a.sample_off = sample_offset;
     hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (int)times[0], 0ull, 0ll);
-    return replay_once(stream, n_steps, use_graph, [&](int) { return run_ddim_step2(s, u, a, B, nb, ws, ws_bytes, stream); });
+    rec_arm(s, -1, 2, 0, stream);
+    return rec_done(rs, replay_once(stream, n_steps, use_graph, [&](int) {
+        if (run_ddim_step2(s, u, a, B, nb, ws, ws_bytes, stream) != 0) return -1;
+        return s->rec ? rec_node(s, x, 0, stream) : 0;
+    }));
 }
 
 extern "C" int cindm_fill_noise2d(float* x, int64_t B, int32_t nb, int32_t hw, int32_t channels, int32_t padded_channels,

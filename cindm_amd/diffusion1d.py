@@ -30,6 +30,7 @@ from torch import nn
 
 from . import _ffi
 from .objectives import PointObjective
+from .record import DeviceRecorder, LoopRecorder
 from .schedule import ddim_schedule, make_schedule, ula_schedule
 
 ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"])
@@ -258,6 +259,28 @@ class GaussianDiffusion1D(nn.Module):
                           "exchange-free plan (correct, slower).  Run chains one after the other, or one process per GPU.", RuntimeWarning)
         return info
 
+    def _recorder(self, every, trajectory, n, shape, device, **when):
+        """The DeviceRecorder of a library chain of ``n`` steps over a state of ``shape`` [B, L, F], or None without the keyword."""
+        if every is None:
+            return None
+        return DeviceRecorder(n, every, trajectory, shape[0] * shape[1] * shape[2], device, **when)
+
+    @staticmethod
+    def _arm(rec, h):
+        """First thing a chain's ``call`` does: the chain call consumes the recorder, so every issue -- the range-rule re-run
+        included -- arms it again."""
+        if rec is not None:
+            rec.arm(h)
+
+    def _recorded(self, out, rec):
+        """What a sampling call returns: the designs, or (designs, ChainRecord) when it recorded."""
+        if rec is None:
+            return out
+        if isinstance(rec, LoopRecorder):
+            return out, rec.result()
+        shape = tuple(out.shape)
+        return out, rec.collect(self._handle(), lambda rows: rows.reshape((rows.shape[0],) + shape))
+
     def last_step_info(self):
         """(kernel launches, update fused into the U-Net's last kernel?) of the reverse step emitted last -- as launched
         by the library, not a model of it (``cindm_ddpm1d_last_step_info``)."""
@@ -484,13 +507,14 @@ class GaussianDiffusion1D(nn.Module):
     # ------------------------------------------------------------------ loops
     @torch.no_grad()
     def _run_loop(self, img, cond, desc, t_start, t_end, *, noise_steps, seed, sample_offset, inpaint_cond,
-                  inpaint_noise_steps, use_graph=True):
+                  inpaint_noise_steps, use_graph=True, rec=None):
         """The unguided reverse loop as one library call (cindm_ddpm1d_sample)."""
         B = img.shape[0]
         cond_d = self._f32(cond, img.device) if (cond is not None and self.conditioned_steps != 0) else None
         inp = self._f32(inpaint_cond, img.device)
 
         def call(h, un, ws):
+            self._arm(rec, h)
             with torch.cuda.device(img.device):
                 _ffi.check(_ffi.lib().cindm_ddpm1d_sample(
                     h, self.model._h, un, C.byref(desc), _ffi.ptr(img), _ffi.ptr(cond_d), _ffi.ptr(noise_steps),
@@ -501,7 +525,7 @@ class GaussianDiffusion1D(nn.Module):
 
     @torch.no_grad()
     def _run_guided_loop(self, img, cond, desc, dz, t_start, t_end, *, noise, seed, sample_offset, inpaint_cond,
-                         initial_state_overwrite, use_graph=True):
+                         initial_state_overwrite, use_graph=True, rec=None):
         """Reverse steps t_start .. t_end guided by the built-in objective as one library call
         (cindm_ddpm1d_sample_guided); ``noise`` rows (step / recur / cond) are indexed by t."""
         device, B = img.device, img.shape[0]
@@ -510,6 +534,7 @@ class GaussianDiffusion1D(nn.Module):
         iso = self._f32(initial_state_overwrite, device)
 
         def call(h, un, ws):
+            self._arm(rec, h)
             with torch.cuda.device(device):
                 _ffi.check(_ffi.lib().cindm_ddpm1d_sample_guided(
                     h, self.model._h, un, C.byref(desc), C.byref(dz), _ffi.ptr(img), _ffi.ptr(cond_d),
@@ -521,7 +546,7 @@ class GaussianDiffusion1D(nn.Module):
 
     @torch.no_grad()
     def _run_guided_ddim(self, img, cond, desc, dz, times, coefs, *, noise, seed, sample_offset, inpaint_cond,
-                         initial_state_overwrite, use_graph=True):
+                         initial_state_overwrite, use_graph=True, rec=None):
         """DDIM steps ``times[0] .. times[-2]`` guided by the built-in objective as one library call
         (cindm_ddpm1d_sample_ddim_guided); ``noise`` rows (step / recur / cond) are indexed by the position in ``times``."""
         device, B = img.device, img.shape[0]
@@ -533,6 +558,7 @@ class GaussianDiffusion1D(nn.Module):
         carr = coefs.contiguous()
 
         def call(h, un, ws):
+            self._arm(rec, h)
             with torch.cuda.device(device):
                 _ffi.check(_ffi.lib().cindm_ddpm1d_sample_ddim_guided(
                     h, self.model._h, un, C.byref(desc), C.byref(dz), _ffi.ptr(img), _ffi.ptr(cond_d), S, tarr, _ffi.ptr(carr),
@@ -558,9 +584,12 @@ class GaussianDiffusion1D(nn.Module):
     @torch.no_grad()
     def p_sample_loop(self, shape, cond, n_composed=0, compose_start_step=4, compose_n_bodies=2, compose_mode="mean",
                       design_fn=None, design_guidance="standard", initial_state_overwrite=None, initialization_mode=0,
-                      initialization_img=None, *, noise=None, seed=None, sample_offset=0, use_graph=True, t_stop=0):
+                      initialization_img=None, *, noise=None, seed=None, sample_offset=0, use_graph=True, t_stop=0,
+                      return_trajectory_every=None, trajectory=("x",)):
         """:1656-1720.  Build-only keywords: ``noise`` (NoiseTape, explicit draws), ``seed`` /
-        ``sample_offset`` (counter-based generator keyed by global sample index), ``t_stop`` (truncate)."""
+        ``sample_offset`` (counter-based generator keyed by global sample index), ``t_stop`` (truncate),
+        ``return_trajectory_every=k`` with ``trajectory=("x",)`` / ``("x", "x0")``: returns (designs, ChainRecord) with the state after
+        every k-th step and after the last one (record.py; recorded inside the captured step on the library routes)."""
         device = self.betas.device
         if device.type != "cuda":
             raise _ffi.CindmError("GaussianDiffusion1D is on the CPU: move it to a ROCm device; there is no CPU execution path")
@@ -584,41 +613,55 @@ class GaussianDiffusion1D(nn.Module):
         inpaint = cond if (self.conditioned_steps == 0 and cond is not None) else None
         fast = design_fn is None and "recurrence" not in design_guidance and initial_state_overwrite is None
         dz = design_fn.descriptor(design_guidance) if isinstance(design_fn, PointObjective) else None
+        t_first, n_steps = self.num_timesteps - 1, self.num_timesteps - int(t_stop)
+        # (the device record buffer is allocated only on the routes that are library chains)
+        device_rec = lambda: self._recorder(return_trajectory_every, trajectory, n_steps, full, device, t_start=t_first)
         if dz is not None and design_fn.last_n_step <= full[1]:
             # built-in objective: the guided loop (gradient, overwrite, relaxations) stays inside the captured step
-            return self._run_guided_loop(img, cond, desc, dz, self.num_timesteps - 1, t_stop, noise=noise, seed=seed,
-                                         sample_offset=sample_offset, inpaint_cond=inpaint,
-                                         initial_state_overwrite=initial_state_overwrite, use_graph=use_graph)
+            rec = device_rec()
+            return self._recorded(self._run_guided_loop(img, cond, desc, dz, t_first, t_stop, noise=noise, seed=seed,
+                                                        sample_offset=sample_offset, inpaint_cond=inpaint,
+                                                        initial_state_overwrite=initial_state_overwrite, use_graph=use_graph,
+                                                        rec=rec), rec)
         if fast:
-            return self._run_loop(img, cond, desc, self.num_timesteps - 1, t_stop,
-                                  noise_steps=None if noise is None else noise.step, seed=seed, sample_offset=sample_offset,
-                                  inpaint_cond=inpaint, inpaint_noise_steps=None if noise is None else noise.cond,
-                                  use_graph=use_graph)
+            rec = device_rec()
+            return self._recorded(self._run_loop(img, cond, desc, t_first, t_stop,
+                                                 noise_steps=None if noise is None else noise.step, seed=seed,
+                                                 sample_offset=sample_offset, inpaint_cond=inpaint,
+                                                 inpaint_noise_steps=None if noise is None else noise.cond,
+                                                 use_graph=use_graph, rec=rec), rec)
         img_T = img
+        # this route loops in Python: the same record, cloned per step
+        rec = None if return_trajectory_every is None else LoopRecorder(n_steps, return_trajectory_every, trajectory, t_start=t_first)
 
         def chain():
             # (the steps' predictions only feed the next step: the exchange flags are read once, after the last one)
             img = img_T
-            for t in reversed(range(t_stop, self.num_timesteps)):
+            if rec is not None:
+                rec.reset()
+            for i, t in enumerate(reversed(range(t_stop, self.num_timesteps))):
                 nz = None if noise is None else noise.step[t]
                 rn = None if (noise is None or noise.recur is None) else noise.recur[t]
-                img, _ = self._guided_step(img, cond, t, desc, design_fn, design_guidance, initial_state_overwrite, nz, rn,
-                                           check=False)
+                img, x_start = self._guided_step(img, cond, t, desc, design_fn, design_guidance, initial_state_overwrite, nz, rn,
+                                                 check=False)
                 if inpaint is not None:
                     zc = noise.cond[t] if (noise is not None and noise.cond is not None) else torch.randn_like(inpaint)
                     img[:, :inpaint.shape[1], :] = self.q_sample(self._f32(inpaint, device), t, zc)
+                if rec is not None:
+                    rec.after(i, img, x_start)
             return img
 
         img = chain()
         if self._timed_out(desc, device):
             img = self._rerun_exchange_free(chain, desc, device)
-        return img
+        return self._recorded(img, rec)
 
     @torch.no_grad()
     def sample(self, batch_size=16, cond=None, is_composing_time=False, n_composed=2, compose_start_step=4,
                compose_n_bodies=2, compose_mode="mean", design_fn=None, design_guidance="standard",
                initial_state_overwrite=None, initialization_mode=0, initialization_img=None, **build_kw):
-        """:2330-2376.  ``build_kw``: noise=, seed=, sample_offset=, use_graph=, t_stop= (see p_sample_loop)."""
+        """:2330-2376.  ``build_kw``: noise=, seed=, sample_offset=, use_graph=, t_stop=, return_trajectory_every=, trajectory=
+        (see p_sample_loop)."""
         self.is_ddim_sampling = self.sampling_timesteps < self.num_timesteps
         if self.is_ddim_sampling:               # :2348-2363
             build_kw.pop("t_stop", None)
@@ -713,14 +756,18 @@ class GaussianDiffusion1D(nn.Module):
 
     @torch.no_grad()
     def sample_compose_multibodies(self, cond, N, L, n_bodies, *, noise=None, seed=None, sample_offset=0,
-                                   use_graph=True, t_stop=0, full_state=False):
+                                   use_graph=True, t_stop=0, full_state=False, return_trajectory_every=None, trajectory=("x",)):
         """:1986-2042: x = cat(cond, noise); for i = N-1 .. 401: L Langevin iterations on the whole x (``sample_step_ULA``, the
         conditioning rows drift too); for i = 400 .. 0: x[:, cs:] = p_sample(x[:, cs:], x[:, :cs], i).  Returns
         [B, rollout_steps, 4*n_bodies].  N <= 401 has no Langevin phase (L and n_bodies are not looked at, as before).
         Build-only keywords: ``noise`` (NoiseTape; ``ula`` feeds the Langevin draws), ``seed`` / ``sample_offset``, ``use_graph``,
         ``t_stop`` (truncate; > 400 stops inside the Langevin phase, after timestep t_stop), ``full_state`` (return the whole
-        [B, conditioned_steps + rollout_steps, F] state, drifted conditioning rows first)."""
+        [B, conditioned_steps + rollout_steps, F] state, drifted conditioning rows first), ``return_trajectory_every`` /
+        ``trajectory`` (N <= 401 only; the records hold the [B, rollout_steps, F] state; see p_sample_loop)."""
         ula = N > 401
+        if ula and return_trajectory_every is not None:
+            raise NotImplementedError("return_trajectory_every with N > 401: the Langevin chain's step index is (timestep, inner iteration) "
+                                      "and the library does not record it")
         if ula:
             self._ula_refusals(N, L, n_bodies)
         if not cond.is_cuda:
@@ -747,10 +794,13 @@ class GaussianDiffusion1D(nn.Module):
                 return x if full_state else x[:, cs:].contiguous()
             # the DDPM phase is conditioned on the DRIFTED rows, not on the caller's cond (:2033)
             img, cond, t_first = x[:, cs:].contiguous(), x[:, :cs].contiguous(), 400
+        rec = self._recorder(return_trajectory_every, trajectory, t_first - int(t_stop) + 1, shape, device, t_start=t_first)
         out = self._run_loop(img, cond, desc, t_first, t_stop, noise_steps=None if noise is None else noise.step,
                              seed=seed, sample_offset=sample_offset, inpaint_cond=None, inpaint_noise_steps=None,
-                             use_graph=use_graph)
-        return torch.cat([self._f32(cond, device), out], dim=1) if full_state else out
+                             use_graph=use_graph, rec=rec)
+        record = None if rec is None else self._recorded(out, rec)[1]
+        out = torch.cat([self._f32(cond, device), out], dim=1) if full_state else out
+        return out if rec is None else (out, record)
 
     # ------------------------------------------------------------------ out of scope
     def forward(self, *a, **k):
@@ -766,7 +816,7 @@ class GaussianDiffusion1D(nn.Module):
     def ddim_sample(self, shape, cond, n_composed=None, clip_denoised=True, compose_start_step=4, compose_n_bodies=2,
                     compose_mode="mean", design_fn=None, design_guidance="standard", initial_state_overwrite=None,
                     initialization_mode=0, initialization_img=None, *, noise=None, seed=None, sample_offset=0,
-                    use_graph=True, init_img=None, step_range=None):
+                    use_graph=True, init_img=None, step_range=None, return_trajectory_every=None, trajectory=("x",)):
         """:1724-1804.  Build-only keywords: ``init_img`` + ``step_range=(i0, i1)`` run DDIM steps i0 .. i1-1 from a given
         state (teacher-forced segments for parity tests: the deterministic sampler amplifies a 1e-6 perturbation of the
         U-Net to 1e-3 .. 1e-2 over 50 .. 250 steps with random-init weights -- measured on the CPU reference itself).
@@ -777,7 +827,8 @@ class GaussianDiffusion1D(nn.Module):
         ``PointObjective`` under "standard" / "standard-alpha" ``-recurrence-N`` (N >= 1, last_n_step <= L) runs as one library
         chain (``cindm_ddpm1d_sample_ddim_guided``; counter-based draws keyed by (seed, sample_offset + b, t, element) when there
         is no tape); any other callable or guidance: each step is ``recurrence`` library predictions + the user's autograd
-        gradient, and the DDIM update of the tiny state runs in torch."""
+        gradient, and the DDIM update of the tiny state runs in torch.
+        ``return_trajectory_every`` / ``trajectory``: as p_sample_loop; steps are counted from the first step this call runs."""
         device = self.betas.device
         if device.type != "cuda":
             raise _ffi.CindmError("GaussianDiffusion1D is on the CPU: move it to a ROCm device; there is no CPU execution path")
@@ -806,14 +857,17 @@ class GaussianDiffusion1D(nn.Module):
             tarr = (C.c_int32 * (S + 1))(*times)
             carr = coefs.contiguous()
 
+            rec = self._recorder(return_trajectory_every, trajectory, S, tuple(img.shape), device, times=times)
+
             def call(h, un, ws):
+                self._arm(rec, h)
                 with torch.cuda.device(device):
                     _ffi.check(_ffi.lib().cindm_ddpm1d_sample_ddim(
                         h, self.model._h, un, C.byref(desc), _ffi.ptr(img), _ffi.ptr(cond_d), S, tarr, _ffi.ptr(carr),
                         _ffi.ptr(None if noise is None else noise.step), C.c_uint64(seed), sample_offset, _ffi.ptr(inp),
                         0 if inp is None else inp.shape[1], _ffi.ptr(None if noise is None else noise.cond), B,
                         _ffi.ptr(ws), ws.numel(), _ffi.current_stream(device), int(use_graph)))
-            return self._chain(img, desc, call)
+            return self._recorded(self._chain(img, desc, call), rec)
         if "recurrence" not in design_guidance:
             raise NotImplementedError("DDIM with design_fn needs a '-recurrence-N' guidance (the reference's other branch "
                                       "returns x_{t-1}, not a noise prediction, :1283)")
@@ -823,37 +877,46 @@ class GaussianDiffusion1D(nn.Module):
         dz = design_fn.descriptor(design_guidance) if isinstance(design_fn, PointObjective) else None
         if dz is not None and dz.recurrence >= 1 and design_fn.last_n_step <= shape[1]:
             # built-in objective: relaxations, gradient, overwrite and the DDIM update stay inside the captured step
-            return self._run_guided_ddim(img, cond, desc, dz, times, coefs, noise=noise, seed=seed, sample_offset=sample_offset,
-                                         inpaint_cond=inpaint, initial_state_overwrite=initial_state_overwrite,
-                                         use_graph=use_graph)
+            rec = self._recorder(return_trajectory_every, trajectory, S, tuple(img.shape), device, times=times)
+            return self._recorded(self._run_guided_ddim(img, cond, desc, dz, times, coefs, noise=noise, seed=seed,
+                                                        sample_offset=sample_offset, inpaint_cond=inpaint,
+                                                        initial_state_overwrite=initial_state_overwrite, use_graph=use_graph,
+                                                        rec=rec), rec)
         coefs = coefs.to(device)
         img_T = img
+        # this route loops in Python: the same record, cloned per step
+        rec = None if return_trajectory_every is None else LoopRecorder(S, return_trajectory_every, trajectory, times=times)
 
         def chain():
             img = img_T
+            if rec is not None:
+                rec.reset()
             for i, (t, tn) in enumerate(zip(times[:-1], times[1:])):
                 rn = None if (noise is None or noise.recur is None) else noise.recur[i]
                 eps, x_start = self._guided_step(img, cond, t, desc, design_fn, design_guidance, initial_state_overwrite,
                                                  None, rn, ddim_return=True, check=False)
                 if tn < 0:
                     img = x_start
-                    continue
-                z = noise.step[i] if noise is not None else torch.randn_like(img)
-                img = x_start * coefs[i, 0] + coefs[i, 1] * eps + coefs[i, 2] * z
-                if inpaint is not None:
-                    zc = noise.cond[i] if (noise is not None and noise.cond is not None) else torch.randn_like(inpaint)
-                    img[:, :inpaint.shape[1], :] = self.q_sample(self._f32(inpaint, device), t, zc)
+                else:
+                    z = noise.step[i] if noise is not None else torch.randn_like(img)
+                    img = x_start * coefs[i, 0] + coefs[i, 1] * eps + coefs[i, 2] * z
+                    if inpaint is not None:
+                        zc = noise.cond[i] if (noise is not None and noise.cond is not None) else torch.randn_like(inpaint)
+                        img[:, :inpaint.shape[1], :] = self.q_sample(self._f32(inpaint, device), t, zc)
+                if rec is not None:
+                    rec.after(i, img, x_start)
             return img
 
         img = chain()
         if self._timed_out(desc, device):
             img = self._rerun_exchange_free(chain, desc, device)
-        return img
+        return self._recorded(img, rec)
 
     # ------------------------------------------------------------------ autoregressive time composition
     @torch.no_grad()
     def autoregress_time_compose_sample(self, batch_size, cond, n_composed, is_single_step_prediction=False, prediction_steps=40,
-                                        *, noise=None, seed=None, sample_offset=0, use_graph=True):
+                                        *, noise=None, seed=None, sample_offset=0, use_graph=True, return_trajectory_every=None,
+                                        trajectory=("x",)):
         """:2240-2327 (the default ``--time_compose_method autoregress`` of inference/inference_1d_composing_time_steps.py, :179-213).
         K segments -- n_composed + 1, or ceil(prediction_steps / conditioned_steps) with ``is_single_step_prediction`` --
         each an unguided DDIM chain on a fresh x_T [B, rollout_steps, F] conditioned on ``cond`` (segment 0) or on the last
@@ -863,6 +926,9 @@ class GaussianDiffusion1D(nn.Module):
         Build-only keywords as ``ddim_sample``: ``seed`` (segment k uses ``autoregress_segment_seeds(seed, K)[k]``, so segment k
         equals ``ddim_sample(seed=seed_k)`` on its condition), ``sample_offset``, ``use_graph``, ``noise`` = NoiseTape(init
         [K,B,R,F], step [K,S,B,R,F]).  The whole rollout is one library call (``cindm_ddpm1d_sample_autoregress``)."""
+        if return_trajectory_every is not None:
+            raise NotImplementedError("return_trajectory_every: the autoregressive rollout's step index is (segment, step) and the "
+                                      "library does not record it; record a segment with ddim_sample(seed=autoregress_segment_seeds(...)[k])")
         K = autoregress_segments(self.conditioned_steps, self.rollout_steps, n_composed, is_single_step_prediction,
                                  prediction_steps)
         Lc, R = self.conditioned_steps, self.rollout_steps

@@ -23,6 +23,7 @@ import torch
 from torch import nn
 
 from . import _ffi
+from .record import DeviceRecorder, LoopRecorder, stream_mask
 from .schedule import ddim_schedule, make_schedule
 from .unet2d import from_device_layout, to_device_layout
 
@@ -319,26 +320,57 @@ class GaussianDiffusion(nn.Module):
         return (_state_cl(noise.step_state[rows].to(device, torch.float32)),
                 _boundary_cl(noise.step_boundary[rows].to(device, torch.float32)))
 
+    def _recorder(self, every, trajectory, n, shape, device, **when):
+        """The DeviceRecorder of a library chain of ``n`` steps over ``shape`` [B, nb, C, H, W] (one record = the state in the
+        library's layout, [B * nb, H * W, padded channels]), or None without the keyword."""
+        if every is None:
+            return None
+        B, nb, Cc, H, W = shape
+        return DeviceRecorder(n, every, trajectory, B * nb * H * W * self.model.padded_channels, device, **when)
+
+    def _recorded(self, out, rec, shape):
+        """What a sampling call returns: the designs, or (designs, ChainRecord) when it recorded."""
+        if rec is None:
+            return out
+        if isinstance(rec, LoopRecorder):
+            return out, rec.result(shape)
+        B, nb, Cc, H, W = shape
+        cp = self.model.padded_channels
+
+        def unpack(rows):
+            n = rows.shape[0]
+            return from_device_layout(rows.reshape(n * B * nb, H * W, cp), Cc, H, W).reshape(n, B, nb, Cc, H, W)
+        return out, rec.collect(self._handle(), unpack)
+
     @torch.no_grad()
     def p_sample_loop(self, shape, design_fn=None, design_guidance="standard", return_all_timesteps=None, *,
-                      noise=None, seed=0, sample_offset=0, use_graph=True, t_stop=0, device=None, fused=True):
+                      noise=None, seed=0, sample_offset=0, use_graph=True, t_stop=0, device=None, fused=True,
+                      return_trajectory_every=None, trajectory=("x",)):
         """:893-907.  Returns [B, nb, C, H, W].  ``noise``: a NoiseTape2D (parity runs); otherwise x_T and the
-        per-step draws come from the library's counter-based generator keyed by (seed, sample_offset + design)."""
+        per-step draws come from the library's counter-based generator keyed by (seed, sample_offset + design).
+        ``return_trajectory_every=k`` with ``trajectory=("x",)`` / ``("x", "x0")``: returns (designs, ChainRecord) with the state
+        [n_records, B, nb, C, H, W] after every k-th step and after the last one (record.py; recorded inside the captured step on the
+        library routes, cloned per step on the routes that loop in Python)."""
         B, nb, Cc, H, W = shape
         device = device or self.betas.device
         if device.type != "cuda":
             raise _ffi.CindmError("sampling needs a ROCm device; there is no CPU execution path")
         L = _ffi.lib()
         T = self.num_timesteps
+        # (the device record buffer is allocated only on the routes that are library chains)
+        device_rec = lambda: self._recorder(return_trajectory_every, trajectory, T - int(t_stop), shape, device, t_start=T - 1)
         x = self._x_T(shape, noise, seed, sample_offset, device)
         if design_fn is None:
+            rec = device_rec()
             h, ws = self._prepare(B * nb, device)
             ns, nbnd = self._tape_cl(noise, device)
+            if rec is not None:
+                rec.arm(h)
             with torch.cuda.device(device):
                 _ffi.check(L.cindm_ddpm2d_sample(h, self.model._h, _ffi.ptr(x), B, nb, self._share_mode(),
                                                  _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, T - 1, int(t_stop),
                                                  _ffi.ptr(ws), ws.numel(), _ffi.current_stream(device), int(use_graph)))
-            return from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W)
+            return self._recorded(from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W), rec, shape)
         from .forceunet import ForceObjective
         if isinstance(design_fn, ForceObjective) and design_guidance == "standard-alpha" and fused:
             # the library's own objective: surrogate forward + input gradient, the reverse step and the guidance shift are
@@ -347,26 +379,33 @@ class GaussianDiffusion(nn.Module):
             if (fo.B, fo.nb) != (B, nb) or Cc != 3 * fo.frames + 3:
                 raise ValueError("ForceObjective was built for another batch / boundary / frame count")
             fo.model.sync_weights()
+            rec = device_rec()
             h, ws = self._prepare(B * nb, device)
             nfb = L.cindm_airfoil_design_workspace_bytes(fo.model._h, B, nb, fo.frames_per_pass)
             wsf = torch.empty(nfb, dtype=torch.uint8, device=device)
             g = torch.empty_like(x)
             eta = (self.coeff_ratio * self.betas.flip(0)).to(device, torch.float32).contiguous()
             ns, nbnd = self._tape_cl(noise, device)
+            if rec is not None:
+                rec.arm(h)
             with torch.cuda.device(device):
                 _ffi.check(L.cindm_ddpm2d_sample_force(h, self.model._h, fo.model._h, _ffi.ptr(x), B, nb, self._share_mode(),
                                                        _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, T - 1, int(t_stop),
                                                        fo.frames, fo.p_min, fo.p_max, fo.lambda_force, fo.lambda_overlap, fo.factor,
                                                        int(fo.sum_boundary), _ffi.ptr(eta), _ffi.ptr(g), _ffi.ptr(ws), ws.numel(), _ffi.ptr(wsf),
                                                        wsf.numel(), _ffi.current_stream(device), int(use_graph)))
-            return from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W)
+            return self._recorded(from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W), rec, shape)
+        # this route loops in Python: the same record, cloned per step
+        rec = None if return_trajectory_every is None else LoopRecorder(T - int(t_stop), return_trajectory_every, trajectory, t_start=T - 1)
         img = from_device_layout(x, Cc, H, W)
-        for t in reversed(range(int(t_stop), T)):
+        for i, t in enumerate(reversed(range(int(t_stop), T))):
             nz = None
             if noise is not None and t > 0:
                 nz = torch.cat([noise.step_state[t].expand(-1, nb, -1, -1, -1), noise.step_boundary[t]], dim=2)
-            img, _ = self.p_sample(shape, img, t, None, design_fn=design_fn, design_guidance=design_guidance, noise=nz)
-        return img.reshape(B, nb, Cc, H, W)
+            img, x_start = self.p_sample(shape, img, t, None, design_fn=design_fn, design_guidance=design_guidance, noise=nz)
+            if rec is not None:
+                rec.after(i, img, x_start)
+        return self._recorded(img.reshape(B, nb, Cc, H, W), rec, shape)
 
     # ------------------------------------------------------------------ DDIM
     def ddim_schedule(self):
@@ -384,7 +423,8 @@ class GaussianDiffusion(nn.Module):
 
     @torch.no_grad()
     def ddim_sample(self, shape, design_fn=None, design_guidance="standard", return_all_timesteps=False, *, noise=None, seed=0,
-                    sample_offset=0, use_graph=True, init_img=None, step_range=None, device=None, fused=True):
+                    sample_offset=0, use_graph=True, init_img=None, step_range=None, device=None, fused=True,
+                    return_trajectory_every=None, trajectory=("x",)):
         """DDIM sampling of the 2-D path (:910-949; the reference's own body cannot run, so this build defines it from its
         working pieces).  Returns [B, nb, C, H, W].  With (times, coefs) = ddim_schedule(), for each pair (t, t_next):
         (pred_noise, x_start) = model_predictions(x, t, clip_x_start=True, rederive_pred_noise=True, share_noise=True);
@@ -399,6 +439,8 @@ class GaussianDiffusion(nn.Module):
         and z come from the library's counter-based generator keyed by (seed, sample_offset + design); ``init_img`` +
         ``step_range=(i0, i1)`` run DDIM steps i0 .. i1-1 from a given state (teacher-forced segments for parity tests: the
         deterministic sampler amplifies a 1e-6 difference of the U-Net to 1e-3 over long chains).
+        ``return_trajectory_every`` / ``trajectory``: as p_sample_loop, steps counted from the first step this call runs; the stream
+        ``x`` only -- the 2-D DDIM update kernels have no x0 operand.
         Refused (NotImplementedError): any other ``design_fn`` or guidance (the reference has no working guided 2-D DDIM),
         share_noise False and ``return_all_timesteps``."""
         from .forceunet import ForceObjective
@@ -411,6 +453,8 @@ class GaussianDiffusion(nn.Module):
                                       "(model_predictions share_noise=True); there is no DDIM form of the shared posterior mean")
         if return_all_timesteps:
             raise NotImplementedError("return_all_timesteps is outside this build's scope (the reference's 2-D sampler does not build it)")
+        if return_trajectory_every is not None and stream_mask(trajectory) & 2:
+            raise NotImplementedError("trajectory 'x0' in 2-D DDIM: the DDIM update kernels have no x0 operand (the DDPM loop records it)")
         B, nb, Cc, H, W = shape
         device = device or self.betas.device
         if device.type != "cuda":
@@ -437,14 +481,19 @@ class GaussianDiffusion(nn.Module):
             # the same definition from existing calls: the objective, one unguided DDIM step, the shift in torch
             w = self.ddim_guidance_weights()
             img = from_device_layout(x, Cc, H, W)
+            lrec = None if return_trajectory_every is None else \
+                LoopRecorder(i1 - i0, return_trajectory_every, trajectory, times=times[i0:i1 + 1])
             for i in range(i0, i1):
                 g = fo(img)
                 img = self.ddim_sample(shape, noise=noise, seed=seed, sample_offset=sample_offset, use_graph=use_graph, init_img=img,
                                        step_range=(i, i + 1), device=device).reshape(B * nb, Cc, H, W)
                 img = img - w[i] * g
-            return img.reshape(B, nb, Cc, H, W)
+                if lrec is not None:
+                    lrec.after(i - i0, img)
+            return self._recorded(img.reshape(B, nb, Cc, H, W), lrec, shape)
         times, coefs = times[i0:i1 + 1], coefs[i0:i1].contiguous()
         S = len(times) - 1
+        rec = self._recorder(return_trajectory_every, trajectory, S, shape, device, times=times)
         ns, nbnd = self._tape_cl(noise, device, slice(i0, i1))
         h, ws = self._prepare(B * nb, device)
         # the per-step device tables live in a caller tensor (the library allocates nothing): [S][4] coefficients + [S] time_next
@@ -460,6 +509,8 @@ class GaussianDiffusion(nn.Module):
             nfb = L.cindm_airfoil_design_workspace_bytes(fo.model._h, B, nb, fo.frames_per_pass)
             wsf = torch.empty(nfb, dtype=torch.uint8, device=device)
             g = torch.empty_like(x)
+            if rec is not None:
+                rec.arm(h)
             with torch.cuda.device(device):
                 _ffi.check(L.cindm_ddpm2d_sample_ddim_force(h, self.model._h, fo.model._h, _ffi.ptr(x), B, nb, self._share_mode(), S, tarr,
                                                             _ffi.ptr(coefs), _ffi.ptr(w), _ffi.ptr(tab), tab.numel() * 4, _ffi.ptr(ns),
@@ -467,17 +518,20 @@ class GaussianDiffusion(nn.Module):
                                                             fo.lambda_force, fo.lambda_overlap, fo.factor, int(fo.sum_boundary), _ffi.ptr(g),
                                                             _ffi.ptr(ws), ws.numel(), _ffi.ptr(wsf), wsf.numel(),
                                                             _ffi.current_stream(device), int(use_graph)))
-            return from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W)
+            return self._recorded(from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W), rec, shape)
+        if rec is not None:
+            rec.arm(h)
         with torch.cuda.device(device):
             _ffi.check(L.cindm_ddpm2d_sample_ddim(h, self.model._h, _ffi.ptr(x), B, nb, self._share_mode(), S, tarr, _ffi.ptr(coefs),
                                                   _ffi.ptr(tab), tab.numel() * 4, _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset,
                                                   _ffi.ptr(ws), ws.numel(), _ffi.current_stream(device), int(use_graph)))
-        return from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W)
+        return self._recorded(from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W), rec, shape)
 
     @torch.no_grad()
     def sample(self, batch_size=16, design_fn=None, design_guidance="standard", num_boundaries=1,
                return_all_timesteps=False, **kw):
-        """:960-963 (``sampling_timesteps < timesteps``: ddim_sample)."""
+        """:960-963 (``sampling_timesteps < timesteps``: ddim_sample).  ``kw``: the build-only keywords of p_sample_loop /
+        ddim_sample, ``return_trajectory_every=`` / ``trajectory=`` among them."""
         S = self.image_size
         shape = (batch_size, num_boundaries, self.channels, S, S)
         if self.is_ddim_sampling:

@@ -131,9 +131,17 @@ def all_gather_designs(local, total, group=None, use_library=None):
     return res.to(local.device) if via_host else res
 
 
+def _no_trajectory(sample_kw):
+    """The sharded helpers gather ONE tensor: a chain record (``return_trajectory_every=``) is refused, not dropped."""
+    if "return_trajectory_every" in sample_kw or "trajectory" in sample_kw:
+        raise ValueError("the sharded helpers do not gather chain records: their all-gather moves one tensor.  Call the diffusion's "
+                         "own sample method on each rank for return_trajectory_every=")
+
+
 def sample_sharded(diffusion, batch_size, *, seed, group=None, gather=True, cond=None, **sample_kw):
     """``diffusion.sample(batch_size=...)`` with the batch partitioned over the process group.
     ``cond`` (if given) is the GLOBAL [batch_size, ...] tensor; each rank takes its slice."""
+    _no_trajectory(sample_kw)
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)
     else:
@@ -144,8 +152,11 @@ def sample_sharded(diffusion, batch_size, *, seed, group=None, gather=True, cond
     return all_gather_designs(local, batch_size, group) if gather else local
 
 
-def sample_multibodies_sharded(diffusion, cond, N, L, n_bodies, *, seed, group=None, gather=True):
+def sample_multibodies_sharded(diffusion, cond, N, L, n_bodies, *, seed, group=None, gather=True, **sample_kw):
     """Sharded ``sample_compose_multibodies`` (BASELINE config 4: batch 1024 over 8 GPUs)."""
+    _no_trajectory(sample_kw)
+    if sample_kw:
+        raise TypeError(f"sample_multibodies_sharded() got unexpected keyword arguments {sorted(sample_kw)}")
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)
     else:
@@ -160,6 +171,7 @@ def sample2d_sharded(diffusion, batch_size, *, seed, num_boundaries=1, group=Non
     """2-D ``GaussianDiffusion.sample(batch_size=..., num_boundaries=...)`` with the DESIGNS partitioned over the
     process group (the boundary copies of a design stay on one rank: they share noise and predicted states).
     Returns [batch_size, num_boundaries, C, H, W] on every rank."""
+    _no_trajectory(sample_kw)
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)
     else:

@@ -405,6 +405,29 @@ int  cindm_ddpm1d_last_step_info(const cindm_ddpm1d* h, int32_t* launches, int32
  * info[2] = chains in flight on the device when it started, itself included.  No reference counterpart. */
 int  cindm_ddpm1d_last_chain_info(const cindm_ddpm1d* h, int32_t info[4]);
 
+/* The chain recorder: every `every`-th state of a sampling chain, copied by one more kernel of the captured step
+ * (chain_record_kernel).  No reference counterpart (its scripts collect per-step lists from inside their Python loops).
+ * cindm_ddpm1d_set_recorder arms the NEXT chain call on this handle; that call consumes the recorder whether it succeeds or fails,
+ * and buf == NULL disarms.  A chain runs n steps i = 0 .. n-1 (DDPM: n = t_start - t_end + 1, step i is timestep t_start - i; DDIM:
+ * n = n_steps, step i is times[i]; a guided step with relaxation iterations is ONE step).  The state after step i is recorded iff
+ * (i + 1) % every == 0 or i == n - 1: ceil(n / every) records, the last one is the chain's result.
+ * streams: bit 0 = x, the state the step leaves behind; bit 1 = x0, the x_start the step predicted, clamped as its update used it
+ * (a guided step: that of its last iteration).  Any other bit, every < 1 or an unaligned buffer is refused here.
+ * buf: DEVICE memory, 16-byte aligned, buf_floats floats, laid out as [records][streams, x before x0][floats per record], followed
+ * by ONE more record when x0 is on (the update kernel stages its x_start there).  A record is the chain's state in the library's
+ * own layout: [B, L_tot, F] for the 1-D entries, [B * nb, H * W, padded channels] for the 2-D entries.  The chain call refuses a
+ * buffer that is too small for it, or a state x that is not 16-byte aligned, before it launches or copies anything (x is untouched).
+ * An every above the chain's step count records what every == steps records: the result alone.  Record offsets are 64-bit.
+ * Served by cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided and cindm_ddpm2d_sample / _sample_ddim /
+ * _sample_force / _sample_ddim_force (x0: not by the two 2-D DDIM entries, whose update kernels have no x0 operand); refused by
+ * cindm_ddpm1d_sample_autoregress and _sample_ula.  A chain that is re-run on the exchange-free plan records again from record 0.
+ * With no recorder armed a chain launches exactly what it launched before this entry existed; with one, one launch more per step
+ * (and a plain 1-D step runs compose_update_kernel instead of the update fused into the U-Net's last kernel when x0 is on).
+ * cindm_ddpm1d_recorder_info: info[0] = records the last chain call wrote (0: it had no recorder, or failed), info[1] = floats
+ * per record, info[2] = steps run, info[3] = streams. */
+int  cindm_ddpm1d_set_recorder(cindm_ddpm1d* h, float* buf, int64_t buf_floats, int32_t every, int32_t streams);
+int  cindm_ddpm1d_recorder_info(const cindm_ddpm1d* h, int32_t info[4]);
+
 /* ===================================================================== 2-D airfoil path
  * Replaces Unet.forward (model/diffusion_2d.py:369-408) and GaussianDiffusion.p_sample /
  * p_sample_loop (model/diffusion_2d.py:788-907) of the reference for the sampling path
