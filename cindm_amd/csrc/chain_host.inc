@@ -5,6 +5,7 @@
 //   graph_capture/_run  capture a step functor into an instantiated graph; launch it n times and synchronise
 //   replay_once         the 2-D chains' replay: stream_steps, or capture + run + destroy (no cache)
 //   upload_ddim_tables  schedule check + the DDIM loops' per-step device tables
+//   DesignTablesScope   the waypoint objective's tables: taken by every chain entry, run by the two guided ones (bottom of this file)
 // The 1-D replay (replay_steps in cindm_hip.hip: graph cached in the handle by key, ping-pong pair + odd tail, flag polls) is built
 // on the same two graph functions.
 
@@ -186,5 +187,60 @@ extern "C" int cindm_ddpm1d_set_recorder(cindm_ddpm1d* h, float* buf, int64_t bu
 extern "C" int cindm_ddpm1d_recorder_info(const cindm_ddpm1d* h, int32_t info[4]) {
     REQUIRE(h && info, "null argument");
     for (int i = 0; i < 4; ++i) info[i] = h->rec_info[i];
+    return 0;
+}
+
+// ---- the waypoint objective's tables (DESIGN 4.5m) -------------------------------------------------------------------------------------
+// cindm_ddpm1d_set_design_tables arms the handle; like the recorder, the next chain entry takes the tables with DesignTablesScope --
+// so the call consumes them however it ends -- and either refuses them (dzt_refuse: every chain that is not guided) or checks them
+// against its descriptor and state (dzt_begin) and runs with them: run_step reads h->dzt for the whole call, the re-run included.
+struct DesignTablesScope {
+    cindm_ddpm1d* h; DesignTables t;
+    explicit DesignTablesScope(cindm_ddpm1d* h_) : h(h_) {
+        if (!h) return;
+        t = h->dzt_armed; h->dzt_armed = DesignTables();
+    }
+    ~DesignTablesScope() { if (h) h->dzt = nullptr; }
+    bool on() const { return t.target != nullptr; }
+};
+
+static int dzt_refuse(const DesignTablesScope& ts) {
+    REQUIRE(!ts.on(), "design tables: only the guided chains (cindm_ddpm1d_sample_guided / _sample_ddim_guided) read them; the tables were dropped");
+    return 0;
+}
+
+static int dzt_begin(DesignTablesScope& ts, const cindm_design_desc* dz, int Ltot, int n_bodies, int64_t B) {
+    const DesignTables& t = ts.t;
+    if (dz->mode != 3 && dz->mode != 4) {
+        REQUIRE(!ts.on(), "design tables are armed but the descriptor's mode is 1 / 2 (the point objective, which reads none); the tables were dropped");
+        return 0;
+    }
+    REQUIRE(ts.on(), "design objective mode 3 / 4 reads its target and scale from tables: arm them with cindm_ddpm1d_set_design_tables "
+                     "before the chain call");
+    if (t.rows != Ltot)
+        return fail("design tables: " + std::to_string(t.rows) + " rows, the state has " + std::to_string(Ltot));
+    if (t.n_bodies != n_bodies)
+        return fail("design tables: " + std::to_string(t.n_bodies) + " bodies, the composition has " + std::to_string(n_bodies));
+    if (t.batch != B)
+        return fail("design tables: made for a batch of " + std::to_string(t.batch) + ", the chain runs " + std::to_string(B));
+    REQUIRE((((uintptr_t)t.target | (uintptr_t)t.scale) & 15) == 0, "design tables: target and scale must be 16-byte aligned");
+    ts.h->dzt = &ts.t;
+    return 0;
+}
+
+static void dzt_key(KeyBuilder& K, const cindm_ddpm1d* h) {
+    if (h->dzt) K(h->dzt->target)(h->dzt->scale)(h->dzt->target_per_design)(h->dzt->scale_per_design);
+}
+
+extern "C" int cindm_ddpm1d_set_design_tables(cindm_ddpm1d* h, const float* target, int32_t target_per_design, const float* scale,
+                                              int32_t scale_per_design, int32_t rows, int32_t n_bodies, int64_t batch) {
+    if (h) h->dzt_armed = DesignTables();      // (a refused call leaves the handle disarmed)
+    REQUIRE(h, "null handle");
+    if (!target && !scale) return 0;
+    REQUIRE(target && scale, "design tables: target and scale come together (NULL, NULL disarms)");
+    REQUIRE(rows >= 1 && n_bodies >= 1 && batch >= 1, "design tables: rows, n_bodies and batch must be >= 1");
+    DesignTables& t = h->dzt_armed;
+    t.target = target; t.scale = scale; t.target_per_design = target_per_design ? 1 : 0; t.scale_per_design = scale_per_design ? 1 : 0;
+    t.rows = rows; t.n_bodies = n_bodies; t.batch = batch;
     return 0;
 }

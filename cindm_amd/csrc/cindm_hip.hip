@@ -2024,6 +2024,12 @@ struct RecSpec {
     int n = 0; int64_t fpr = 0; float* x0_stage = nullptr;
 };
 
+// The waypoint objective's device tables as armed by the caller (cindm_ddpm1d_set_design_tables, chain_host.inc)
+struct DesignTables {
+    const float* target = nullptr; const float* scale = nullptr; int target_per_design = 0, scale_per_design = 0;
+    int rows = 0, n_bodies = 0; int64_t batch = 0;
+};
+
 struct cindm_ddpm1d {
     int T = 0;
     float* tab = nullptr;        // 13 tables, each [T]
@@ -2038,6 +2044,8 @@ struct cindm_ddpm1d {
     // the chain recorder (cindm_ddpm1d_set_recorder, chain_host.inc): what the next chain call will take, the one a running chain
     // records with (null: none) and what the last chain wrote (cindm_ddpm1d_recorder_info)
     RecSpec rec_armed; const RecSpec* rec = nullptr; int rec_info[4] = {0, 0, 0, 0};
+    // the design tables: what the next chain call will take, and the ones a running guided chain reads (null: none)
+    DesignTables dzt_armed; const DesignTables* dzt = nullptr;
     void drop_graph() {
         if (gexec) (void)hipGraphExecDestroy(gexec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -2247,8 +2255,14 @@ static int run_step(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, c
     }
     const bool guided = io.dz && io.x_out;
     if (guided) {
-        a.dz_mode = io.dz->mode; a.dz_alpha = io.dz->alpha; a.dz_last_n = io.dz->last_n_step; a.dz_coef = io.dz->coef;
-        a.dz_tc = io.dz->time_consistency_coef; a.dz_tx = io.dz->pos_target[0]; a.dz_ty = io.dz->pos_target[1];
+        a.dz_mode = io.dz->mode; a.dz_alpha = io.dz->alpha; a.dz_tc = io.dz->time_consistency_coef;
+        if (io.dz->mode >= 3) {     // table objective: the addresses and the per-design flags are operands of the captured update
+            REQUIRE(h->dzt, "design objective mode 3 / 4 outside a chain that took design tables (internal error)");
+            a.dz_target = h->dzt->target; a.dz_scale = h->dzt->scale;
+            a.dz_mode |= (h->dzt->target_per_design ? kDzTargetPerDesign : 0) | (h->dzt->scale_per_design ? kDzScalePerDesign : 0);
+        } else {
+            a.dz_last_n = io.dz->last_n_step; a.dz_coef = io.dz->coef; a.dz_tx = io.dz->pos_target[0]; a.dz_ty = io.dz->pos_target[1];
+        }
         a.relax = io.relax; a.recur_noise = io.recur_noise; a.recur_t_stride = io.recur_t_stride; a.recur_tag = io.recur_tag;
         a.iso = io.iso; a.iso_steps = io.iso_steps;
         a.betas = tb; a.ac = tb + 1 * T; a.acp = tb + 2 * T;
@@ -2563,6 +2577,8 @@ extern "C" int cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_un
                                    int32_t t_start, int32_t t_end, int64_t B, void* ws, size_t ws_bytes, void* stream_,
                                    int32_t use_graph) {
     RecScope rs(h);
+    DesignTablesScope ts(h);
+    if (dzt_refuse(ts) != 0) return -1;
     REQUIRE(h && pair && c && x, "null argument");
     REQUIRE(t_start < h->T && t_end >= 0 && t_end <= t_start, "bad timestep range");
     if (rec_begin(rs, x, t_start - t_end + 1, state_floats(pair, c, B)) != 0) return -1;
@@ -2581,6 +2597,8 @@ extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cin
                                         const float* inpaint_cond, int32_t inpaint_steps, const float* inpaint_noise_steps,
                                         int64_t B, void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(h);
+    DesignTablesScope ts(h);
+    if (dzt_refuse(ts) != 0) return -1;
     REQUIRE(h && pair && c && x && times && coefs, "null argument");
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     if (rec_begin(rs, x, n_steps, state_floats(pair, c, B)) != 0) return -1;
@@ -2609,6 +2627,8 @@ extern "C" int cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pa
                                                const float* init_tape, const float* noise_steps, int64_t sample_offset, int64_t B,
                                                void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(h);
+    DesignTablesScope ts(h);
+    if (dzt_refuse(ts) != 0) return -1;
     REQUIRE(!rs.on(), "recorder: the autoregressive rollout is not recorded (its step index is (segment, step)); the recorder was dropped");
     REQUIRE(h && pair && c && x && cond && cond_buf && out && times && coefs && seeds, "null argument");
     REQUIRE(c->mode == CINDM_COMPOSE_PLAIN || c->mode == CINDM_COMPOSE_MULTIBODY, "the rollout runs the plain (or multibody) prediction");
@@ -2662,6 +2682,8 @@ extern "C" int cindm_ddpm1d_sample_ula(cindm_ddpm1d* h, cindm_unet1d* pair, cind
                                        const float* noise_tape, uint64_t seed, int64_t sample_offset, int64_t B,
                                        void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(h);
+    DesignTablesScope ts(h);
+    if (dzt_refuse(ts) != 0) return -1;
     REQUIRE(!rs.on(), "recorder: the Langevin chain is not recorded (its step index is (timestep, inner iteration)); the recorder was dropped");
     REQUIRE(h && pair && c && x && scalar && step_size && noise_std && tab, "null argument");
     REQUIRE(c->mode == CINDM_COMPOSE_MULTIBODY && uncond, "the Langevin phase runs the multibody composition (pair + unconditioned model)");
@@ -2698,12 +2720,14 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
                                           int32_t t_start, int32_t t_end, int64_t B, void* ws, size_t ws_bytes, void* stream_,
                                           int32_t use_graph) {
     RecScope rs(h);
+    DesignTablesScope ts(h);
     REQUIRE(h && pair && c && dz && x, "null argument");
     REQUIRE(t_start < h->T && t_end >= 0 && t_end <= t_start, "bad timestep range");
-    REQUIRE(dz->mode == 1 || dz->mode == 2, "design objective mode must be 1 (L2) or 2 (L2square)");
+    REQUIRE(dz->mode >= 1 && dz->mode <= 4, "design objective mode must be 1 (L2), 2 (L2square), 3 (table L2) or 4 (table L2square)");
     REQUIRE(dz->recurrence >= 0 && dz->recurrence <= 64, "recurrence count out of range");
     const int Ltot = state_len(pair, c);
-    REQUIRE(dz->last_n_step >= 1 && dz->last_n_step <= Ltot, "last_n_step out of range");
+    if (dzt_begin(ts, dz, Ltot, c->n_bodies, B) != 0) return -1;
+    REQUIRE(dz->mode >= 3 || (dz->last_n_step >= 1 && dz->last_n_step <= Ltot), "last_n_step out of range");
     REQUIRE(!initial_state_overwrite || (overwrite_steps >= 1 && overwrite_steps <= Ltot), "bad overwrite_steps");
     if (rec_begin(rs, x, t_start - t_end + 1, state_floats(pair, c, B)) != 0) return -1;
     hipStream_t stream = nullptr;
@@ -2739,6 +2763,7 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
         KeyBuilder K;
         key_common(K, 2, pair, uncond, c, io, B, ws, ws_bytes);
         K(*dz)(recur_noise_steps)(R);
+        dzt_key(K, h);
         return replay_steps(h, K.k, stream, t_start - t_end + 1, use_graph, step, pair, ch.un());
     }));
 }
@@ -2759,12 +2784,14 @@ extern "C" int cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pa
                                                const float* initial_state_overwrite, int32_t overwrite_steps, int64_t B,
                                                void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(h);
+    DesignTablesScope ts(h);
     REQUIRE(h && pair && c && dz && x && times && coefs, "null argument");
-    REQUIRE(dz->mode == 1 || dz->mode == 2, "design objective mode must be 1 (L2) or 2 (L2square)");
+    REQUIRE(dz->mode >= 1 && dz->mode <= 4, "design objective mode must be 1 (L2), 2 (L2square), 3 (table L2) or 4 (table L2square)");
     REQUIRE(dz->recurrence >= 1 && dz->recurrence <= 64,
             "guided DDIM needs a recurrence count in 1 .. 64 (without recurrence the reference returns no noise prediction)");
     const int Ltot = state_len(pair, c);
-    REQUIRE(dz->last_n_step >= 1 && dz->last_n_step <= Ltot, "last_n_step out of range");
+    if (dzt_begin(ts, dz, Ltot, c->n_bodies, B) != 0) return -1;
+    REQUIRE(dz->mode >= 3 || (dz->last_n_step >= 1 && dz->last_n_step <= Ltot), "last_n_step out of range");
     REQUIRE(!initial_state_overwrite || (overwrite_steps >= 1 && overwrite_steps <= Ltot), "bad overwrite_steps");
     REQUIRE(!inpaint_cond || (inpaint_steps >= 1 && inpaint_steps <= Ltot), "bad inpaint_steps");
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
@@ -2804,6 +2831,7 @@ extern "C" int cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pa
         KeyBuilder K;
         key_common(K, 4, pair, uncond, c, io, B, ws, ws_bytes);
         K(*dz)(recur_noise_steps)(R);
+        dzt_key(K, h);
         const int rc = replay_steps(h, K.k, stream, n_steps, use_graph, step, pair, ch.un(), true);
         if (rc == 0 && (((int64_t)n_steps * R) & 1)) {        // the last iteration wrote the workspace buffer
             HIPCHK(hipMemcpyAsync(x, x2, (size_t)n_state * sizeof(float), hipMemcpyDeviceToDevice, stream));

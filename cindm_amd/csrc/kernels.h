@@ -23,6 +23,7 @@
 // so that no separate normalisation pass over HBM exists.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <type_traits>
 
@@ -2548,9 +2549,16 @@ struct ComposeArgs {
     int* sidx_next;                     // ping-pong DDIM loop: the other slot's step index (written with t_next by the step's update)
     // built-in design objective (the paper's point objective, inference/inverse_design_diffusion_1d.py:211-229) with
     // "standard" / "standard-alpha" (-recurrence-N) guidance: pred = mean - [eta_t] * grad_x objective(x)
-    int dz_mode;                 // 0 off, 1 "L2", 2 "L2square"
+    // The waypoint objective (modes 3 / 4) reads a target per (design | all designs, row, body) and a non-negative scale per
+    // (design | all designs, row, body) from device tables instead; their addresses share the storage of the point objective's
+    // scalars, so the struct -- which sits by value in the kernarg of ups_last_kernel and its fused forms -- keeps its size.
+    int dz_mode;                 // 0 off; bits 0-2: 1 "L2", 2 "L2square" (point), 3 "L2", 4 "L2square" (tables); kDzTargetPerDesign, kDzScalePerDesign
     int dz_alpha;                // 1: scale the gradient by eta_t = beta_t / sqrt(alphas_cumprod_prev_t) (standard-alpha)
-    int dz_last_n; float dz_coef, dz_tc, dz_tx, dz_ty;
+    union {
+        struct { int dz_last_n; float dz_coef, dz_tx, dz_ty; };              // modes 1, 2
+        struct { const float* dz_target; const float* dz_scale; };           // modes 3, 4: [B | 1, Ltot, nb, 2] and [B | 1, Ltot, nb]
+    };
+    float dz_tc;
     int relax;                   // this launch is a relaxation iteration (:1365-1367): x <- a_t pred + b_t z' (guided DDIM: and the step state stays)
     const float* recur_noise;    // explicit z' of this iteration (+ t * recur_t_stride), or null (counter-based, tag below)
     int64_t recur_t_stride; uint32_t recur_tag;
@@ -2562,6 +2570,8 @@ struct ComposeArgs {
     int* t_next;                                         // null: off
     const int* ep_cur0; int* ep_next0; const int* ep_cur1; int* ep_next1;     // exchange epochs of the U-Nets the next step runs (or null)
 };
+constexpr int kDzModeMask = 7, kDzTargetPerDesign = 0x100, kDzScalePerDesign = 0x200;
+static_assert(offsetof(ComposeArgs, recur_noise) - offsetof(ComposeArgs, dz_mode) == 32, "the design objective's fields must not grow ComposeArgs");
 __device__ __forceinline__ void compose_advance(const ComposeArgs& a, int t) {
     if (!a.t_next) return;
     if (a.ddim_tab && a.relax) { a.t_next[0] = t; a.sidx_next[0] = a.step_idx[0]; }      // guided DDIM: a relaxation iteration stays on its step
@@ -3625,8 +3635,23 @@ __device__ void compose_update_element(const ComposeArgs& a, int64_t i) {
         // guided update with the built-in objective (x_out never aliases x here: the gradient reads neighbours).  With ddim_tab set
         // too this is the guided DDIM loop: relaxation iterations as below, the last iteration is the DDIM update on (eps + g, x0).
         float g = 0.f;
+        const int dzm = a.dz_mode & kDzModeMask;
         if (comp < 2) {
-            if (lx >= a.Ltot - a.dz_last_n) {
+            if (dzm >= 3) {
+                // table objective: the point branch's expressions with the scale and the target read per (design | all, row, body)
+                const int64_t bs = (a.dz_mode & kDzScalePerDesign) ? b : 0, bt = (a.dz_mode & kDzTargetPerDesign) ? b : 0;
+                const float s = a.dz_scale[(bs * a.Ltot + lx) * a.nb + body];
+                if (s != 0.f) {
+                    const float* tp = a.dz_target + ((bt * a.Ltot + lx) * a.nb + body) * 2;
+                    const float d = xv - tp[comp];
+                    if (dzm == 3) {
+                        const float dother = a.x[i ^ 1] - tp[comp ^ 1];
+                        g = s * d / sqrtf(d * d + dother * dother);
+                    } else {
+                        g = s * 2.0f * d;
+                    }
+                }
+            } else if (lx >= a.Ltot - a.dz_last_n) {
                 const float d = xv - (comp == 0 ? a.dz_tx : a.dz_ty);
                 const float scale = a.dz_coef / (float)a.dz_last_n;
                 if (a.dz_mode == 1) {

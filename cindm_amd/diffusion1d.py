@@ -10,7 +10,7 @@ What runs where
     between two library calls per step, exactly where the reference takes it.
   * DDIM (``sampling_timesteps < timesteps``, ``ddim_sample`` :1724-1804): unguided = ONE library call
     (``cindm_ddpm1d_sample_ddim``, same captured-step replay with per-step coefficient tables); guided by a ``PointObjective``
-    ("standard" / "standard-alpha" with ``-recurrence-N``) = ONE library call too (``cindm_ddpm1d_sample_ddim_guided``: relaxation
+    or a ``WaypointObjective`` ("standard" / "standard-alpha" with ``-recurrence-N``) = ONE library call too (``cindm_ddpm1d_sample_ddim_guided``: relaxation
     iterations and the DDIM update of (eps + grad, x_start) inside the captured step, state and step state ping-ponged); guided by
     any other callable or guidance (recurrence guidance) = library predictions + the user's gradient per step.
   * autoregressive time composition (``autoregress_time_compose_sample`` :2240-2327): the whole rollout -- every segment's
@@ -29,7 +29,7 @@ import torch
 from torch import nn
 
 from . import _ffi
-from .objectives import PointObjective
+from .objectives import PointObjective, WaypointObjective
 from .record import DeviceRecorder, LoopRecorder
 from .schedule import ddim_schedule, make_schedule, ula_schedule
 
@@ -271,6 +271,25 @@ class GaussianDiffusion1D(nn.Module):
         included -- arms it again."""
         if rec is not None:
             rec.arm(h)
+
+    @staticmethod
+    def _arm_tables(obj, h, img):
+        """A WaypointObjective's tables, armed like the recorder: the guided chain call consumes them, so every issue arms again."""
+        if obj is not None:
+            obj.arm(h, img.shape[0], img.device)
+
+    @staticmethod
+    def _builtin(design_fn, design_guidance, B, L, n_bodies):
+        """(descriptor, tables) when ``design_fn`` under ``design_guidance`` runs inside the captured step -- a PointObjective whose
+        last_n_step fits the state, or a WaypointObjective -- else (None, None).  A WaypointObjective whose tables do not fit the
+        state [B, L, 4 * n_bodies] is a ValueError on every route, before any device work."""
+        if isinstance(design_fn, WaypointObjective):
+            design_fn.check_state(B, L, n_bodies)
+            dz = design_fn.descriptor(design_guidance)
+            return dz, (design_fn if dz is not None else None)
+        if isinstance(design_fn, PointObjective) and design_fn.last_n_step <= L:
+            return design_fn.descriptor(design_guidance), None
+        return None, None
 
     def _recorded(self, out, rec):
         """What a sampling call returns: the designs, or (designs, ChainRecord) when it recorded."""
@@ -525,9 +544,10 @@ class GaussianDiffusion1D(nn.Module):
 
     @torch.no_grad()
     def _run_guided_loop(self, img, cond, desc, dz, t_start, t_end, *, noise, seed, sample_offset, inpaint_cond,
-                         initial_state_overwrite, use_graph=True, rec=None):
+                         initial_state_overwrite, use_graph=True, rec=None, tables=None):
         """Reverse steps t_start .. t_end guided by the built-in objective as one library call
-        (cindm_ddpm1d_sample_guided); ``noise`` rows (step / recur / cond) are indexed by t."""
+        (cindm_ddpm1d_sample_guided); ``noise`` rows (step / recur / cond) are indexed by t.  ``tables``: the WaypointObjective
+        whose descriptor ``dz`` is (modes 3 / 4): every issue of the call arms its tables."""
         device, B = img.device, img.shape[0]
         cond_d = self._f32(cond, device) if (cond is not None and self.conditioned_steps != 0) else None
         inp = self._f32(inpaint_cond, device)
@@ -535,6 +555,7 @@ class GaussianDiffusion1D(nn.Module):
 
         def call(h, un, ws):
             self._arm(rec, h)
+            self._arm_tables(tables, h, img)
             with torch.cuda.device(device):
                 _ffi.check(_ffi.lib().cindm_ddpm1d_sample_guided(
                     h, self.model._h, un, C.byref(desc), C.byref(dz), _ffi.ptr(img), _ffi.ptr(cond_d),
@@ -546,9 +567,10 @@ class GaussianDiffusion1D(nn.Module):
 
     @torch.no_grad()
     def _run_guided_ddim(self, img, cond, desc, dz, times, coefs, *, noise, seed, sample_offset, inpaint_cond,
-                         initial_state_overwrite, use_graph=True, rec=None):
+                         initial_state_overwrite, use_graph=True, rec=None, tables=None):
         """DDIM steps ``times[0] .. times[-2]`` guided by the built-in objective as one library call
-        (cindm_ddpm1d_sample_ddim_guided); ``noise`` rows (step / recur / cond) are indexed by the position in ``times``."""
+        (cindm_ddpm1d_sample_ddim_guided); ``noise`` rows (step / recur / cond) are indexed by the position in ``times``.
+        ``tables``: as _run_guided_loop."""
         device, B = img.device, img.shape[0]
         S = len(times) - 1
         cond_d = self._f32(cond, device) if (cond is not None and self.conditioned_steps != 0) else None
@@ -559,6 +581,7 @@ class GaussianDiffusion1D(nn.Module):
 
         def call(h, un, ws):
             self._arm(rec, h)
+            self._arm_tables(tables, h, img)
             with torch.cuda.device(device):
                 _ffi.check(_ffi.lib().cindm_ddpm1d_sample_ddim_guided(
                     h, self.model._h, un, C.byref(desc), C.byref(dz), _ffi.ptr(img), _ffi.ptr(cond_d), S, tarr, _ffi.ptr(carr),
@@ -601,6 +624,7 @@ class GaussianDiffusion1D(nn.Module):
         B, T1 = shape[0], shape[1]
         full = (B, T1 + n_composed * compose_start_step, compose_n_bodies * 4)
         assert compose_start_step < T1
+        dz, tables = self._builtin(design_fn, design_guidance, B, full[1], compose_n_bodies)
         init = self._init_state(full, device, noise, seed, sample_offset, self.num_timesteps)
         if initialization_mode == 0:
             img = init
@@ -612,17 +636,16 @@ class GaussianDiffusion1D(nn.Module):
         desc = self._desc_for(full, compose_mode, n_composed, compose_start_step, T1, compose_n_bodies, outside=not inside)
         inpaint = cond if (self.conditioned_steps == 0 and cond is not None) else None
         fast = design_fn is None and "recurrence" not in design_guidance and initial_state_overwrite is None
-        dz = design_fn.descriptor(design_guidance) if isinstance(design_fn, PointObjective) else None
         t_first, n_steps = self.num_timesteps - 1, self.num_timesteps - int(t_stop)
         # (the device record buffer is allocated only on the routes that are library chains)
         device_rec = lambda: self._recorder(return_trajectory_every, trajectory, n_steps, full, device, t_start=t_first)
-        if dz is not None and design_fn.last_n_step <= full[1]:
+        if dz is not None:
             # built-in objective: the guided loop (gradient, overwrite, relaxations) stays inside the captured step
             rec = device_rec()
             return self._recorded(self._run_guided_loop(img, cond, desc, dz, t_first, t_stop, noise=noise, seed=seed,
                                                         sample_offset=sample_offset, inpaint_cond=inpaint,
                                                         initial_state_overwrite=initial_state_overwrite, use_graph=use_graph,
-                                                        rec=rec), rec)
+                                                        rec=rec, tables=tables), rec)
         if fast:
             rec = device_rec()
             return self._recorded(self._run_loop(img, cond, desc, t_first, t_stop,
@@ -824,7 +847,7 @@ class GaussianDiffusion1D(nn.Module):
         Without ``design_fn`` the whole loop is one library call (``cindm_ddpm1d_sample_ddim``); as in the reference the
         prediction then ignores the compose keywords (:1755).  With ``design_fn`` (recurrence guidance only -- the
         reference's non-recurrence branch does not return a noise prediction, :1283) the prediction honours them.  A
-        ``PointObjective`` under "standard" / "standard-alpha" ``-recurrence-N`` (N >= 1, last_n_step <= L) runs as one library
+        ``PointObjective`` (last_n_step <= L) or ``WaypointObjective`` under "standard" / "standard-alpha" ``-recurrence-N`` (N >= 1) runs as one library
         chain (``cindm_ddpm1d_sample_ddim_guided``; counter-based draws keyed by (seed, sample_offset + b, t, element) when there
         is no tape); any other callable or guidance: each step is ``recurrence`` library predictions + the user's autograd
         gradient, and the DDIM update of the tiny state runs in torch.
@@ -838,6 +861,7 @@ class GaussianDiffusion1D(nn.Module):
         if noise is not None:
             noise = noise.to(device)
         B = shape[0]
+        dz, tables = self._builtin(design_fn, design_guidance, B, shape[1], compose_n_bodies)
         if init_img is not None:
             img = self._f32(init_img, device).clone()
         else:
@@ -874,14 +898,13 @@ class GaussianDiffusion1D(nn.Module):
         n_composed = 0 if n_composed is None else n_composed
         desc = self._desc_for(shape, compose_mode, n_composed, compose_start_step, shape[1], compose_n_bodies,
                               clip=True)     # p_sample_compose_inside's own default: clip_denoised is not forwarded (:1758-1770)
-        dz = design_fn.descriptor(design_guidance) if isinstance(design_fn, PointObjective) else None
-        if dz is not None and dz.recurrence >= 1 and design_fn.last_n_step <= shape[1]:
+        if dz is not None and dz.recurrence >= 1:
             # built-in objective: relaxations, gradient, overwrite and the DDIM update stay inside the captured step
             rec = self._recorder(return_trajectory_every, trajectory, S, tuple(img.shape), device, times=times)
             return self._recorded(self._run_guided_ddim(img, cond, desc, dz, times, coefs, noise=noise, seed=seed,
                                                         sample_offset=sample_offset, inpaint_cond=inpaint,
                                                         initial_state_overwrite=initial_state_overwrite, use_graph=use_graph,
-                                                        rec=rec), rec)
+                                                        rec=rec, tables=tables), rec)
         coefs = coefs.to(device)
         img_T = img
         # this route loops in Python: the same record, cloned per step

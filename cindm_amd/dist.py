@@ -148,6 +148,9 @@ def sample_sharded(diffusion, batch_size, *, seed, group=None, gather=True, cond
         rank, world = 0, 1
     lo, hi = shard_bounds(batch_size, rank, world)
     local_cond = None if cond is None else cond[lo:hi]
+    design_fn = sample_kw.get("design_fn")
+    if hasattr(design_fn, "shard"):        # an objective with per-design tables (WaypointObjective): each rank takes its slice
+        sample_kw = dict(sample_kw, design_fn=design_fn.shard(lo, hi))
     local = diffusion.sample(batch_size=hi - lo, cond=local_cond, seed=seed, sample_offset=lo, **sample_kw)
     return all_gather_designs(local, batch_size, group) if gather else local
 

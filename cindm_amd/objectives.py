@@ -7,7 +7,15 @@ path; in addition ``GaussianDiffusion1D`` recognises it and, for "standard" / "s
 without ``-recurrence-N``), evaluates its closed-form gradient inside the library's update kernel so that the whole
 guided reverse loop stays one captured-graph replay (``cindm_ddpm1d_sample_guided``) -- no autograd, no host code in
 the loop.  With ``sampling_timesteps < timesteps`` and a ``-recurrence-N`` guidance (N >= 1) the guided DDIM loop is one
-library chain in the same way (``cindm_ddpm1d_sample_ddim_guided``)."""
+library chain in the same way (``cindm_ddpm1d_sample_ddim_guided``).
+
+``WaypointObjective`` is the table form of the same two norms: a target per (design | all designs, row, body) and a non-negative
+weight per (design | all designs, row, body).  It covers what the point objective cannot say -- a target per body, a waypoint at an
+intermediate row, a sweep of targets and coefficients over the designs of one batch (the reference script loops over such a sweep
+call by call, :283-315) -- and takes the same two library chains: the update kernel reads the two tables from device memory
+(``cindm_ddpm1d_set_design_tables``, descriptor modes 3 / 4)."""
+import copy
+
 import torch
 
 from . import _ffi
@@ -59,3 +67,170 @@ class PointObjective:
         d.coef, d.time_consistency_coef = self.coef, self.time_consistency_coef
         d.pos_target[0], d.pos_target[1] = float(self.pos_target[0]), float(self.pos_target[1])
         return d
+
+
+class WaypointObjective:
+    """``target`` [L, nb, 2] or [B, L, nb, 2]: the position (features 4j, 4j+1) body j is drawn to at that row, in state units.
+    ``weight`` [L, nb] or [B, L, nb]: finite, >= 0; 0 = no waypoint at that (row, body).  The value for pos [B, L, 4*nb] is
+
+        sum_b sum_l sum_j scale[b, l, j] * ||pos[b, l, 4j:4j+2] - target[b, l, j]||_2          ("L2"; squared for "L2square")
+        + the time-consistency term of PointObjective
+
+    with scale = fp32(coef) * fp32(weight), formed once: ``__call__`` and the kernel read the same table.  An entry whose scale is 0
+    contributes exactly 0 to the value and to the gradient, also where pos == target."""
+
+    def __init__(self, target, weight, *, coef=1.0, time_consistency_coef=0.0, design_fn_mode="L2", _scale=None):
+        """``_scale``: a ready fp32 scale table in place of coef * weight (from_point's, formed by a division)."""
+        if design_fn_mode not in ("L2", "L2square"):
+            raise ValueError(design_fn_mode)
+        if _scale is None:
+            weight = torch.as_tensor(weight).detach().to("cpu", torch.float32)
+            if not bool(torch.isfinite(weight).all()) or bool((weight < 0).any()):
+                raise ValueError("weight must be finite and >= 0")
+            _scale = torch.tensor(float(coef), dtype=torch.float32) * weight
+        target = torch.as_tensor(target).detach().to("cpu", torch.float32).contiguous()
+        scale = torch.as_tensor(_scale).detach().to("cpu", torch.float32).contiguous()
+        if target.dim() not in (3, 4) or target.shape[-1] != 2:
+            raise ValueError(f"target must be [L, nb, 2] or [B, L, nb, 2], not {tuple(target.shape)}")
+        if scale.dim() not in (2, 3):
+            raise ValueError(f"weight must be [L, nb] or [B, L, nb], not {tuple(scale.shape)}")
+        if tuple(target.shape[-3:-1]) != tuple(scale.shape[-2:]) or 0 in target.shape or 0 in scale.shape:
+            raise ValueError(f"target {tuple(target.shape)} and weight {tuple(scale.shape)} disagree on (L, nb)")
+        if target.dim() == 4 and scale.dim() == 3 and target.shape[0] != scale.shape[0]:
+            raise ValueError(f"target is for {target.shape[0]} designs, weight for {scale.shape[0]}")
+        if not bool(torch.isfinite(target).all()):
+            raise ValueError("target must be finite")
+        if not bool(torch.isfinite(scale).all()) or bool((scale < 0).any()):
+            raise ValueError("coef * weight must be finite and >= 0")
+        self.target, self.scale = target, scale
+        self.time_consistency_coef, self.design_fn_mode = float(time_consistency_coef), design_fn_mode
+        self._dev = {}
+
+    @classmethod
+    def from_point(cls, pos_target, last_n_step, L, n_bodies, coef=100, time_consistency_coef=0, design_fn_mode="L2"):
+        """The table form of ``PointObjective(pos_target, last_n_step, coef=coef, ...)`` on a state of ``L`` rows and ``n_bodies``
+        bodies: scale = fp32(coef) / fp32(last_n_step) -- the one division the kernel's point branch does -- on the last n rows."""
+        n, L, nb = int(last_n_step), int(L), int(n_bodies)
+        if not 1 <= n <= L:
+            raise ValueError(f"last_n_step {n} outside 1 .. L = {L}")
+        pt = torch.as_tensor(pos_target, dtype=torch.float32).reshape(-1)
+        if pt.numel() != 2:
+            raise ValueError("pos_target is a 2-D position")
+        scale = torch.zeros((L, nb), dtype=torch.float32)
+        scale[L - n:] = torch.tensor(float(coef), dtype=torch.float32) / torch.tensor(float(n), dtype=torch.float32)
+        return cls(pt.expand(L, nb, 2), None, time_consistency_coef=time_consistency_coef, design_fn_mode=design_fn_mode, _scale=scale)
+
+    # ------------------------------------------------------------------ shapes
+    @property
+    def rows(self):
+        return self.scale.shape[-2]
+
+    @property
+    def n_bodies(self):
+        return self.scale.shape[-1]
+
+    @property
+    def per_design(self):
+        """Designs the per-design tables are for, or None when both tables are shared by every design."""
+        if self.target.dim() == 4:
+            return self.target.shape[0]
+        return self.scale.shape[0] if self.scale.dim() == 3 else None
+
+    def check_state(self, B, L, n_bodies):
+        """ValueError unless the tables fit a state [B, L, 4 * n_bodies]."""
+        if self.rows != L:
+            raise ValueError(f"WaypointObjective: tables of {self.rows} rows, the state has {L}")
+        if self.n_bodies != n_bodies:
+            raise ValueError(f"WaypointObjective: tables of {self.n_bodies} bodies, the state has {n_bodies}")
+        if self.per_design is not None and self.per_design != B:
+            raise ValueError(f"WaypointObjective: per-design tables for {self.per_design} designs, the batch has {B} "
+                             "(shard(lo, hi) slices them for a part of the batch)")
+
+    def shard(self, lo, hi):
+        """The objective of designs lo .. hi-1: per-design tables sliced, tables shared by every design passed through."""
+        o = copy.copy(self)
+        o.target = self.target[lo:hi].contiguous() if self.target.dim() == 4 else self.target
+        o.scale = self.scale[lo:hi].contiguous() if self.scale.dim() == 3 else self.scale
+        o._dev = {}
+        return o
+
+    def tables(self, device):
+        """(target, scale): the two contiguous fp32 tensors on ``device`` (cached per device) the kernel reads."""
+        device = torch.device(device)
+        if device not in self._dev:
+            self._dev[device] = (self.target.to(device).contiguous(), self.scale.to(device).contiguous())
+        return self._dev[device]
+
+    # ------------------------------------------------------------------ value and gradient
+    def _time_consistency(self, pos, n_bodies):
+        idx = torch.cat([torch.arange(ii * 4, ii * 4 + 2) for ii in range(n_bodies)]).to(pos.device)
+        return (pos[:, 1:, idx] - pos[:, :-1, idx]).square().sum(-1).mean(-1).sum() * self.time_consistency_coef
+
+    def __call__(self, pos):
+        """pos: [B, L, n_bodies*4] -> scalar loss (summed over the batch)."""
+        B, L, F = pos.shape
+        self.check_state(B, L, F // 4)
+        target, scale = self.target.to(pos), self.scale.to(pos)
+        on = scale > 0
+        sq = (pos.reshape(B, L, F // 4, 4)[..., :2] - target).square().sum(-1)
+        if self.design_fn_mode == "L2":
+            # (the square root only sees entries that count: its derivative at 0 is inf, and 0 * inf would reach the gradient)
+            sq = torch.sqrt(torch.where(on, sq, torch.ones_like(sq)))
+        total = torch.where(on, scale * sq, torch.zeros_like(sq)).sum()
+        if self.time_consistency_coef > 0:
+            total = total + self._time_consistency(pos, F // 4)
+        return total
+
+    def closed_form_grad(self, pos):
+        """The gradient of ``__call__`` as compose_update_element evaluates it, operation for operation (the kernel's table branch
+        followed by its time-consistency term): per position component, d = pos - target,
+            "L2": (s * d) / sqrt(d * d + d_other * d_other),   "L2square": (s * 2) * d,   skipped where s == 0,
+            + ((tc * 2) * lap) / (L - 1),  lap = (x_l - x_{l-1}) [l >= 1] - (x_{l+1} - x_l) [l + 1 < L]."""
+        B, L, F = pos.shape
+        self.check_state(B, L, F // 4)
+        target, scale = self.target.to(pos), self.scale.to(pos)
+        x = pos.reshape(B, L, F // 4, 4)[..., :2]
+        s = scale.unsqueeze(-1).expand(x.shape)
+        on = s != 0
+        d = x - target
+        if self.design_fn_mode == "L2":
+            dd = d * d
+            den = torch.sqrt(torch.where(on, dd + dd.flip(-1), torch.ones_like(dd)))
+            g = s * d / den
+        else:
+            g = s * 2.0 * d
+        g = torch.where(on, g, torch.zeros_like(g))
+        if self.time_consistency_coef > 0 and L > 1:
+            lap = torch.zeros_like(x)
+            lap[:, 1:] += x[:, 1:] - x[:, :-1]
+            lap[:, :-1] -= x[:, 1:] - x[:, :-1]
+            g = g + self.time_consistency_coef * 2.0 * lap / float(L - 1)
+        out = torch.zeros_like(pos).reshape(B, L, F // 4, 4)
+        out[..., :2] = g
+        return out.reshape(B, L, F)
+
+    def descriptor(self, design_guidance):
+        """cindm_design_desc (mode 3 / 4: the tables are armed per call) for this objective under ``design_guidance``, or None when
+        that guidance needs the generic (autograd) path."""
+        g = design_guidance
+        rec = 0
+        if "recurrence" in g:
+            rec = int(g.split("-")[-1])
+            g = g[:g.index("-recurrence")]
+            if rec < 1:
+                return None
+        if g not in ("standard", "standard-alpha"):
+            return None
+        d = _ffi.DesignDesc()
+        d.mode = 3 if self.design_fn_mode == "L2" else 4
+        d.alpha = int(g == "standard-alpha")
+        d.recurrence, d.time_consistency_coef = rec, self.time_consistency_coef
+        return d
+
+    def arm(self, handle, B, device):
+        """Arms the next guided chain call on ``handle`` (a cindm_ddpm1d) with this objective's tables, for a batch of ``B`` designs
+        (per-design tables declare their own extent: the chain call refuses another batch)."""
+        target, scale = self.tables(device)
+        batch = B if self.per_design is None else self.per_design
+        _ffi.check(_ffi.lib().cindm_ddpm1d_set_design_tables(handle, _ffi.ptr(target), int(target.dim() == 4), _ffi.ptr(scale),
+                                                            int(scale.dim() == 3), self.rows, self.n_bodies, batch))

@@ -262,9 +262,12 @@ int  cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* unco
  *   "L2":       coef * sum_bodies sum_b mean_{last n steps} || pos - target ||_2
  *   "L2square": coef * sum_bodies sum_b mean_{last n steps} || pos - target ||_2^2
  *   (+ time_consistency_coef * sum_b mean_l || pos[l+1] - pos[l] ||^2 over the position channels),
- * whose gradient with respect to the state is evaluated in closed form inside the update kernel. */
+ * whose gradient with respect to the state is evaluated in closed form inside the update kernel.
+ * Modes 3 / 4 are the waypoint objective, the same two norms read from device tables (cindm_ddpm1d_set_design_tables below):
+ *   sum_b sum_l sum_j scale[b | 0, l, j] * || pos[b, l, 4j : 4j+2] - target[b | 0, l, j] ||_2     (mode 4: ||.||_2^2)
+ *   (+ the time-consistency term); in these modes last_n_step, coef and pos_target are not read. */
 typedef struct {
-    int32_t mode;               /* 1 = "L2", 2 = "L2square" */
+    int32_t mode;               /* 1 = "L2", 2 = "L2square"; 3 = table "L2", 4 = table "L2square" */
     int32_t alpha;              /* 0: "standard" (gradient as is), 1: "standard-alpha" (x eta_t)   :1243-1248 */
     int32_t recurrence;         /* 0: non-recurrence branch; N >= 1: "-recurrence-N"                :1284-1370 */
     int32_t last_n_step;
@@ -427,6 +430,26 @@ int  cindm_ddpm1d_last_chain_info(const cindm_ddpm1d* h, int32_t info[4]);
  * per record, info[2] = steps run, info[3] = streams. */
 int  cindm_ddpm1d_set_recorder(cindm_ddpm1d* h, float* buf, int64_t buf_floats, int32_t every, int32_t streams);
 int  cindm_ddpm1d_recorder_info(const cindm_ddpm1d* h, int32_t info[4]);
+
+/* The waypoint objective's tables (cindm_design_desc modes 3 / 4).  No reference counterpart: its script evaluates one target
+ * per sample() call (inference/inverse_design_diffusion_1d.py:283-315); here a batch can carry a target and a weight per design.
+ * target: DEVICE floats [batch, rows, n_bodies, 2] when target_per_design, else [rows, n_bodies, 2] shared by every design: the
+ * position (features 4j, 4j+1) body j is drawn to at that row, in state units.
+ * scale:  DEVICE floats [batch, rows, n_bodies] when scale_per_design, else [rows, n_bodies]: finite and >= 0; an entry that is 0
+ * contributes nothing to the gradient (its target is not read).  The update kernel evaluates, per position component,
+ *   "L2": scale * d / sqrtf(d * d + d_other * d_other),  "L2square": scale * 2 * d,  d = pos - target,
+ * the point objective's expressions with scale in place of coef / last_n_step.
+ * cindm_ddpm1d_set_design_tables arms the NEXT chain call on this handle; that call consumes the tables whether it succeeds or
+ * fails, and (NULL, NULL) disarms.  cindm_ddpm1d_sample_guided / _sample_ddim_guided check rows == L_tot, n_bodies == c->n_bodies,
+ * batch == B and that both tables are 16-byte aligned before they launch or copy anything, and refuse modes 3 / 4 with nothing
+ * armed and armed tables with modes 1 / 2; every other chain entry refuses armed tables.  The tables must stay alive and
+ * unchanged until the chain's work has finished: with use_graph that is when the call returns (it synchronises; an exchange-free
+ * re-run inside the call reads them again); with use_graph = 0 the steps are only enqueued on the caller's stream, so the tables
+ * must outlive that stream's work (free or overwrite them after a synchronise, or in stream order).  Their addresses and the two
+ * flags are operands of the captured update: a call with other tables captures its step again. */
+int  cindm_ddpm1d_set_design_tables(cindm_ddpm1d* h, const float* target, int32_t target_per_design,
+                                    const float* scale, int32_t scale_per_design,
+                                    int32_t rows, int32_t n_bodies, int64_t batch);
 
 /* ===================================================================== 2-D airfoil path
  * Replaces Unet.forward (model/diffusion_2d.py:369-408) and GaussianDiffusion.p_sample /
