@@ -6,6 +6,9 @@
 //   replay_once         the 2-D chains' replay: stream_steps, or capture + run + destroy (no cache)
 //   upload_ddim_tables  schedule check + the DDIM loops' per-step device tables
 //   DesignTablesScope   the waypoint objective's tables: taken by every chain entry, run by the two guided ones (bottom of this file)
+// On top of these, the 1-D entries (cindm_hip.hip) state their own facts once in Chain1D, chain_io, loop_chain and chain_slices, and
+// the four 2-D entries (ddpm2d_host.inc) theirs in Chain2D (the workspace layout), chain2_refuse / force_refuse, ForceGuide,
+// ddim_args2, ddpm_step2 / ddim_step2 and run_chain2.
 // The 1-D replay (replay_steps in cindm_hip.hip: graph cached in the handle by key, ping-pong pair + odd tail, flag polls) is built
 // on the same two graph functions.
 

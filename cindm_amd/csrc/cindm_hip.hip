@@ -2854,6 +2854,7 @@ extern "C" int cindm_fill_normal(float* out, int64_t B, int64_t per_sample, uint
 // ============================================================================ 2-D airfoil path
 #include "unet2d_host.inc"
 #include "forceunet_host.inc"
+#include "ddpm2d_host.inc"
 
 // ---- multi-GPU: the one all-gather of the path, on RCCL (include/cindm_hip.h) -----------------------------------------------
 #include <dlfcn.h>

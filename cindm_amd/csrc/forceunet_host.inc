@@ -833,43 +833,8 @@ extern "C" int cindm_airfoil_design_grad(cindm_forceunet* h, const float* x, int
     return 0;
 }
 
-
-// A surrogate-guided 2-D chain with its recovery (as run_chain_with_recovery of the 1-D path): the surrogate's GroupNorm derivative
-// exchanges partial sums between the workgroups of an image (fu_gn_silu_bwd_cluster_kernel); a partner kept off the chip by foreign load
-// times out, poisons that image's gradient with NaN and raises the handle's error word.  x_T is kept in its slice of the caller's
-// diffusion workspace; a chain that ends with the word raised is re-run ONCE from it on the exchange-free derivative (counter-based
-// noise / read-only tapes: the same draws).  chain() sets the device counter and replays the steps.
-template <typename ChainFn>
-static int force_chain_with_recovery(cindm_unet2d* u, cindm_forceunet* f, float* x, int64_t NI, void* ws, size_t ws_bytes,
-                                     hipStream_t stream, ChainFn chain) {
-    const size_t n_floats = (size_t)NI * u->d.image_size * u->d.image_size * u->CP();
-    const bool guard = f->O("gn_bwd_fused") >= 2 && !f->O("no_exchange");
-    REQUIRE(ws && ws_bytes >= cindm_ddpm2d_workspace_bytes(u, NI), "workspace too small (cindm_ddpm2d_workspace_bytes)");
-    float* xT = reinterpret_cast<float*>((char*)ws + ddpm2d_xT_offset(u, NI));      // (a slice of the caller's workspace)
-    if (guard) HIPCHK(hipMemcpyAsync(xT, x, n_floats * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    if (chain() != 0) return -1;
-    if (!guard) return 0;
-    const int st = cindm_forceunet_status(f, stream);       // (synchronises: an eager chain is handed back checked too)
-    if (st < 0) return -1;
-    if (st == 0) return 0;
-    if (!f->O("recover")) return fail("an in-kernel exchange of the surrogate's GroupNorm derivative timed out (foreign load on the device); "
-                                      "option recover = 0: not re-run");
-    HIPCHK(hipMemcpyAsync(x, xT, n_floats * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    f->nx_force = 1; ++f->recovered;
-    const int rc2 = chain();
-    f->nx_force = 0;
-    if (rc2 != 0) return -1;
-    if (cindm_forceunet_status(f, stream) == 1) return fail("an exchange timed out during the exchange-free re-run (internal error)");
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Design-guided 2-D sampling with the airfoil objective INSIDE the captured step (inference/inverse_design_2d.py:236-244
-// with design_guidance = "standard-alpha", model/diffusion_2d.py:788-845): per reverse step
-//     g = d(force + overlap)/dx at x_t      (cindm_airfoil_design_grad: 6 surrogate forward + input-gradient passes)
-//     x_{t-1} = p_sample(x_t)               (Unet forward, boundary sharing, posterior mean + sigma_t z)
-//     x_{t-1} -= eta[t] * g                 (eta = coeff_ratio * betas.flip(0), a device table of the caller)
-// as ONE hipGraph replayed once per timestep -- no host code, no layout conversion between the three parts.
+// The guidance shift of the design-guided DDPM chain (ddpm_step2 in ddpm2d_host.inc): x_{t-1} -= eta[t] * g, the third part of its
+// captured step.
 __global__ void guided_shift2d_kernel(float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ eta,
                                       const int* __restrict__ t_dev, int64_t n4) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -879,106 +844,4 @@ __global__ void guided_shift2d_kernel(float* __restrict__ x, const float* __rest
     const float4 d = reinterpret_cast<const float4*>(g)[i];
     v.x -= e * d.x; v.y -= e * d.y; v.z -= e * d.z; v.w -= e * d.w;
     reinterpret_cast<float4*>(x)[i] = v;
-}
-
-extern "C" int cindm_ddpm2d_sample_force(cindm_ddpm1d* s, cindm_unet2d* u, cindm_forceunet* f, float* x, int64_t B, int32_t nb,
-                                         int32_t use_average_share, const float* noise_state_steps,
-                                         const float* noise_boundary_steps, uint64_t seed, int64_t sample_offset,
-                                         int32_t t_start, int32_t t_end, int32_t frames, float p_min, float p_max,
-                                         float lambda_force, float lambda_overlap, int32_t down_factor, int32_t sum_boundary,
-                                         const float* eta, float* grad, void* ws, size_t ws_bytes, void* ws_force,
-                                         size_t ws_force_bytes, void* stream_, int32_t use_graph) {
-    RecScope rs(s);
-    REQUIRE(s && u && f && x && eta && grad && ws && ws_force, "null argument");
-    REQUIRE(t_start < s->T && t_end >= 0 && t_end <= t_start, "bad timestep range");
-    REQUIRE(u->d.image_size == f->d.image_size, "Unet and ForceUnet image sizes differ");
-    REQUIRE(u->d.channels == 3 * frames + 3, "state channels must be 3 * frames + 3");
-    if (rec_begin2(rs, u, x, t_start - t_end + 1, B, nb) != 0) return -1;
-    hipStream_t stream = nullptr;
-    if (chain_stream(s, stream_, use_graph, &stream) != 0) return -1;
-    const int HW = u->d.image_size * u->d.image_size, CP = u->CP();
-    Step2IO io = chain_io2(u, x, B, nb, noise_state_steps, noise_boundary_steps, seed, sample_offset);
-    if (s->rec) io.x0_out = s->rec->x0_stage;
-    const int64_t n4 = B * nb * (int64_t)HW * (CP / 4);
-    auto one_step = [&](int) -> int {
-        if (cindm_airfoil_design_grad(f, x, B, nb, frames, CP, p_min, p_max, lambda_force, lambda_overlap, down_factor, sum_boundary,
-                                      grad, ws_force, ws_force_bytes, stream) != 0) return -1;
-        if (run_step2(s, u, io, B, nb, use_average_share, 1, 0, s->t_dev, ws, ws_bytes, stream) != 0) return -1;
-        hipLaunchKernelGGL(guided_shift2d_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, x, grad, eta, s->t_dev, n4);
-        HIPCHK(hipGetLastError());
-        return s->rec ? rec_node(s, x, 0, stream) : 0;      // (the shift is the step's last writer of the state)
-    };
-    const int nsteps = t_start - t_end + 1;
-    return rec_done(rs, force_chain_with_recovery(u, f, x, B * nb, ws, ws_bytes, stream, [&]() -> int {
-        hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (int)t_start, 0ull, 0ll);
-        rec_arm(s, (int)t_start, 0, 0, stream);
-        return replay_once(stream, nsteps, use_graph, one_step);
-    }));
-}
-
-// Guided DDIM of the 2-D path with the airfoil objective inside the captured step (DESIGN 4.5k): per DDIM step i, pair (t, t_next),
-//     g = d(force + overlap)/dx at x_t      (cindm_airfoil_design_grad)
-//     x' = the DDIM update of x_t           (Unet forward + the update of cindm_ddpm2d_sample_ddim, the same draws)
-//     x_next = x' - weights[i] * g          (in the same launch: ddim2d_guided_update_kernel)
-// as ONE hipGraph replayed n_steps times; weights ride in the 4th word of the caller's per-step table rows.
-extern "C" int cindm_ddpm2d_sample_ddim_force(cindm_ddpm1d* s, cindm_unet2d* u, cindm_forceunet* f, float* x, int64_t B, int32_t nb,
-                                              int32_t use_average_share, int32_t n_steps, const int32_t* times, const float* coefs,
-                                              const float* weights, void* tab, size_t tab_bytes, const float* noise_state_steps,
-                                              const float* noise_boundary_steps, uint64_t seed, int64_t sample_offset, int32_t frames,
-                                              float p_min, float p_max, float lambda_force, float lambda_overlap, int32_t down_factor,
-                                              int32_t sum_boundary, float* grad, void* ws, size_t ws_bytes, void* ws_force,
-                                              size_t ws_force_bytes, void* stream_, int32_t use_graph) {
-    RecScope rs(s);
-    REQUIRE(s && u && f && x && times && coefs && weights && tab && grad && ws && ws_force, "null argument");
-    REQUIRE(((use_average_share >> 4) & 3) <= 2 && (use_average_share & ~0x31) == 0,
-            "bad use_average_share word (bit 0 mean / sum, bits 4-5 objective 0..2; DDIM has no share_noise False)");
-    REQUIRE(B > 0 && nb >= 1, "bad batch");
-    REQUIRE(s->T <= u->d.timesteps, "the diffusion has more timesteps than the Unet's per-timestep table (construct Unet(..., timesteps=T))");
-    REQUIRE(f->finalized, "cindm_forceunet_finalize has not been called");
-    REQUIRE(u->d.image_size == f->d.image_size, "Unet and ForceUnet image sizes differ");
-    REQUIRE(frames >= 1 && u->d.channels == 3 * frames + 3, "state channels must be 3 * frames + 3");
-    REQUIRE(f->d.channels == 4, "the airfoil objective feeds (pressure, 3 boundary channels): ForceUnet(channels=4)");
-    REQUIRE(down_factor >= 1 && u->d.image_size % down_factor == 0, "downsampling_factor must divide the image size");
-    // (n_steps < 1 and the schedule itself are refused by upload_ddim_tables, before anything is copied)
-    REQUIRE(tab_bytes >= (size_t)std::max(n_steps, 0) * 5 * sizeof(float) && ((uintptr_t)tab & 15) == 0, "DDIM table buffer too small or not 16-byte aligned");
-    const int64_t NI = B * nb;
-    const int HW = u->d.image_size * u->d.image_size, CP = u->CP(), Cs = u->d.channels - 3;
-    REQUIRE(NI * (int64_t)HW * CP < (1ll << 31), "state too large for one launch");
-    REQUIRE(ws_bytes >= cindm_ddpm2d_workspace_bytes(u, NI), "workspace too small");
-    REQUIRE((((uintptr_t)x | (uintptr_t)grad | (uintptr_t)ws) & 15) == 0, "x, grad and ws must be 16-byte aligned");
-    REQUIRE(((uintptr_t)ws_force & 255) == 0 && ws_force_bytes >= cindm_airfoil_design_workspace_bytes(f, B, nb, 1),
-            "surrogate workspace too small (cindm_airfoil_design_workspace_bytes) or not 256-byte aligned");
-    if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    if (rec_begin2(rs, u, x, n_steps, B, nb, kNoX0Ddim2d) != 0) return -1;
-    hipStream_t stream = nullptr;
-    if (chain_stream(s, stream_, use_graph, &stream) != 0) return -1;
-    float* tab_f = (float*)tab;
-    int* tn_dev = nullptr;
-    if (upload_ddim_tables(s->T, n_steps, times, coefs, tab_f, stream, &tn_dev, weights) != 0) return -1;
-    Ddim2dArgs a; std::memset(&a, 0, sizeof(a));
-    a.x = x; a.x_out = x;
-    a.B = (int)B; a.nb = nb; a.HW = HW; a.C = u->d.channels; a.CP = CP; a.use_avg = use_average_share;
-    const float* tb = s->tab; const size_t T = s->T;
-    a.sqrt_recip = tb + 6 * T; a.sqrt_recipm1 = tb + 7 * T; a.sqrt_ac = tb + 3 * T; a.sqrt_1mac = tb + 4 * T;
-    a.t_dev = s->t_dev; a.tab = tab_f; a.tnext = tn_dev;
-    a.noise_state = noise_state_steps; a.ns_t_stride = B * (int64_t)HW * Cs;
-    a.noise_bound = noise_boundary_steps; a.nb_t_stride = NI * (int64_t)HW * 3;
-    a.seed = seed; a.sample_off = sample_offset;
-    a.eps = (const float*)ws;
-    const size_t st = (((size_t)NI * HW * CP * sizeof(float)) + 255) / 256 * 256;
-    const int64_t ne = B * (int64_t)HW * (CP / 4);
-    auto one_step = [&](int) -> int {
-        if (cindm_airfoil_design_grad(f, x, B, nb, frames, CP, p_min, p_max, lambda_force, lambda_overlap, down_factor, sum_boundary,
-                                      grad, ws_force, ws_force_bytes, stream) != 0) return -1;
-        if (cindm_unet2d_forward(u, x, 0, s->t_dev, (float*)ws, NI, (char*)ws + st, ws_bytes - st, stream) != 0) return -1;
-        hipLaunchKernelGGL(ddim2d_guided_update_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a, (const float*)grad);
-        hipLaunchKernelGGL(step_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (const int*)tn_dev, (int*)nullptr, (int*)nullptr);
-        HIPCHK(hipGetLastError());
-        return s->rec ? rec_node(s, x, 0, stream) : 0;
-    };
-    return rec_done(rs, force_chain_with_recovery(u, f, x, NI, ws, ws_bytes, stream, [&]() -> int {
-        hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (int)times[0], 0ull, 0ll);
-        rec_arm(s, -1, 2, 0, stream);
-        return replay_once(stream, n_steps, use_graph, one_step);
-    }));
 }

@@ -1122,184 +1122,7 @@ extern "C" int cindm_unet2d_tap(cindm_unet2d* h, const char* name, int64_t image
     return 0;
 }
 
-// ---- GaussianDiffusion (2-D) -----------------------------------------------------------------------------
-extern "C" size_t cindm_ddpm2d_workspace_bytes(const cindm_unet2d* u, int64_t images) {
-    if (!u) return 0;
-    const size_t st = (size_t)images * u->d.image_size * u->d.image_size * u->CP() * sizeof(float);
-    // [predicted noise][U-Net workspace][x_T snapshot of the guided chain's recovery (cindm_ddpm2d_sample_force): no allocation after *_create]
-    return 2 * (((st + 255) / 256) * 256) + ((cindm_unet2d_workspace_bytes(u, images) + 255) / 256) * 256 + 256;
-}
-// offset of the x_T snapshot inside a diffusion workspace
-static size_t ddpm2d_xT_offset(const cindm_unet2d* u, int64_t images) {
-    const size_t st = (size_t)images * u->d.image_size * u->d.image_size * u->CP() * sizeof(float);
-    return ((st + 255) / 256) * 256 + ((cindm_unet2d_workspace_bytes(u, images) + 255) / 256) * 256;
-}
-
-struct Step2IO {
-    const float* x; float* x_out; float* x0_out; float* mean_out;
-    float* eps_out = nullptr; int predict = 0, rederive = 0;      // cindm_ddpm2d_predict
-    const float* noise_state; int64_t ns_stride; const float* noise_bound; int64_t nb_stride;
-    uint64_t seed; int64_t off; int add_noise; int dec_t;
-};
-
-static int run_step2(cindm_ddpm1d* s, cindm_unet2d* u, const Step2IO& io, int64_t B, int nb, int use_avg, int clip,
-                     int32_t t, const int32_t* t_dev, void* ws, size_t ws_bytes, hipStream_t stream) {
-    // the share word: bit 0 = mean (1) / sum (0) over the boundary copies, bit 1 = share_noise False, bits 4-5 = objective (0 pred_noise,
-    // 1 pred_x0, 2 pred_v).  Anything else is a caller error, not a silent x_start of 0 (objective 3) or a silent "sum" (2 for "true")
-    REQUIRE(((use_avg >> 4) & 3) <= 2 && (use_avg & ~0x33) == 0, "bad use_average_share word (bit 0 mean / sum, bit 1 share_noise off, bits 4-5 objective 0..2)");
-    REQUIRE(s && u && io.x && ws, "null argument");
-    REQUIRE(B > 0 && nb >= 1, "bad batch");
-    REQUIRE(t_dev || (t >= 0 && t < s->T), "timestep out of range");
-    REQUIRE(s->T <= u->d.timesteps, "the diffusion has more timesteps than the Unet's per-timestep table (construct Unet(..., timesteps=T))");
-    const int64_t NI = B * nb;
-    const int HW = u->d.image_size * u->d.image_size, CP = u->CP();
-    REQUIRE(ws_bytes >= cindm_ddpm2d_workspace_bytes(u, NI), "workspace too small");
-    char* w = (char*)ws;
-    float* eps = (float*)w;
-    const size_t st = (((size_t)NI * HW * CP * sizeof(float)) + 255) / 256 * 256;
-    if (cindm_unet2d_forward(u, io.x, t, t_dev, eps, NI, w + st, ws_bytes - st, stream) != 0) return -1;
-    Update2dArgs a; std::memset(&a, 0, sizeof(a));
-    a.x = io.x; a.eps = eps; a.x_out = io.x_out; a.x0_out = io.x0_out; a.mean_out = io.mean_out;
-    a.eps_out = io.eps_out; a.predict = io.predict; a.rederive = io.rederive;
-    REQUIRE(NI * (int64_t)HW * CP < (1ll << 31), "state too large for one launch");
-    a.B = (int)B; a.nb = nb; a.HW = HW; a.C = u->d.channels; a.CP = CP; a.use_avg = use_avg; a.clip = clip; a.add_noise = io.add_noise;
-    const float* tb = s->tab; const size_t T = s->T;
-    a.sqrt_recip = tb + 6 * T; a.sqrt_recipm1 = tb + 7 * T; a.logvar = tb + 9 * T; a.coef1 = tb + 10 * T; a.coef2 = tb + 11 * T;
-    a.sqrt_ac = tb + 3 * T; a.sqrt_1mac = tb + 4 * T;
-    a.t_ptr = t_dev; a.t_imm = t;
-    a.noise_state = io.noise_state; a.ns_t_stride = io.ns_stride; a.noise_bound = io.noise_bound; a.nb_t_stride = io.nb_stride;
-    a.seed = io.seed; a.sample_off = io.off;
-    const int64_t ne = B * (int64_t)HW * (CP / 4);
-    hipLaunchKernelGGL(update2d_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a);
-    if (io.dec_t) hipLaunchKernelGGL(step_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (const int*)nullptr, (int*)nullptr, (int*)nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int cindm_ddpm2d_step(cindm_ddpm1d* s, cindm_unet2d* u, float* x, int64_t B, int32_t nb, int32_t use_average_share,
-                                 int32_t clip_denoised, const float* noise_state, const float* noise_boundary, uint64_t seed,
-                                 int64_t sample_offset, int32_t t, const int32_t* t_dev, float* x0_out, float* mean_out,
-                                 void* ws, size_t ws_bytes, void* stream) {
-    Step2IO io{};
-    io.x = x; io.x_out = x; io.x0_out = x0_out; io.mean_out = mean_out;
-    io.noise_state = noise_state; io.noise_bound = noise_boundary; io.ns_stride = 0; io.nb_stride = 0;
-    io.seed = seed; io.off = sample_offset; io.add_noise = 1;
-    return run_step2(s, u, io, B, nb, use_average_share, clip_denoised, t, t_dev, ws, ws_bytes, (hipStream_t)stream);
-}
-
-// model_predictions (:727-754): the U-Net and the boundary sharing of its output, x_start, optional clamp / re-derived noise
-extern "C" int cindm_ddpm2d_predict(cindm_ddpm1d* s, cindm_unet2d* u, const float* x, int64_t B, int32_t nb, int32_t use_average_share,
-                                    int32_t share_noise, int32_t clip_x_start, int32_t rederive_pred_noise, int32_t t,
-                                    const int32_t* t_dev, float* pred_noise_out, float* x_start_out, void* ws, size_t ws_bytes,
-                                    void* stream) {
-    Step2IO io{};
-    io.x = x; io.x_out = nullptr; io.x0_out = x_start_out; io.mean_out = nullptr;
-    io.eps_out = pred_noise_out; io.predict = 1; io.rederive = (clip_x_start && rederive_pred_noise) ? 1 : 0;
-    io.add_noise = 0;
-    return run_step2(s, u, io, B, nb, ((use_average_share & ~0x30) ? 1 : 0) | (share_noise ? 0 : 2) | (use_average_share & 0x30), clip_x_start, t, t_dev, ws, ws_bytes,
-                     (hipStream_t)stream);
-}
-
-// the recorder of a 2-D chain: one record is the whole state in the library's layout, [B * nb][H * W][padded channels]
-static const char* const kNoX0Ddim2d = "recorder: the 2-D DDIM update kernels have no x0 operand: the x0 stream is served by the DDPM entries only";
-static int rec_begin2(RecScope& rs, const cindm_unet2d* u, const float* x, int n_steps, int64_t B, int nb, const char* x0_refusal = nullptr) {
-    if (!rs.on()) return 0;
-    REQUIRE(u && B > 0 && nb >= 1, "bad batch");
-    return rec_begin(rs, x, n_steps, B * nb * (int64_t)u->d.image_size * u->d.image_size * u->CP(), x0_refusal);
-}
-
-// the Step2IO of a 2-D sample loop: in-place state, per-step tapes (or counter noise), the device counter decremented by the step
-static Step2IO chain_io2(const cindm_unet2d* u, float* x, int64_t B, int nb, const float* noise_state_steps,
-                         const float* noise_boundary_steps, uint64_t seed, int64_t sample_offset) {
-    const int HW = u->d.image_size * u->d.image_size, Cs = u->d.channels - 3;
-    Step2IO io{};
-    io.x = x; io.x_out = x;
-    io.noise_state = noise_state_steps; io.ns_stride = (int64_t)B * HW * Cs;
-    io.noise_bound = noise_boundary_steps; io.nb_stride = (int64_t)B * nb * HW * 3;
-    io.seed = seed; io.off = sample_offset; io.add_noise = 1; io.dec_t = 1;
-    return io;
-}
-
-extern "C" int cindm_ddpm2d_sample(cindm_ddpm1d* s, cindm_unet2d* u, float* x, int64_t B, int32_t nb, int32_t use_average_share,
-                                   const float* noise_state_steps, const float* noise_boundary_steps, uint64_t seed,
-                                   int64_t sample_offset, int32_t t_start, int32_t t_end, void* ws, size_t ws_bytes,
-                                   void* stream_, int32_t use_graph) {
-    RecScope rs(s);
-    REQUIRE(s && u && x, "null argument");
-    REQUIRE(t_start < s->T && t_end >= 0 && t_end <= t_start, "bad timestep range");
-    if (rec_begin2(rs, u, x, t_start - t_end + 1, B, nb) != 0) return -1;
-    hipStream_t stream = nullptr;
-    if (chain_stream(s, stream_, use_graph, &stream) != 0) return -1;
-    Step2IO io = chain_io2(u, x, B, nb, noise_state_steps, noise_boundary_steps, seed, sample_offset);
-    if (s->rec) io.x0_out = s->rec->x0_stage;
-    hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (int)t_start, 0ull, 0ll);
-    rec_arm(s, (int)t_start, 0, 0, stream);
-    return rec_done(rs, replay_once(stream, t_start - t_end + 1, use_graph, [&](int) {
-        if (run_step2(s, u, io, B, nb, use_average_share, 1, 0, s->t_dev, ws, ws_bytes, stream) != 0) return -1;
-        return s->rec ? rec_node(s, x, 0, stream) : 0;      // (after the step's counter launch: the word is the next timestep)
-    }));
-}
-
-// DDIM loop of the 2-D path (ddim_sample; DESIGN 4.5g): one step = the U-Net + ddim2d_update_kernel + step_counter_kernel
-// (t and the step index advance on the device from the time_next table), replayed n_steps times
-static int run_ddim_step2(cindm_ddpm1d* s, cindm_unet2d* u, const Ddim2dArgs& proto, int64_t B, int nb, void* ws, size_t ws_bytes,
-                          hipStream_t stream) {
-    const int64_t NI = B * nb;
-    const int HW = u->d.image_size * u->d.image_size, CP = u->CP();
-    char* w = (char*)ws;
-    float* eps = (float*)w;
-    const size_t st = (((size_t)NI * HW * CP * sizeof(float)) + 255) / 256 * 256;
-    if (cindm_unet2d_forward(u, proto.x, 0, s->t_dev, eps, NI, w + st, ws_bytes - st, stream) != 0) return -1;
-    Ddim2dArgs a = proto;
-    a.eps = eps;
-    const int64_t ne = B * (int64_t)HW * (CP / 4);
-    hipLaunchKernelGGL(ddim2d_update_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(step_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, a.tnext, (int*)nullptr, (int*)nullptr);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int cindm_ddpm2d_sample_ddim(cindm_ddpm1d* s, cindm_unet2d* u, float* x, int64_t B, int32_t nb, int32_t use_average_share,
-                                        int32_t n_steps, const int32_t* times, const float* coefs, void* tab, size_t tab_bytes,
-                                        const float* noise_state_steps, const float* noise_boundary_steps, uint64_t seed,
-                                        int64_t sample_offset, void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
-    RecScope rs(s);
-    REQUIRE(s && u && x && times && coefs && tab && ws, "null argument");
-    REQUIRE(((use_average_share >> 4) & 3) <= 2 && (use_average_share & ~0x31) == 0,
-            "bad use_average_share word (bit 0 mean / sum, bits 4-5 objective 0..2; DDIM has no share_noise False)");
-    REQUIRE(B > 0 && nb >= 1, "bad batch");
-    REQUIRE(s->T <= u->d.timesteps, "the diffusion has more timesteps than the Unet's per-timestep table (construct Unet(..., timesteps=T))");
-    // (n_steps < 1 and the schedule itself are refused by upload_ddim_tables, before anything is copied)
-    REQUIRE(tab_bytes >= (size_t)std::max(n_steps, 0) * 5 * sizeof(float) && ((uintptr_t)tab & 15) == 0, "DDIM table buffer too small or not 16-byte aligned");
-    const int64_t NI = B * nb;
-    const int HW = u->d.image_size * u->d.image_size, CP = u->CP(), Cs = u->d.channels - 3;
-    REQUIRE(NI * (int64_t)HW * CP < (1ll << 31), "state too large for one launch");
-    REQUIRE(ws_bytes >= cindm_ddpm2d_workspace_bytes(u, NI), "workspace too small");
-    if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    if (rec_begin2(rs, u, x, n_steps, B, nb, kNoX0Ddim2d) != 0) return -1;
-    hipStream_t stream = nullptr;
-    if (chain_stream(s, stream_, use_graph, &stream) != 0) return -1;
-    // the per-step tables go to the caller's device buffer
-    float* tab_f = (float*)tab;
-    int* tn_dev = nullptr;
-    if (upload_ddim_tables(s->T, n_steps, times, coefs, tab_f, stream, &tn_dev) != 0) return -1;
-    Ddim2dArgs a; std::memset(&a, 0, sizeof(a));
-    a.x = x; a.x_out = x;
-    a.B = (int)B; a.nb = nb; a.HW = HW; a.C = u->d.channels; a.CP = CP; a.use_avg = use_average_share;
-    const float* tb = s->tab; const size_t T = s->T;
-    a.sqrt_recip = tb + 6 * T; a.sqrt_recipm1 = tb + 7 * T; a.sqrt_ac = tb + 3 * T; a.sqrt_1mac = tb + 4 * T;
-    a.t_dev = s->t_dev; a.tab = tab_f; a.tnext = tn_dev;
-    a.noise_state = noise_state_steps; a.ns_t_stride = B * (int64_t)HW * Cs;
-    a.noise_bound = noise_boundary_steps; a.nb_t_stride = NI * (int64_t)HW * 3;
-    a.seed = seed; a.sample_off = sample_offset;
-    hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, stream, s->t_dev, (int)times[0], 0ull, 0ll);
-    rec_arm(s, -1, 2, 0, stream);
-    return rec_done(rs, replay_once(stream, n_steps, use_graph, [&](int) {
-        if (run_ddim_step2(s, u, a, B, nb, ws, ws_bytes, stream) != 0) return -1;
-        return s->rec ? rec_node(s, x, 0, stream) : 0;
-    }));
-}
-
+// x_T of the 2-D chains (ddpm2d_host.inc), drawn by the counter-based generator
 extern "C" int cindm_fill_noise2d(float* x, int64_t B, int32_t nb, int32_t hw, int32_t channels, int32_t padded_channels,
                                   uint64_t seed, int64_t sample_offset, int32_t step_tag, void* stream) {
     REQUIRE(x && B > 0 && nb > 0, "bad argument");

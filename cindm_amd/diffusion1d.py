@@ -29,9 +29,10 @@ import torch
 from torch import nn
 
 from . import _ffi
+from .diffusion_base import DiffusionHandle
 from .objectives import PointObjective, WaypointObjective
 from .record import DeviceRecorder, LoopRecorder
-from .schedule import ddim_schedule, make_schedule, ula_schedule
+from .schedule import make_schedule, ula_schedule
 
 ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"])
 
@@ -91,7 +92,7 @@ def autoregress_segments(conditioned_steps, rollout_steps, n_composed, is_single
     return K
 
 
-class GaussianDiffusion1D(nn.Module):
+class GaussianDiffusion1D(DiffusionHandle, nn.Module):
     """Drop-in for the reference's ``GaussianDiffusion1D`` (constructor :802-822)."""
 
     def __init__(self, model, model_unconditioned=None, betas_inference=None, *, image_size, conditioned_steps,
@@ -115,10 +116,7 @@ class GaussianDiffusion1D(nn.Module):
         assert objective in {"pred_noise", "pred_x0", "pred_v"}, "objective must be pred_noise, pred_x0 or pred_v"
         tables = make_schedule(beta_schedule, timesteps, objective)
         self.num_timesteps = int(timesteps)
-        # the model's time path is a table with model.timesteps rows (the reference evaluates its time MLP per call)
-        mt = getattr(model, "timesteps", None)
-        if mt is not None and int(mt) < int(timesteps):
-            raise ValueError(f"model was built with timesteps={mt} < diffusion timesteps={timesteps}: pass timesteps={timesteps} to the model")
+        self._check_model_timesteps(model, timesteps)
         self.loss_type = loss_type
         self.loss_weight_discount = loss_weight_discount
         self.sampling_timesteps = sampling_timesteps if _exists(sampling_timesteps) else timesteps
@@ -130,40 +128,6 @@ class GaussianDiffusion1D(nn.Module):
         self._h = None
         self._tab_sig = None
         self._ws = None
-
-    def __del__(self):
-        h = self.__dict__.get("_h")
-        if h is not None and h.value:
-            try:
-                _ffi.lib().cindm_ddpm1d_destroy(h)
-            except Exception:
-                pass
-            self.__dict__["_h"] = None
-
-    # ------------------------------------------------------------------ library handle
-    def _handle(self):
-        sig = tuple((getattr(self, n).data_ptr(), getattr(self, n)._version) for n in _ffi.SCHED_NAMES)
-        if self._h is not None and sig == self._tab_sig:
-            return self._h
-        L = _ffi.lib()
-        if self._h is not None:
-            L.cindm_ddpm1d_destroy(self._h)
-        d = _ffi.SchedDesc()
-        d.timesteps = self.num_timesteps
-        keep = []
-        for n in _ffi.SCHED_NAMES:
-            t = getattr(self, n).detach().to("cpu", torch.float32).contiguous()
-            keep.append(t)
-            setattr(d, n, t.data_ptr())
-        h = C.c_void_p()
-        dev = self.betas.device
-        if dev.type != "cuda":
-            raise _ffi.CindmError("GaussianDiffusion1D is on the CPU: move it to a ROCm device (.to('cuda')); "
-                                  "there is no CPU execution path")
-        with torch.cuda.device(dev):
-            _ffi.check(L.cindm_ddpm1d_create(C.byref(d), C.byref(h)))
-        self._h, self._tab_sig = h, sig
-        return h
 
     def _compose_desc(self, mode, n_composed, compose_start_step, window, n_bodies, clip=True, uncond_coef=1.4):
         c = _ffi.ComposeDesc()
@@ -324,12 +288,6 @@ class GaussianDiffusion1D(nn.Module):
         if noise is None:
             noise = torch.randn_like(x_start)
         return self.sqrt_alphas_cumprod[t].view(-1, 1, 1) * x_start + self.sqrt_one_minus_alphas_cumprod[t].view(-1, 1, 1) * noise
-
-    @staticmethod
-    def _t_int(t):
-        if torch.is_tensor(t):
-            return int(t.reshape(-1)[0])
-        return int(t)
 
     def _models(self, desc):
         return [self.model] + ([self.model_unconditioned] if desc.mode == _ffi.COMPOSE_MULTIBODY else [])
@@ -830,11 +788,6 @@ class GaussianDiffusion1D(nn.Module):
         raise NotImplementedError("training loss (p_losses, :2438-2501) is out of this build's scope")
 
     # ------------------------------------------------------------------ DDIM
-    def ddim_schedule(self):
-        """(times [S+1] descending to -1, coefs [S,3] = (sqrt(alpha_next), c, sigma)) of ddim_sample (:1743-1777), in the
-        reference's fp32 tensor arithmetic (schedule.ddim_schedule)."""
-        return ddim_schedule(self)
-
     @torch.no_grad()
     def ddim_sample(self, shape, cond, n_composed=None, clip_denoised=True, compose_start_step=4, compose_n_bodies=2,
                     compose_mode="mean", design_fn=None, design_guidance="standard", initial_state_overwrite=None,

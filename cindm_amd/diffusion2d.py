@@ -23,8 +23,9 @@ import torch
 from torch import nn
 
 from . import _ffi
+from .diffusion_base import DiffusionHandle
 from .record import DeviceRecorder, LoopRecorder, stream_mask
-from .schedule import ddim_schedule, make_schedule
+from .schedule import make_schedule
 from .unet2d import from_device_layout, to_device_layout
 
 
@@ -52,7 +53,7 @@ def _boundary_cl(s):
     return s.reshape(*lead, b * nb, c, h * w).transpose(-1, -2).contiguous()
 
 
-class GaussianDiffusion(nn.Module):
+class GaussianDiffusion(DiffusionHandle, nn.Module):
     """Drop-in for the reference's 2-D ``GaussianDiffusion`` (constructor :552-676)."""
 
     def __init__(self, model, *, image_size, frames=6, cond_frames=4, timesteps=1000, sampling_timesteps=None,
@@ -82,10 +83,7 @@ class GaussianDiffusion(nn.Module):
         assert image_size == model.image_size, "image_size must match the Unet's launch plan"
         tables = make_schedule(beta_schedule, timesteps, objective)
         self.num_timesteps = int(timesteps)
-        # the model's time path is a table with model.timesteps rows (the reference evaluates its time MLP per call)
-        mt = getattr(model, "timesteps", None)
-        if mt is not None and int(mt) < int(timesteps):
-            raise ValueError(f"model was built with timesteps={mt} < diffusion timesteps={timesteps}: pass timesteps={timesteps} to the model")
+        self._check_model_timesteps(model, timesteps)
         self.loss_type = loss_type
         self.sampling_timesteps = sampling_timesteps if sampling_timesteps is not None else timesteps
         assert self.sampling_timesteps <= timesteps
@@ -98,15 +96,6 @@ class GaussianDiffusion(nn.Module):
         self._ws = None
         self._ddim_tab = None
 
-    def __del__(self):
-        h = self.__dict__.get("_h")
-        if h is not None and h.value:
-            try:
-                _ffi.lib().cindm_ddpm1d_destroy(h)
-            except Exception:
-                pass
-            self.__dict__["_h"] = None
-
     def _share_mode(self):
         """The library's ``use_average_share`` word: bit 0 = mean (1) / sum (0) over the boundary copies of a design, bit 1 =
         share_noise False -- the clamped x_start and the posterior mean are shared instead of the prediction (:757-773); bits 4-5 =
@@ -114,30 +103,6 @@ class GaussianDiffusion(nn.Module):
         return int(bool(self.use_average_share)) | (0 if self.share_noise else 2) | (_ffi.OBJECTIVES[self.objective] << 4)
 
     # ------------------------------------------------------------------ library handle
-    def _handle(self):
-        sig = tuple((getattr(self, n).data_ptr(), getattr(self, n)._version) for n in _ffi.SCHED_NAMES)
-        if self._h is not None and sig == self._tab_sig:
-            return self._h
-        L = _ffi.lib()
-        if self._h is not None:
-            L.cindm_ddpm1d_destroy(self._h)
-        dev = self.betas.device
-        if dev.type != "cuda":
-            raise _ffi.CindmError("GaussianDiffusion is on the CPU: move it to a ROCm device (.to('cuda')); "
-                                  "there is no CPU execution path")
-        d = _ffi.SchedDesc()
-        d.timesteps = self.num_timesteps
-        keep = []
-        for n in _ffi.SCHED_NAMES:
-            t = getattr(self, n).detach().to("cpu", torch.float32).contiguous()
-            keep.append(t)
-            setattr(d, n, t.data_ptr())
-        h = C.c_void_p()
-        with torch.cuda.device(dev):
-            _ffi.check(L.cindm_ddpm1d_create(C.byref(d), C.byref(h)))
-        self._h, self._tab_sig = h, sig
-        return h
-
     def _prepare(self, images, device):
         self.model.sync_weights()
         h = self._handle()
@@ -171,10 +136,6 @@ class GaussianDiffusion(nn.Module):
         state = torch.randn((shape[0], 1, shape[2] - 3, shape[3], shape[4]), device=device)
         boundary = torch.randn((shape[0], shape[1], 3, shape[3], shape[4]), device=device)
         return torch.cat([state.expand(-1, shape[1], -1, -1, -1), boundary], dim=2)
-
-    @staticmethod
-    def _t_int(t):
-        return int(t.reshape(-1)[0]) if torch.is_tensor(t) else int(t)
 
     # ------------------------------------------------------------------ one reverse step
     @torch.no_grad()
@@ -342,6 +303,31 @@ class GaussianDiffusion(nn.Module):
             return from_device_layout(rows.reshape(n * B * nb, H * W, cp), Cc, H, W).reshape(n, B, nb, Cc, H, W)
         return out, rec.collect(self._handle(), unpack)
 
+    def _chain2(self, shape, x, rec, call):
+        """One library chain on the state ``x`` (device layout, updated in place): the workspace, the recorder armed, the entry
+        ``call(L, h, ws)`` and what the sampling call returns."""
+        B, nb, Cc, H, W = shape
+        h, ws = self._prepare(B * nb, x.device)
+        if rec is not None:
+            rec.arm(h)
+        with torch.cuda.device(x.device):
+            _ffi.check(call(_ffi.lib(), h, ws))
+        return self._recorded(from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W), rec, shape)
+
+    def _force_part(self, fo, shape, device, buffers=True):
+        """A ForceObjective's part of a guided library call: (surrogate handle, its scalar arguments in ABI order, gradient buffer,
+        surrogate workspace).  ``buffers=False``: the shape check alone (the routes that loop in Python call the objective itself)."""
+        B, nb, Cc, H, W = shape
+        if (fo.B, fo.nb) != (B, nb) or Cc != 3 * fo.frames + 3:
+            raise ValueError("ForceObjective was built for another batch / boundary / frame count")
+        if not buffers:
+            return None
+        fo.model.sync_weights()
+        nfb = _ffi.lib().cindm_airfoil_design_workspace_bytes(fo.model._h, B, nb, fo.frames_per_pass)
+        wsf = torch.empty(nfb, dtype=torch.uint8, device=device)
+        g = torch.empty((B * nb, H * W, self.model.padded_channels), dtype=torch.float32, device=device)
+        return fo.model._h, (fo.frames, fo.p_min, fo.p_max, fo.lambda_force, fo.lambda_overlap, fo.factor, int(fo.sum_boundary)), g, wsf
+
     @torch.no_grad()
     def p_sample_loop(self, shape, design_fn=None, design_guidance="standard", return_all_timesteps=None, *,
                       noise=None, seed=0, sample_offset=0, use_graph=True, t_stop=0, device=None, fused=True,
@@ -355,46 +341,26 @@ class GaussianDiffusion(nn.Module):
         device = device or self.betas.device
         if device.type != "cuda":
             raise _ffi.CindmError("sampling needs a ROCm device; there is no CPU execution path")
-        L = _ffi.lib()
         T = self.num_timesteps
         # (the device record buffer is allocated only on the routes that are library chains)
         device_rec = lambda: self._recorder(return_trajectory_every, trajectory, T - int(t_stop), shape, device, t_start=T - 1)
         x = self._x_T(shape, noise, seed, sample_offset, device)
+        stream, share = _ffi.current_stream(device), self._share_mode()
         if design_fn is None:
-            rec = device_rec()
-            h, ws = self._prepare(B * nb, device)
             ns, nbnd = self._tape_cl(noise, device)
-            if rec is not None:
-                rec.arm(h)
-            with torch.cuda.device(device):
-                _ffi.check(L.cindm_ddpm2d_sample(h, self.model._h, _ffi.ptr(x), B, nb, self._share_mode(),
-                                                 _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, T - 1, int(t_stop),
-                                                 _ffi.ptr(ws), ws.numel(), _ffi.current_stream(device), int(use_graph)))
-            return self._recorded(from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W), rec, shape)
+            return self._chain2(shape, x, device_rec(), lambda L, h, ws: L.cindm_ddpm2d_sample(
+                h, self.model._h, _ffi.ptr(x), B, nb, share, _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, T - 1, int(t_stop),
+                _ffi.ptr(ws), ws.numel(), stream, int(use_graph)))
         from .forceunet import ForceObjective
         if isinstance(design_fn, ForceObjective) and design_guidance == "standard-alpha" and fused:
             # the library's own objective: surrogate forward + input gradient, the reverse step and the guidance shift are
             # ONE captured graph per timestep (cindm_ddpm2d_sample_force), as PointObjective is in the 1-D path
-            fo = design_fn
-            if (fo.B, fo.nb) != (B, nb) or Cc != 3 * fo.frames + 3:
-                raise ValueError("ForceObjective was built for another batch / boundary / frame count")
-            fo.model.sync_weights()
-            rec = device_rec()
-            h, ws = self._prepare(B * nb, device)
-            nfb = L.cindm_airfoil_design_workspace_bytes(fo.model._h, B, nb, fo.frames_per_pass)
-            wsf = torch.empty(nfb, dtype=torch.uint8, device=device)
-            g = torch.empty_like(x)
+            fh, fargs, g, wsf = self._force_part(design_fn, shape, device)
             eta = (self.coeff_ratio * self.betas.flip(0)).to(device, torch.float32).contiguous()
             ns, nbnd = self._tape_cl(noise, device)
-            if rec is not None:
-                rec.arm(h)
-            with torch.cuda.device(device):
-                _ffi.check(L.cindm_ddpm2d_sample_force(h, self.model._h, fo.model._h, _ffi.ptr(x), B, nb, self._share_mode(),
-                                                       _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, T - 1, int(t_stop),
-                                                       fo.frames, fo.p_min, fo.p_max, fo.lambda_force, fo.lambda_overlap, fo.factor,
-                                                       int(fo.sum_boundary), _ffi.ptr(eta), _ffi.ptr(g), _ffi.ptr(ws), ws.numel(), _ffi.ptr(wsf),
-                                                       wsf.numel(), _ffi.current_stream(device), int(use_graph)))
-            return self._recorded(from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W), rec, shape)
+            return self._chain2(shape, x, device_rec(), lambda L, h, ws: L.cindm_ddpm2d_sample_force(
+                h, self.model._h, fh, _ffi.ptr(x), B, nb, share, _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, T - 1, int(t_stop),
+                *fargs, _ffi.ptr(eta), _ffi.ptr(g), _ffi.ptr(ws), ws.numel(), _ffi.ptr(wsf), wsf.numel(), stream, int(use_graph)))
         # this route loops in Python: the same record, cloned per step
         rec = None if return_trajectory_every is None else LoopRecorder(T - int(t_stop), return_trajectory_every, trajectory, t_start=T - 1)
         img = from_device_layout(x, Cc, H, W)
@@ -408,11 +374,6 @@ class GaussianDiffusion(nn.Module):
         return self._recorded(img.reshape(B, nb, Cc, H, W), rec, shape)
 
     # ------------------------------------------------------------------ DDIM
-    def ddim_schedule(self):
-        """(times [S+1] descending to -1, coefs [S,3] = (sqrt(alpha_next), c, sigma)) of ddim_sample, in the reference's fp32
-        tensor arithmetic -- the 1-D path's schedule (schedule.ddim_schedule)."""
-        return ddim_schedule(self)
-
     def ddim_guidance_weights(self):
         """fp32 [S]: the "standard-alpha" guidance weight of every DDIM step -- for the pair (t, t_next) of ddim_schedule() the sum
         (in float64, rounded once) of eta = coeff_ratio * betas.flip(0) over the DDPM steps t_next+1 .. t that the step stands for,
@@ -460,10 +421,8 @@ class GaussianDiffusion(nn.Module):
         if device.type != "cuda":
             raise _ffi.CindmError("sampling needs a ROCm device; there is no CPU execution path")
         fo = design_fn
-        if fo is not None and ((fo.B, fo.nb) != (B, nb) or Cc != 3 * fo.frames + 3):
-            raise ValueError("ForceObjective was built for another batch / boundary / frame count")
+        force = None if fo is None else self._force_part(fo, shape, device, buffers=fused)
         cp = self.model.padded_channels
-        L = _ffi.lib()
         times, coefs = self.ddim_schedule()
         i0, i1 = (0, len(times) - 1) if step_range is None else step_range
         if not 0 <= i0 < i1 <= len(times) - 1:
@@ -495,37 +454,24 @@ class GaussianDiffusion(nn.Module):
         S = len(times) - 1
         rec = self._recorder(return_trajectory_every, trajectory, S, shape, device, times=times)
         ns, nbnd = self._tape_cl(noise, device, slice(i0, i1))
-        h, ws = self._prepare(B * nb, device)
         # the per-step device tables live in a caller tensor (the library allocates nothing): [S][4] coefficients + [S] time_next
         if self._ddim_tab is None or self._ddim_tab.numel() < 5 * S or self._ddim_tab.device != device:
             self._ddim_tab = torch.empty(5 * max(S, self.sampling_timesteps), dtype=torch.float32, device=device)
         tab = self._ddim_tab
         tarr = (C.c_int32 * (S + 1))(*times)
+        stream, share = _ffi.current_stream(device), self._share_mode()
         if fo is not None:
             # the library's own objective: surrogate gradient, U-Net and the update that carries the shift are ONE captured graph
             # per DDIM step (cindm_ddpm2d_sample_ddim_force); the weights ride in the 4th word of the table rows
-            fo.model.sync_weights()
+            fh, fargs, g, wsf = force
             w = self.ddim_guidance_weights()[i0:i1].contiguous()
-            nfb = L.cindm_airfoil_design_workspace_bytes(fo.model._h, B, nb, fo.frames_per_pass)
-            wsf = torch.empty(nfb, dtype=torch.uint8, device=device)
-            g = torch.empty_like(x)
-            if rec is not None:
-                rec.arm(h)
-            with torch.cuda.device(device):
-                _ffi.check(L.cindm_ddpm2d_sample_ddim_force(h, self.model._h, fo.model._h, _ffi.ptr(x), B, nb, self._share_mode(), S, tarr,
-                                                            _ffi.ptr(coefs), _ffi.ptr(w), _ffi.ptr(tab), tab.numel() * 4, _ffi.ptr(ns),
-                                                            _ffi.ptr(nbnd), seed, sample_offset, fo.frames, fo.p_min, fo.p_max,
-                                                            fo.lambda_force, fo.lambda_overlap, fo.factor, int(fo.sum_boundary), _ffi.ptr(g),
-                                                            _ffi.ptr(ws), ws.numel(), _ffi.ptr(wsf), wsf.numel(),
-                                                            _ffi.current_stream(device), int(use_graph)))
-            return self._recorded(from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W), rec, shape)
-        if rec is not None:
-            rec.arm(h)
-        with torch.cuda.device(device):
-            _ffi.check(L.cindm_ddpm2d_sample_ddim(h, self.model._h, _ffi.ptr(x), B, nb, self._share_mode(), S, tarr, _ffi.ptr(coefs),
-                                                  _ffi.ptr(tab), tab.numel() * 4, _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset,
-                                                  _ffi.ptr(ws), ws.numel(), _ffi.current_stream(device), int(use_graph)))
-        return self._recorded(from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W), rec, shape)
+            return self._chain2(shape, x, rec, lambda L, h, ws: L.cindm_ddpm2d_sample_ddim_force(
+                h, self.model._h, fh, _ffi.ptr(x), B, nb, share, S, tarr, _ffi.ptr(coefs), _ffi.ptr(w), _ffi.ptr(tab), tab.numel() * 4,
+                _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, *fargs, _ffi.ptr(g), _ffi.ptr(ws), ws.numel(), _ffi.ptr(wsf),
+                wsf.numel(), stream, int(use_graph)))
+        return self._chain2(shape, x, rec, lambda L, h, ws: L.cindm_ddpm2d_sample_ddim(
+            h, self.model._h, _ffi.ptr(x), B, nb, share, S, tarr, _ffi.ptr(coefs), _ffi.ptr(tab), tab.numel() * 4, _ffi.ptr(ns),
+            _ffi.ptr(nbnd), seed, sample_offset, _ffi.ptr(ws), ws.numel(), stream, int(use_graph)))
 
     @torch.no_grad()
     def sample(self, batch_size=16, design_fn=None, design_guidance="standard", num_boundaries=1,

@@ -87,15 +87,73 @@ def test_symbol_declared_exported_and_bound():
     assert b"null argument" in L.cindm_last_error()
 
 
+def _chunks(src):
+    """name -> text of every top-level function and struct of a host file, comments stripped (a chunk runs from a line that
+    starts in column 0 to the next line that starts with '}'; one-line declarations that end with ';' are not chunks)."""
+    out, lines, i = {}, [re.sub(r"//.*", "", ln).rstrip() for ln in src.split("\n")], 0
+    while i < len(lines):
+        ln = lines[i]
+        if not ln or ln[0].isspace() or ln[0] in "}#" or ln.endswith(";"):
+            i += 1
+            continue
+        j = i
+        while not (lines[j].startswith("}") or (j == i and ln.endswith("}"))):
+            j += 1
+        text = "\n".join(lines[i:j + 1])
+        head = re.sub(r"^template\s*<[^>]*>\s*", "", text)
+        m = re.match(r"struct\s+(\w+)", head) or re.search(r"(\w+)\s*\(", head)
+        out[m.group(1)] = text
+        i = j + 1
+    return out
+
+
+def _with_helpers(chunks, name):
+    """The entry `name` and every function / struct of the same file that it names, transitively."""
+    seen, todo = {}, [name]
+    while todo:
+        n = todo.pop()
+        if n in seen:
+            continue
+        seen[n] = chunks[n]
+        todo += [k for k in chunks if k not in seen and re.search(r"\b" + k + r"\b", chunks[n])]
+    return seen
+
+
+WORK = ("chain_stream(", "upload_ddim_tables(", "hipLaunchKernelGGL", "hipMemcpyAsync", "hipMemsetAsync")
+
+
 def test_entry_allocates_nothing_and_checks_before_it_launches():
     """The x_T snapshot is a slice of the caller's diffusion workspace and the tables live in the caller's buffer; every refusal
-    of the entry's own stands before its first launch or copy."""
-    src = open(os.path.join(ROOT, "cindm_amd", "csrc", "forceunet_host.inc")).read()
-    start = src.index('extern "C" int ' + NAME)
-    nxt = src.find('\nextern "C"', start + 10)
-    body = src[start:nxt if nxt > 0 else len(src)]
-    assert "force_chain_with_recovery" in body and "replay_once" in body and "ddim2d_guided_update_kernel" in body
-    assert "guided_shift2d_kernel" not in body                       # the shift is part of the update, not a second pass
-    assert not re.search(r"\bhip(Malloc|Free)\w*\s*\(", body)
-    first_work = min(body.index(k) for k in ("chain_stream(", "upload_ddim_tables(", "hipLaunchKernelGGL", "hipMemcpyAsync") if k in body)
-    assert body.rindex("REQUIRE(") < first_work
+    of the entry's own stands before its first launch or copy.  Stated over the entry and the static helpers of its file
+    (ddpm2d_host.inc) that it calls; the guided DDPM entry refuses before its first work in the same way."""
+    for entry in (NAME, "cindm_ddpm2d_sample_force"):
+        _check_entry(entry)
+
+
+def _check_entry(entry):
+    chunks = _chunks(open(os.path.join(ROOT, "cindm_amd", "csrc", "ddpm2d_host.inc")).read())
+    used = _with_helpers(chunks, entry)
+    everything = "\n".join(used.values())
+    assert not re.search(r"\bhip(Malloc|Free)\w*\s*\(", everything)
+    # the entry: its last refusal (a REQUIRE of its own or a refusal function) stands before its first work; the refusal functions
+    # themselves, and the recorder's check, issue none
+    body = used[entry]
+    first_work = min(body.index(k) for k in WORK if k in body)
+    assert "chain_stream(" in body and "run_chain2(" in body
+    assert max(body.rindex(k) for k in ("REQUIRE(", "_refuse(") if k in body) < first_work < body.index("run_chain2(")
+    assert "chain2_refuse(" in body and "force_refuse(" in body
+    for k in ("step2_refuse", "chain2_refuse", "force_refuse", "rec_begin2"):
+        assert not any(w in used[k] for w in WORK), k
+    # the chain runs under force_chain_with_recovery through replay_once
+    tail = used["run_chain2"]
+    assert "force_chain_with_recovery(" in tail and "replay_once(" in tail
+    assert "chain()" in used["force_chain_with_recovery"]
+    # the one call of the objective, on the chain's x
+    assert everything.count("cindm_airfoil_design_grad(") == 1
+    if entry == NAME:
+        # the guided DDIM step: the shift is part of the update, not a second pass
+        assert "ddim_step2" in used and "ddpm_step2" not in used
+        assert "ddim2d_guided_update_kernel" in used["run_ddim_step2"]
+        assert "guided_shift2d_kernel" not in everything
+    else:
+        assert "ddpm_step2" in used and "guided_shift2d_kernel" in used["ddpm_step2"]

@@ -397,3 +397,52 @@ def test_surrogate_exchange_timeout_is_recovered(device):
     assert m.recovered == before + 1 and bool(torch.isfinite(got).all()) and torch.equal(got, want)
     m.set_option("dbg", 0)
     assert torch.equal(m.input_grad(x, lambda_force=1.3)[1], dx_f) and m.recovered == before + 1
+
+
+def test_guided_chain_refuses_before_it_touches_the_device(device):
+    """``cindm_ddpm2d_sample_force`` refuses a surrogate that was not finalized, a ``downsampling_factor`` that does not divide the
+    image size and a misaligned surrogate workspace up front, with the reason -- not inside its first captured step, behind the x_T
+    snapshot copy: the state is bit-identical afterwards.  No chain runs (32 x 32, three-level surrogate, B = 1, nb = 2)."""
+    import ctypes as C
+    from cindm_amd import _ffi
+    from test_gpu_parity_2d import build_unet2d
+    size, B, nb, frames, mults = 32, 1, 2, 6, (1, 2, 8)
+    u, _ = build_unet2d(device, image_size=size)
+    d = cindm_amd.GaussianDiffusion(u, image_size=size, frames=frames, cond_frames=2, timesteps=1000, sampling_timesteps=1000,
+                                    loss_type="l2", coeff_ratio=0.05).to(device)
+
+    def surrogate():
+        f = cindm_amd.ForceUnet(dim=64, dim_mults=mults, channels=4, image_size=size)
+        f.load_state_dict(O.synth_state_dict_2d(O.force_unet_param_shapes(dim_mults=mults), 5), strict=True)
+        return f.to(device)
+    f, raw = surrogate(), surrogate()
+    f.sync_weights()                                  # (finalizes; `raw` has its parameters on the device and was never finalized)
+    L = _ffi.lib()
+    shape = (B, nb, 3 * frames + 3, size, size)
+    x = d._x_T(shape, None, 5, 0, device)
+    x0 = x.clone()
+    h, ws = d._prepare(B * nb, device)
+    g = torch.empty_like(x)
+    eta = (d.coeff_ratio * d.betas.flip(0)).to(device, torch.float32).contiguous()
+    nfb = L.cindm_airfoil_design_workspace_bytes(f._h, B, nb, frames)
+    assert nfb > 0
+    wsf = torch.empty(nfb + 256, dtype=torch.uint8, device=device)
+    assert wsf.data_ptr() % 256 == 0
+
+    def refused(fh, factor=4, off=0, use_graph=1):
+        rc = L.cindm_ddpm2d_sample_force(h, u._h, fh, _ffi.ptr(x), B, nb, d._share_mode(), None, None, 5, 0, 999, 998, frames, -37.7, 57.6,
+                                         1.0, 1.0, factor, 1, _ffi.ptr(eta), _ffi.ptr(g), _ffi.ptr(ws), ws.numel(),
+                                         C.c_void_p(wsf.data_ptr() + off), nfb, _ffi.current_stream(device), use_graph)
+        msg = L.cindm_last_error().decode()
+        torch.cuda.synchronize(device)
+        assert rc != 0 and torch.equal(x, x0), msg
+        return msg
+
+    for use_graph in (1, 0):
+        assert "cindm_forceunet_finalize has not been called" in refused(raw._h, use_graph=use_graph)
+        assert "downsampling_factor must divide the image size" in refused(f._h, factor=5, use_graph=use_graph)
+        assert "surrogate workspace too small (cindm_airfoil_design_workspace_bytes) or not 256-byte aligned" in refused(f._h, off=16, use_graph=use_graph)
+    # the same through the Python face (which finalizes the surrogate and aligns the workspace itself)
+    fo = cindm_amd.ForceObjective(f, B, nb, frames, p_min=-37.7, p_max=57.6, downsampling_factor=5)
+    with pytest.raises(cindm_amd.CindmError, match="downsampling_factor must divide the image size"):
+        d.sample(batch_size=B, num_boundaries=nb, design_fn=fo, design_guidance="standard-alpha", seed=5, t_stop=998)
