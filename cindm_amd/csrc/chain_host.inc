@@ -1,16 +1,61 @@
 // The chain driver: what every sampling entry (cindm_ddpm1d_sample*, cindm_ddpm2d_sample*) does around its own step.
-// Textually included by cindm_hip.hip after struct cindm_ddpm1d and before the 2-D host files; each piece exists once.
+// Textually included by cindm_hip.hip after the 1-D U-Net's host code and before ddpm1d_host.inc and the 2-D host files; each piece
+// exists once.
+//   RecSpec, DesignTables, cindm_ddpm1d, KeyBuilder   the schedule handle both sides run on, with what a chain call arms on it
 //   chain_stream        which stream a chain runs on
 //   stream_steps        the eager loop
 //   graph_capture/_run  capture a step functor into an instantiated graph; launch it n times and synchronise
 //   replay_once         the 2-D chains' replay: stream_steps, or capture + run + destroy (no cache)
 //   upload_ddim_tables  schedule check + the DDIM loops' per-step device tables
+//   RecScope            the chain recorder: taken by every chain entry
 //   DesignTablesScope   the waypoint objective's tables: taken by every chain entry, run by the two guided ones (bottom of this file)
-// On top of these, the 1-D entries (cindm_hip.hip) state their own facts once in Chain1D, chain_io, loop_chain and chain_slices, and
-// the four 2-D entries (ddpm2d_host.inc) theirs in Chain2D (the workspace layout), chain2_refuse / force_refuse, ForceGuide,
-// ddim_args2, ddpm_step2 / ddim_step2 and run_chain2.
-// The 1-D replay (replay_steps in cindm_hip.hip: graph cached in the handle by key, ping-pong pair + odd tail, flag polls) is built
+// On top of these, the six 1-D entries (ddpm1d_host.inc) state their own facts once in Chain1D (the workspace layout), step1_refuse /
+// chain1_refuse / guided_refuse, chain_io, ddim_tables1, loop_chain and guided_chain, and the four 2-D entries (ddpm2d_host.inc)
+// theirs in Chain2D (the workspace layout), chain2_refuse / force_refuse, ForceGuide, ddim_args2, ddpm_step2 / ddim_step2 and run_chain2.
+// The 1-D replay (replay_steps in ddpm1d_host.inc: graph cached in the handle by key, ping-pong pair + odd tail, flag polls) is built
 // on the same two graph functions.
+
+// A recorder as armed by the caller (buf .. streams) and as one chain runs it (the rest, filled by rec_begin)
+struct RecSpec {
+    float* buf = nullptr; int64_t buf_floats = 0; int every = 0, streams = 0;
+    int n = 0; int64_t fpr = 0; float* x0_stage = nullptr;
+};
+
+// The waypoint objective's device tables as armed by the caller (cindm_ddpm1d_set_design_tables, below)
+struct DesignTables {
+    const float* target = nullptr; const float* scale = nullptr; int target_per_design = 0, scale_per_design = 0;
+    int rows = 0, n_bodies = 0; int64_t batch = 0;
+};
+
+struct cindm_ddpm1d {
+    int T = 0;
+    float* tab = nullptr;        // 13 tables, each [T]
+    int* t_dev = nullptr;        // device step state used by the sample loops: [0] = t, [1] = block counter, [2] = DDIM step index
+    hipStream_t own = nullptr;   // capture stream used when the caller passes the legacy default stream
+    // the instantiated graph of the last captured step and everything it embeds (handles + their pack generation,
+    // descriptor, tensor / workspace pointers, batch): a loop with the same key replays it without a new capture
+    std::vector<unsigned char> gkey; hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr;
+    int last_step_launches = 0, last_step_fused = 0;     // what the last emitted reverse step consisted of (cindm_ddpm1d_last_step_info)
+    int last_chain_recovered = 0, last_chain_crowded = 0, last_chain_in_flight = 0, last_chain_range = 0;     // cindm_ddpm1d_last_chain_info
+    hipGraph_t graph1 = nullptr; hipGraphExec_t gexec1 = nullptr;      // ping-pong loops: the one-step graph that ends an odd count
+    // the chain recorder (cindm_ddpm1d_set_recorder): what the next chain call will take, the one a running chain
+    // records with (null: none) and what the last chain wrote (cindm_ddpm1d_recorder_info)
+    RecSpec rec_armed; const RecSpec* rec = nullptr; int rec_info[4] = {0, 0, 0, 0};
+    // the design tables: what the next chain call will take, and the ones a running guided chain reads (null: none)
+    DesignTables dzt_armed; const DesignTables* dzt = nullptr;
+    void drop_graph() {
+        if (gexec) (void)hipGraphExecDestroy(gexec);
+        if (graph) (void)hipGraphDestroy(graph);
+        if (gexec1) (void)hipGraphExecDestroy(gexec1);
+        if (graph1) (void)hipGraphDestroy(graph1);
+        gexec = nullptr; graph = nullptr; gexec1 = nullptr; graph1 = nullptr; gkey.clear();
+    }
+};
+
+struct KeyBuilder {
+    std::vector<unsigned char> k;
+    template <typename T> KeyBuilder& operator()(const T& v) { const auto* p = reinterpret_cast<const unsigned char*>(&v); k.insert(k.end(), p, p + sizeof(T)); return *this; }
+};
 
 // The legacy default stream cannot be captured: a graph chain handed that stream orders against it with a device synchronise
 // and runs on the handle's private stream (the graph path synchronises at the end anyway).

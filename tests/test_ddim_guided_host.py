@@ -15,6 +15,7 @@ import torch
 
 import cindm_amd
 from cindm_amd import _ffi
+from test_ddim_guided_2d_host import WORK, _chunks, _with_helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "cindm_ddpm1d_sample_ddim_guided"
@@ -34,14 +35,42 @@ def test_symbol_declared_exported_and_bound():
     assert b"null argument" in L.cindm_last_error()
 
 
+ENTRIES = ("cindm_ddpm1d_sample", "cindm_ddpm1d_sample_ddim", "cindm_ddpm1d_sample_autoregress", "cindm_ddpm1d_sample_ula",
+           "cindm_ddpm1d_sample_guided", NAME)
+
+
 def test_entry_allocates_nothing():
-    """The second state buffer is a slice of the caller's workspace: the entry's body holds no allocation (the project-wide
-    source test, test_host_logic.py::test_no_allocation_outside_create_finalize_destroy, covers the rest of the file)."""
-    src = open(os.path.join(ROOT, "cindm_amd", "csrc", "cindm_hip.hip")).read()
-    start = src.index('extern "C" int ' + NAME)
-    body = src[start:src.index('\nextern "C"', start + 10)]
-    assert "chain_slices" in body and "run_chain_with_recovery" in body and "replay_steps" in body
-    assert "hipMalloc" not in body and "hipFree" not in body
+    """The x_T snapshot, the DDIM tables and the second state buffer are slices of the caller's workspace, laid out once per call
+    by Chain1D; every refusal of an entry stands before its first launch, copy or synchronise.  Stated over each of the six 1-D
+    entries and, transitively, the helpers of its file (ddpm1d_host.inc) that it names."""
+    csrc = os.path.join(ROOT, "cindm_amd", "csrc")
+    chunks = _chunks(open(os.path.join(csrc, "ddpm1d_host.inc")).read())
+    driver = _chunks(open(os.path.join(csrc, "chain_host.inc")).read())
+    for entry in ENTRIES:
+        used = _with_helpers(chunks, entry)
+        everything = "\n".join(used.values())
+        assert not re.search(r"\bhip(Malloc|Free)\w*\s*\(", everything), entry
+        # the entry: its last refusal (a REQUIRE of its own or a refusal function) stands before its first work
+        body = used[entry]
+        assert "chain_stream(" in body
+        first_work = min(body.index(k) for k in WORK if k in body)
+        assert max(body.rindex(k) for k in ("REQUIRE(", "_refuse(") if k in body) < first_work, entry
+        stmts = [ln.strip() for ln in body[body.index(") {") + 3:].split("\n") if ln.strip()]
+        assert stmts[:2] == ["RecScope rs(h);", "DesignTablesScope ts(h);"], entry      # the call consumes what was armed however it ends
+        assert "chain1_refuse(" in body and "step1_refuse(" in used["chain1_refuse"]
+        assert ("guided_refuse(" in body) == entry.endswith("guided") and ("dzt_refuse(" in body) != entry.endswith("guided")
+        # the chain runs under run_chain_with_recovery through replay_steps
+        assert "run_chain_with_recovery" in used and "replay_steps" in used, entry
+        assert "body()" in used["run_chain_with_recovery"]
+    # the refusal functions themselves, the recorder's check and the design tables' issue no work
+    for k in ("step1_refuse", "chain1_refuse", "guided_refuse"):
+        assert not any(w in chunks[k] for w in WORK), k
+    for k in ("rec_begin", "dzt_begin", "dzt_refuse"):
+        assert not any(w in driver[k] for w in WORK), k
+    # one layout per call: Chain1D's constructor computes it, the size query is the only other caller
+    callers = sorted(k for k, v in chunks.items() if k != "step_layout" and "step_layout(" in v)
+    assert callers == ["Chain1D", "cindm_ddpm1d_workspace_bytes"]
+    assert "".join(chunks.values()).count("step_layout(") == 3
 
 
 # ------------------------------------------------------------------ routing

@@ -631,6 +631,88 @@ def test_fused_update_other_state_widths(device, F):
     assert float(res[1][0].abs().max()) > 0
 
 
+def test_1d_chains_refuse_before_they_touch_the_device(device, unet8):
+    """The 1-D chain entries refuse a workspace one byte short, a misaligned workspace, ``cond_steps > 0`` without ``cond`` and (DDIM)
+    more steps than the U-Net has timesteps up front, with the reason -- not inside their first captured step, behind the stream
+    switch, the x_T snapshot, the workspace memsets, the counter and epoch launches and the dropped graph.  After each refused call
+    the state is bit-identical and an armed recorder is consumed; afterwards the first chain repeats bit for bit (step state, epochs
+    and cached graph of the handles are usable).  Horizon 24, B = 3, three steps (odd: the ping-pong tail graph).
+    Most of this also holds where the refusals arrive late but leave x alone; what tells the two apart is the source test
+    tests/test_ddim_guided_host.py::test_entry_allocates_nothing."""
+    import ctypes as C
+    from cindm_amd import _ffi
+    m, _ = unet8
+    HZ, B, S = 24, 3, 3
+    d = cindm_amd.GaussianDiffusion1D(m, image_size=HZ, conditioned_steps=0, timesteps=1000, sampling_timesteps=S).to(device)
+    L, shape = _ffi.lib(), (B, HZ, 8)
+    desc = d._desc_for(shape, "mean-inside", 0, 4, HZ, 2)
+    no_cond = _ffi.ComposeDesc.from_buffer_copy(desc)
+    no_cond.cond_steps = 4                                 # (one window of the model's horizon: 4 prepended rows + a state of 20)
+    h, un, _ = d._prepare(desc, B, device)
+    nbytes = L.cindm_ddpm1d_workspace_bytes(h, m._h, un, C.byref(desc), B)
+    assert 0 < nbytes <= L.cindm_ddpm1d_workspace_bytes(h, m._h, un, C.byref(no_cond), B)
+    ws = torch.empty(L.cindm_ddpm1d_workspace_bytes(h, m._h, un, C.byref(no_cond), B) + 256, dtype=torch.uint8, device=device)
+    assert ws.data_ptr() % 256 == 0
+    x_T = d._init_state(shape, device, None, 5, 0, d.num_timesteps)
+    x = x_T.clone()
+    times, coefs = d.ddim_schedule()
+    tarr, carr = (C.c_int32 * (S + 1))(*times), coefs.contiguous()
+    T1 = m.timesteps + 1                                   # one step more than the U-Net's per-timestep table has rows
+    long_t, long_c = (C.c_int32 * (T1 + 1))(*range(T1 - 1, -2, -1)), torch.zeros((T1, 3))
+    dz = cindm_amd.PointObjective([0.25, -0.5], 2, coef=2.0).descriptor("standard-recurrence-2")
+    assert dz is not None and dz.recurrence == 2
+    rec_buf = torch.zeros(T1 * x.numel(), device=device)   # (large enough for every call below: the refusal is never the recorder's)
+    info = (C.c_int32 * 4)()
+    stream = lambda: _ffi.current_stream(device)
+
+    def good():
+        x.copy_(x_T)
+        with torch.cuda.device(device):
+            _ffi.check(L.cindm_ddpm1d_sample(h, m._h, un, C.byref(desc), _ffi.ptr(x), None, None, C.c_uint64(5), 0, None, 0, None,
+                                             999, 997, B, _ffi.ptr(ws), nbytes, stream(), 1))
+        torch.cuda.synchronize(device)
+        return x.clone()
+
+    def entry(name, c, w, wb, n_steps, t, co, use_graph):
+        head = (h, m._h, un, C.byref(c))
+        tail = (B, w, wb, stream(), use_graph)
+        if name == "sample":
+            return L.cindm_ddpm1d_sample(*head, _ffi.ptr(x), None, None, C.c_uint64(5), 0, None, 0, None, 999, 997, *tail)
+        if name == "ddim":
+            return L.cindm_ddpm1d_sample_ddim(*head, _ffi.ptr(x), None, n_steps, t, _ffi.ptr(co), None, C.c_uint64(5), 0, None, 0, None, *tail)
+        if name == "guided":
+            return L.cindm_ddpm1d_sample_guided(*head, C.byref(dz), _ffi.ptr(x), None, None, None, C.c_uint64(5), 0, None, 0, None, None, 0,
+                                                999, 997, *tail)
+        return L.cindm_ddpm1d_sample_ddim_guided(*head, C.byref(dz), _ffi.ptr(x), None, n_steps, t, _ffi.ptr(co), None, None, C.c_uint64(5), 0,
+                                                 None, 0, None, None, 0, *tail)
+
+    def refused(name, use_graph, c=desc, w=None, wb=nbytes, n_steps=S, t=tarr, co=carr):
+        _ffi.check(L.cindm_ddpm1d_set_recorder(h, _ffi.ptr(rec_buf), rec_buf.numel(), 1, 1))
+        with torch.cuda.device(device):
+            rc = entry(name, c, _ffi.ptr(ws) if w is None else w, wb, n_steps, t, co, use_graph)
+        msg = L.cindm_last_error().decode()
+        torch.cuda.synchronize(device)
+        assert rc != 0 and torch.equal(x, x_T), (name, use_graph, msg)
+        _ffi.check(L.cindm_ddpm1d_recorder_info(h, info))
+        assert list(info) == [0, 0, 0, 0], (name, use_graph, msg)
+        return msg
+
+    first = good()
+    assert bool(torch.isfinite(first).all()) and not torch.equal(first, x_T)
+    x.copy_(x_T)
+    for use_graph in (1, 0):
+        for name in ("sample", "ddim", "guided", "ddim_guided"):
+            assert "workspace too small" in refused(name, use_graph, wb=nbytes - 1)
+            assert "workspace must be 256-byte aligned" in refused(name, use_graph, w=C.c_void_p(ws.data_ptr() + 16))
+            assert "cond_steps > 0 requires cond" in refused(name, use_graph, c=no_cond, wb=ws.numel() - 256)
+            if "ddim" in name:
+                assert "more DDIM steps than the U-Net's timesteps" in refused(name, use_graph, n_steps=T1, t=long_t, co=long_c)
+    again = good()                                         # no recorder armed: the refused calls consumed theirs
+    _ffi.check(L.cindm_ddpm1d_recorder_info(h, info))
+    assert list(info) == [0, 0, 0, 0] and not bool(rec_buf.any())
+    assert torch.equal(again, first)
+
+
 def test_second_chain_on_a_device_goes_exchange_free_up_front(device):
     """One sampling chain per device is the rule of the exchange kernels.  Two host threads run a chain each, at the same time, on
     their own streams and their own models: the library's per-device registry sees the second chain start while the first is in
