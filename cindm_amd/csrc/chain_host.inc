@@ -8,7 +8,8 @@
 //   replay_once         the 2-D chains' replay: stream_steps, or capture + run + destroy (no cache)
 //   upload_ddim_tables  schedule check + the DDIM loops' per-step device tables
 //   RecScope            the chain recorder: taken by every chain entry
-//   DesignTablesScope   the waypoint objective's tables: taken by every chain entry, run by the two guided ones (bottom of this file)
+//   DesignTablesScope   the waypoint objective's tables: taken by every 1-D chain entry, run by the two guided ones
+//   Known2DScope        the 2-D chains' known region: taken by every chain entry, run by the four 2-D ones (bottom of this file)
 // On top of these, the six 1-D entries (ddpm1d_host.inc) state their own facts once in Chain1D (the workspace layout), step1_refuse /
 // chain1_refuse / guided_refuse, chain_io, ddim_tables1, loop_chain and guided_chain, and the four 2-D entries (ddpm2d_host.inc)
 // theirs in Chain2D (the workspace layout), chain2_refuse / force_refuse, ForceGuide, ddim_args2, ddpm_step2 / ddim_step2 and run_chain2.
@@ -27,6 +28,15 @@ struct DesignTables {
     int rows = 0, n_bodies = 0; int64_t batch = 0;
 };
 
+// The known region of a 2-D chain as armed by the caller (cindm_ddpm1d_set_known2d, below: known .. cp) and as one chain runs it
+// (the rest, filled by the entry: known2_begin in ddpm2d_host.inc)
+struct Known2D {
+    const float* known = nullptr; const unsigned char* mask = nullptr;
+    const float* zi_state = nullptr; const float* zi_bound = nullptr; const float* z_state = nullptr; const float* z_bound = nullptr;
+    int64_t zs_stride = 0, zb_stride = 0, images = 0; int hw = 0, cp = 0;
+    const int* tnext = nullptr; uint64_t seed = 0; int64_t sample_off = 0;
+};
+
 struct cindm_ddpm1d {
     int T = 0;
     float* tab = nullptr;        // 13 tables, each [T]
@@ -43,6 +53,8 @@ struct cindm_ddpm1d {
     RecSpec rec_armed; const RecSpec* rec = nullptr; int rec_info[4] = {0, 0, 0, 0};
     // the design tables: what the next chain call will take, and the ones a running guided chain reads (null: none)
     DesignTables dzt_armed; const DesignTables* dzt = nullptr;
+    // the known region of the 2-D chains: what the next chain call will take, and the one a running 2-D chain holds (null: none)
+    Known2D kn_armed; const Known2D* kn = nullptr;
     void drop_graph() {
         if (gexec) (void)hipGraphExecDestroy(gexec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -290,5 +302,47 @@ extern "C" int cindm_ddpm1d_set_design_tables(cindm_ddpm1d* h, const float* targ
     DesignTables& t = h->dzt_armed;
     t.target = target; t.scale = scale; t.target_per_design = target_per_design ? 1 : 0; t.scale_per_design = scale_per_design ? 1 : 0;
     t.rows = rows; t.n_bodies = n_bodies; t.batch = batch;
+    return 0;
+}
+
+// ---- the known region of the 2-D chains (DESIGN 4.5n) ----------------------------------------------------------------------------------
+// cindm_ddpm1d_set_known2d arms the handle; like the recorder, the next chain entry takes the region with Known2DScope -- so the call
+// consumes it however it ends -- and either refuses it (known2_refuse: every 1-D chain) or checks it against its state (known2_begin,
+// ddpm2d_host.inc) and runs with it: the chain body and the captured step read h->kn for the whole call, the re-run included.
+struct Known2DScope {
+    cindm_ddpm1d* h; Known2D k;
+    explicit Known2DScope(cindm_ddpm1d* h_) : h(h_) {
+        if (!h) return;
+        k = h->kn_armed; h->kn_armed = Known2D();
+    }
+    ~Known2DScope() { if (h) h->kn = nullptr; }
+    bool on() const { return k.known != nullptr; }
+};
+
+static int known2_refuse(const Known2DScope& ks) {
+    REQUIRE(!ks.on(), "known region: only the 2-D chains (cindm_ddpm2d_sample / _sample_ddim / _sample_force / _sample_ddim_force) hold one; "
+                      "the 1-D chains inpaint through their own arguments (inpaint_cond, initial_state_overwrite); the region was dropped");
+    return 0;
+}
+
+extern "C" int cindm_ddpm1d_set_known2d(cindm_ddpm1d* h, const float* known, const uint8_t* mask, const float* noise_init_state,
+                                        const float* noise_init_boundary, const float* noise_state_steps,
+                                        const float* noise_boundary_steps, int64_t state_step_stride, int64_t boundary_step_stride,
+                                        int64_t images, int32_t hw, int32_t cp) {
+    if (h) h->kn_armed = Known2D();      // (a refused call leaves the handle disarmed)
+    REQUIRE(h, "null handle");
+    if (!known && !mask) return 0;
+    REQUIRE(known && mask, "known region: values and mask come together (NULL, NULL disarms)");
+    REQUIRE(images >= 1 && hw >= 1 && cp >= 4 && (cp & 3) == 0, "known region: images and hw must be >= 1, cp a multiple of 4");
+    const int tapes = (noise_init_state != nullptr) + (noise_init_boundary != nullptr) + (noise_state_steps != nullptr) + (noise_boundary_steps != nullptr);
+    REQUIRE(tapes == 0 || tapes == 4, "known region: the four noise tapes come together (all NULL: the counter-based generator)");
+    REQUIRE(tapes == 0 || (state_step_stride >= 0 && boundary_step_stride >= 0), "known region: negative tape stride");
+    for (const void* p : {(const void*)known, (const void*)mask, (const void*)noise_init_state, (const void*)noise_init_boundary,
+                          (const void*)noise_state_steps, (const void*)noise_boundary_steps})
+        REQUIRE(((uintptr_t)p & 15) == 0, "known region: values, mask and tapes must be 16-byte aligned");
+    Known2D& k = h->kn_armed;
+    k.known = known; k.mask = mask; k.zi_state = noise_init_state; k.zi_bound = noise_init_boundary;
+    k.z_state = noise_state_steps; k.z_bound = noise_boundary_steps; k.zs_stride = state_step_stride; k.zb_stride = boundary_step_stride;
+    k.images = images; k.hw = hw; k.cp = cp;
     return 0;
 }

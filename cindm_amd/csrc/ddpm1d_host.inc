@@ -13,7 +13,7 @@
 //   ddim_tables1               the DDIM preamble: per-step tables into the workspace's slice
 //   loop_steps, loop_chain     the unguided loop and the chain that is one such loop
 //   guided_step, guided_chain  the recurrence iterations of a guided step and the guided chains' tail
-// An entry is: RecScope, DesignTablesScope, Chain1D, refusals, rec_begin, chain_stream, (DDIM: ddim_tables1,) chain_io plus what it
+// An entry is: RecScope, DesignTablesScope, Known2DScope, Chain1D, refusals, rec_begin, chain_stream, (DDIM: ddim_tables1,) chain_io plus what it
 // adds, and one call of loop_chain, guided_chain or its own body (the rollout).
 
 extern "C" int cindm_ddpm1d_create(const cindm_sched_desc* d, cindm_ddpm1d** out) {
@@ -628,9 +628,10 @@ extern "C" int cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_un
                                    int32_t use_graph) {
     RecScope rs(h);
     DesignTablesScope ts(h);
+    Known2DScope ks(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
-    if (dzt_refuse(ts) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0) return -1;
+    if (dzt_refuse(ts) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0) return -1;
     if (rec_begin(rs, x, nsteps, ch.n_state()) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     const StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
@@ -644,9 +645,10 @@ extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cin
                                         int64_t B, void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(h);
     DesignTablesScope ts(h);
+    Known2DScope ks(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
-    if (dzt_refuse(ts) != 0 || chain1_refuse(ch, x, cond, &dd) != 0) return -1;
+    if (dzt_refuse(ts) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, &dd) != 0) return -1;
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     if (rec_begin(rs, x, n_steps, ch.n_state()) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
@@ -668,9 +670,10 @@ extern "C" int cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pa
                                                void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(h);
     DesignTablesScope ts(h);
+    Known2DScope ks(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
-    if (dzt_refuse(ts) != 0) return -1;
+    if (dzt_refuse(ts) != 0 || known2_refuse(ks) != 0) return -1;
     REQUIRE(!rs.on(), "recorder: the autoregressive rollout is not recorded (its step index is (segment, step)); the recorder was dropped");
     REQUIRE(h && pair && c && x && cond && cond_buf && out && times && coefs && seeds, "null argument");
     REQUIRE(c->mode == CINDM_COMPOSE_PLAIN || c->mode == CINDM_COMPOSE_MULTIBODY, "the rollout runs the plain (or multibody) prediction");
@@ -721,8 +724,9 @@ extern "C" int cindm_ddpm1d_sample_ula(cindm_ddpm1d* h, cindm_unet1d* pair, cind
                                        void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(h);
     DesignTablesScope ts(h);
+    Known2DScope ks(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
-    if (dzt_refuse(ts) != 0) return -1;
+    if (dzt_refuse(ts) != 0 || known2_refuse(ks) != 0) return -1;
     REQUIRE(!rs.on(), "recorder: the Langevin chain is not recorded (its step index is (timestep, inner iteration)); the recorder was dropped");
     REQUIRE(h && pair && c && x && scalar && step_size && noise_std && tab, "null argument");
     REQUIRE(c->mode == CINDM_COMPOSE_MULTIBODY && uncond, "the Langevin phase runs the multibody composition (pair + unconditioned model)");
@@ -758,9 +762,10 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
                                           int32_t use_graph) {
     RecScope rs(h);
     DesignTablesScope ts(h);
+    Known2DScope ks(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
-    if (chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0 || guided_refuse(ch, ts, dz, 0, initial_state_overwrite, overwrite_steps) != 0) return -1;
+    if (known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0 || guided_refuse(ch, ts, dz, 0, initial_state_overwrite, overwrite_steps) != 0) return -1;
     if (rec_begin(rs, x, nsteps, ch.n_state()) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
@@ -785,9 +790,10 @@ extern "C" int cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pa
                                                void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(h);
     DesignTablesScope ts(h);
+    Known2DScope ks(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
-    if (chain1_refuse(ch, x, cond, &dd) != 0 || guided_refuse(ch, ts, dz, 1, initial_state_overwrite, overwrite_steps) != 0) return -1;
+    if (known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, &dd) != 0 || guided_refuse(ch, ts, dz, 1, initial_state_overwrite, overwrite_steps) != 0) return -1;
     REQUIRE(!inpaint_cond || (inpaint_steps >= 1 && inpaint_steps <= ch.Ltot()), "bad inpaint_steps");
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     if (rec_begin(rs, x, n_steps, ch.n_state()) != 0) return -1;

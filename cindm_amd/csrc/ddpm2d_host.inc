@@ -8,9 +8,10 @@
 //   chain2_refuse, force_refuse   what a chain entry refuses, on top of that, before it touches the device
 //   ForceGuide                 the airfoil objective of a guided chain and its one cindm_airfoil_design_grad call
 //   ddim_args2                 the Ddim2dArgs of a DDIM chain
-//   ddpm_step2, ddim_step2     the captured step: [gradient,] step, [shift,] [record node]
-//   run_chain2                 the tail: counter, rec_arm, replay -- under force_chain_with_recovery when guided -- and rec_done
-// An entry is: RecScope, refusals, rec_begin2, chain_stream, (DDIM: upload_ddim_tables,) build the step, run_chain2.
+//   known2_begin, known2_node  the known region of a chain (cindm_ddpm1d_set_known2d): its check against the state, and its launch
+//   ddpm_step2, ddim_step2     the captured step: [gradient,] step, [shift,] [known node,] [record node]
+//   run_chain2                 the tail: counter, rec_arm, [known node: rule 1,] replay -- under force_chain_with_recovery when guided -- and rec_done
+// An entry is: RecScope, Known2DScope, refusals, rec_begin2, known2_begin, chain_stream, (DDIM: upload_ddim_tables,) build the step, run_chain2.
 
 // Returns the bytes of a diffusion workspace for `images` images; the offsets of its second and third slice go to *o_unet / *o_xT.
 // The x_T snapshot serves the guided chains' recovery (force_chain_with_recovery): no allocation after *_create.
@@ -160,6 +161,37 @@ static int rec_begin2(RecScope& rs, const Chain2D& ch, const float* x, int n_ste
     return rs.on() ? rec_begin(rs, x, n_steps, ch.state_floats(), x0_refusal) : 0;
 }
 
+// The known region of a 2-D chain (DESIGN 4.5n): checked against the chain's state before the entry's first launch or copy, then held
+// by the handle for the whole call.  The draws are the chain's own (seed, sample_offset), under known2d_kernel's seed word.
+static int known2_begin(Known2DScope& ks, const Chain2D& ch, const float* x, const Draws2& z) {
+    if (!ks.on()) return 0;
+    Known2D& k = ks.k;
+    if (k.images != ch.NI() || k.hw != ch.HW() || k.cp != ch.CP())
+        return fail("known region: made for " + std::to_string(k.images) + " images of " + std::to_string(k.hw) + " pixels x " + std::to_string(k.cp) +
+                    " padded channels, the chain runs " + std::to_string(ch.NI()) + " x " + std::to_string(ch.HW()) + " x " + std::to_string(ch.CP()));
+    if (((uintptr_t)x & 15) != 0) return fail("known region: the state x must be 16-byte aligned (the node moves 16 bytes per lane)");
+    if (k.z_state && (k.zs_stride < ch.B * (int64_t)ch.HW() * (ch.u->d.channels - 3) || k.zb_stride < ch.NI() * (int64_t)ch.HW() * 3))
+        return fail("known region: a tape stride is smaller than one row ([B, H*W, C-3] state floats, [B*nb, H*W, 3] boundary floats)");
+    k.seed = z.seed; k.sample_off = z.sample_offset;
+    ks.h->kn = &ks.k;
+    return 0;
+}
+
+// the known node: init = 1 is rule 1 (the chain body's, at the first timestep), init = 0 the step's (after its counter launch)
+static int known2_node(const Chain2D& ch, float* x, int init) {
+    const Known2D& k = *ch.s->kn;
+    Known2dArgs a; std::memset(&a, 0, sizeof(a));
+    a.x = x; a.known = k.known; a.mask = k.mask;
+    a.B = (int)ch.B; a.nb = ch.nb; a.HW = ch.HW(); a.C = ch.u->d.channels; a.CP = ch.CP();
+    a.sqrt_ac = ch.s->tab + 3 * (size_t)ch.s->T; a.sqrt_1mac = ch.s->tab + 4 * (size_t)ch.s->T;
+    a.t_dev = ch.s->t_dev; a.tnext = k.tnext; a.init = init; a.init_tag = (uint32_t)ch.s->T;
+    a.zi_state = k.zi_state; a.zi_bound = k.zi_bound; a.z_state = k.z_state; a.zs_stride = k.zs_stride; a.z_bound = k.z_bound; a.zb_stride = k.zb_stride;
+    a.seed = k.seed; a.sample_off = k.sample_off;
+    hipLaunchKernelGGL(known2d_kernel, dim3(ch.update_blocks()), dim3(256), 0, ch.stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // the Step2IO of a 2-D sample loop: in-place state, per-step tapes (or counter noise), the device counter decremented by the step
 static Step2IO chain_io2(const Chain2D& ch, float* x, const Draws2& z) {
     Step2IO io{};
@@ -212,7 +244,9 @@ static auto ddpm_step2(const Chain2D& ch, const Step2IO& io, float* x, const For
             hipLaunchKernelGGL(guided_shift2d_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, ch.stream, x, g->grad, eta, ch.s->t_dev, n4);
             HIPCHK(hipGetLastError());
         }
-        // (after the step's counter launch: the word is the next timestep; the shift is a guided step's last writer of the state)
+        // (after the step's counter launch: the word is the next timestep; the shift is a guided step's last writer of the state,
+        // the known node, when a region is armed, the step's)
+        if (ch.s->kn && known2_node(ch, x, 0) != 0) return -1;
         return ch.s->rec ? rec_node(ch.s, x, 0, ch.stream) : 0;
     };
 }
@@ -226,6 +260,7 @@ static auto ddim_step2(const Chain2D& ch, const Ddim2dArgs& a, float* x, const F
     return [=](int) -> int {
         if (g && g->gradient(ch, x) != 0) return -1;
         if (run_ddim_step2(ch, a, g ? g->grad : nullptr) != 0) return -1;
+        if (ch.s->kn && known2_node(ch, x, 0) != 0) return -1;
         return ch.s->rec ? rec_node(ch.s, x, 0, ch.stream) : 0;
     };
 }
@@ -264,6 +299,7 @@ static int run_chain2(RecScope& rs, const Chain2D& ch, const ForceGuide* g, floa
     auto chain = [&]() -> int {
         hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, ch.stream, ch.s->t_dev, t0, 0ull, 0ll);
         rec_arm(ch.s, ddim ? -1 : t0, ddim ? 2 : 0, 0, ch.stream);
+        if (ch.s->kn && known2_node(ch, x, 1) != 0) return -1;      // (rule 1; a recovery re-run starts from it again)
         return replay_once(ch.stream, nsteps, ch.use_graph, step);
     };
     return rec_done(rs, g ? force_chain_with_recovery(ch, g->f, x, chain) : chain());
@@ -274,12 +310,14 @@ extern "C" int cindm_ddpm2d_sample(cindm_ddpm1d* s, cindm_unet2d* u, float* x, i
                                    int64_t sample_offset, int32_t t_start, int32_t t_end, void* ws, size_t ws_bytes,
                                    void* stream_, int32_t use_graph) {
     RecScope rs(s);
+    Known2DScope ks(s);
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
     if (chain2_refuse(ch, x, nullptr, t_start, t_end) != 0) return -1;
-    if (rec_begin2(rs, ch, x, nsteps) != 0) return -1;
+    const Draws2 z{noise_state_steps, noise_boundary_steps, seed, sample_offset};
+    if (rec_begin2(rs, ch, x, nsteps) != 0 || known2_begin(ks, ch, x, z) != 0) return -1;
     if (chain_stream(s, stream_, use_graph, &ch.stream) != 0) return -1;
-    const Step2IO io = chain_io2(ch, x, {noise_state_steps, noise_boundary_steps, seed, sample_offset});
+    const Step2IO io = chain_io2(ch, x, z);
     return run_chain2(rs, ch, nullptr, x, t_start, false, nsteps, ddpm_step2(ch, io, x));
 }
 
@@ -288,15 +326,18 @@ extern "C" int cindm_ddpm2d_sample_ddim(cindm_ddpm1d* s, cindm_unet2d* u, float*
                                         const float* noise_state_steps, const float* noise_boundary_steps, uint64_t seed,
                                         int64_t sample_offset, void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(s);
+    Known2DScope ks(s);
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const Ddim2dCall dd{n_steps, times, coefs, nullptr, tab, tab_bytes};
     if (chain2_refuse(ch, x, &dd) != 0) return -1;
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    if (rec_begin2(rs, ch, x, n_steps, kNoX0Ddim2d) != 0) return -1;
+    const Draws2 z{noise_state_steps, noise_boundary_steps, seed, sample_offset};
+    if (rec_begin2(rs, ch, x, n_steps, kNoX0Ddim2d) != 0 || known2_begin(ks, ch, x, z) != 0) return -1;
     if (chain_stream(s, stream_, use_graph, &ch.stream) != 0) return -1;
     int* tn_dev = nullptr;      // the per-step tables go to the caller's device buffer
     if (upload_ddim_tables(s->T, n_steps, times, coefs, (float*)tab, ch.stream, &tn_dev) != 0) return -1;
-    const Ddim2dArgs a = ddim_args2(ch, x, dd, tn_dev, {noise_state_steps, noise_boundary_steps, seed, sample_offset});
+    ks.k.tnext = tn_dev;
+    const Ddim2dArgs a = ddim_args2(ch, x, dd, tn_dev, z);
     return run_chain2(rs, ch, nullptr, x, times[0], true, n_steps, ddim_step2(ch, a, x));
 }
 
@@ -309,13 +350,15 @@ extern "C" int cindm_ddpm2d_sample_force(cindm_ddpm1d* s, cindm_unet2d* u, cindm
                                          const float* eta, float* grad, void* ws, size_t ws_bytes, void* ws_force,
                                          size_t ws_force_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(s);
+    Known2DScope ks(s);
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const ForceGuide g{f, frames, p_min, p_max, lambda_force, lambda_overlap, down_factor, sum_boundary, grad, ws_force, ws_force_bytes};
     const int nsteps = t_start - t_end + 1;
     if (chain2_refuse(ch, x, nullptr, t_start, t_end) != 0 || force_refuse(ch, g, x, eta) != 0) return -1;
-    if (rec_begin2(rs, ch, x, nsteps) != 0) return -1;
+    const Draws2 z{noise_state_steps, noise_boundary_steps, seed, sample_offset};
+    if (rec_begin2(rs, ch, x, nsteps) != 0 || known2_begin(ks, ch, x, z) != 0) return -1;
     if (chain_stream(s, stream_, use_graph, &ch.stream) != 0) return -1;
-    const Step2IO io = chain_io2(ch, x, {noise_state_steps, noise_boundary_steps, seed, sample_offset});
+    const Step2IO io = chain_io2(ch, x, z);
     return run_chain2(rs, ch, &g, x, t_start, false, nsteps, ddpm_step2(ch, io, x, &g, eta));
 }
 
@@ -328,15 +371,18 @@ extern "C" int cindm_ddpm2d_sample_ddim_force(cindm_ddpm1d* s, cindm_unet2d* u, 
                                               int32_t sum_boundary, float* grad, void* ws, size_t ws_bytes, void* ws_force,
                                               size_t ws_force_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(s);
+    Known2DScope ks(s);
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const Ddim2dCall dd{n_steps, times, coefs, weights, tab, tab_bytes};
     const ForceGuide g{f, frames, p_min, p_max, lambda_force, lambda_overlap, down_factor, sum_boundary, grad, ws_force, ws_force_bytes};
     if (chain2_refuse(ch, x, &dd) != 0 || force_refuse(ch, g, x, weights) != 0) return -1;
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    if (rec_begin2(rs, ch, x, n_steps, kNoX0Ddim2d) != 0) return -1;
+    const Draws2 z{noise_state_steps, noise_boundary_steps, seed, sample_offset};
+    if (rec_begin2(rs, ch, x, n_steps, kNoX0Ddim2d) != 0 || known2_begin(ks, ch, x, z) != 0) return -1;
     if (chain_stream(s, stream_, use_graph, &ch.stream) != 0) return -1;
     int* tn_dev = nullptr;
     if (upload_ddim_tables(s->T, n_steps, times, coefs, (float*)tab, ch.stream, &tn_dev, weights) != 0) return -1;
-    const Ddim2dArgs a = ddim_args2(ch, x, dd, tn_dev, {noise_state_steps, noise_boundary_steps, seed, sample_offset});
+    ks.k.tnext = tn_dev;
+    const Ddim2dArgs a = ddim_args2(ch, x, dd, tn_dev, z);
     return run_chain2(rs, ch, &g, x, times[0], true, n_steps, ddim_step2(ch, a, x, &g));
 }

@@ -3037,4 +3037,93 @@ __global__ void fill_noise2d_kernel(float* x, int B, int nb, int HW, int C, int 
     *reinterpret_cast<float4*>(x + (size_t)i * 4) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Replacement conditioning of the 2-D chains (cindm_ddpm1d_set_known2d): one more node of the captured step, after
+// the step's update, guidance shift and counter.  The known region (mask) of the state is put on the forward-diffusion trajectory
+// of its clean values k at the level the state has just reached:
+//   x[m] = q(k, level, z) = sqrt_ac[level] k + sqrt_1mac[level] z   for level >= 0,    x[m] = k   for level < 0
+// (the two products and the sum round once each, as the torch expression does).  level: init = 1 (rule 1, before the first step):
+// t_dev[0], the chain's first timestep; a DDPM step: t_dev[0], which the step's counter has already decremented; a DDIM step:
+// tnext[t_dev[2] - 1], the time_next of the step the counter has just left.  z as sample_noise (:775-785): state channels per
+// design, boundary channels per image; from the caller's rows when given -- the init rows, or row t = level + 1 (DDPM) / the step
+// index (DDIM), as the step rows are indexed -- else from the counter-based generator under seed ^ kKnown2dSeed, keyed
+// (design / image, level; the init draw: init_tag = T, which no level equals).  Drawn at every level >= 0, whatever the DDIM sigma.
+// mask: one byte per (image, pixel, channel group of four), bit j = channel 4 g + j is known; padded channels are never known, so
+// they stay zero.  Threads as ddim2d_update_kernel: one per (design, pixel, channel group) across the nb copies, so the shared
+// state draw is made once; a thread whose group holds nothing known returns after its nb byte loads, and an image's group that is
+// known whole is stored without being read.  16-byte loads and stores.
+static constexpr uint64_t kKnown2dSeed = 0x6b6e6f776e326421ull;
+struct Known2dArgs {
+    float* x; const float* known; const unsigned char* mask;
+    int B, nb, HW, C, CP;
+    const float* sqrt_ac; const float* sqrt_1mac;
+    const int* t_dev; const int* tnext;                     // tnext null: a DDPM chain
+    int init; uint32_t init_tag;
+    const float* zi_state; const float* zi_bound;           // [B, HW, C-3] / [B*nb, HW, 3] or null
+    const float* z_state; int64_t zs_stride;                // [rows][B, HW, C-3] or null
+    const float* z_bound; int64_t zb_stride;                // [rows][B*nb, HW, 3]
+    uint64_t seed; int64_t sample_off;
+};
+__global__ __launch_bounds__(256) void known2d_kernel(const Known2dArgs a) {
+    const int G = a.CP >> 2;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    int level, row = 0;
+    if (a.init) level = uniform_word(a.t_dev);
+    else if (a.tnext) { row = uniform_word(a.t_dev + 2) - 1; level = uniform_word(a.tnext + row); }
+    else { level = uniform_word(a.t_dev); row = level + 1; }
+    if (i >= a.B * a.HW * G) return;
+    const int g = i % G;
+    const int bp = i / G;
+    const int pix = bp % a.HW;
+    const int b = bp / a.HW;
+    const int c0 = 4 * g, Cs = a.C - 3;
+    unsigned any = 0;
+    for (int k = 0; k < a.nb; ++k) any |= a.mask[(((size_t)(b * a.nb + k) * a.HW) + pix) * G + g];
+    if (!any) return;
+    const bool noisy = level >= 0;
+    const float sa = noisy ? a.sqrt_ac[level] : 1.f, sm = noisy ? a.sqrt_1mac[level] : 0.f;
+    const uint32_t tag = a.init ? a.init_tag : (uint32_t)level;
+    const float* rs = a.init ? a.zi_state : a.z_state ? a.z_state + (size_t)row * a.zs_stride : nullptr;
+    const float* rb = a.init ? a.zi_bound : a.z_bound ? a.z_bound + (size_t)row * a.zb_stride : nullptr;
+    const unsigned real = c0 + 4 <= a.C ? 0xfu : c0 < a.C ? (1u << (a.C - c0)) - 1u : 0u;      // the group's channels that are not padding
+    float zs[4] = {0.f, 0.f, 0.f, 0.f};
+    if (noisy && c0 < Cs) {
+        if (rs) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (c0 + j < Cs) zs[j] = rs[((size_t)b * a.HW + pix) * Cs + c0 + j];
+        } else {
+            noise2d_state4(a.seed ^ kKnown2dSeed, a.sample_off + b, tag, (uint32_t)pix, G, g, zs);
+        }
+    }
+    for (int k = 0; k < a.nb; ++k) {
+        const int im = b * a.nb + k;
+        const unsigned mb = a.mask[(((size_t)im * a.HW) + pix) * G + g] & real;
+        if (!mb) continue;
+        const size_t o = (((size_t)im * a.HW) + pix) * a.CP + c0;
+        const float4 k4 = *reinterpret_cast<const float4*>(a.known + o);
+        // (a group that is known whole is not read: its padded channels, if any, are zero in the state and stay zero)
+        const float4 x4 = mb == real ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(a.x + o);
+        const float kv[4] = {k4.x, k4.y, k4.z, k4.w}, xv[4] = {x4.x, x4.y, x4.z, x4.w};
+        float zb[4] = {0.f, 0.f, 0.f, 0.f};
+        if (noisy && c0 + 3 >= Cs && c0 < a.C) {
+            if (rb) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (c0 + j >= Cs && c0 + j < a.C) zb[j] = rb[((size_t)im * a.HW + pix) * 3 + (c0 + j - Cs)];
+            } else {
+                noise2d_bound4(a.seed ^ kKnown2dSeed, (a.sample_off + b) * a.nb + k, tag, (uint32_t)pix, G, g, zb);
+            }
+        }
+        float r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j;
+            const float q = noisy ? __fadd_rn(__fmul_rn(sa, kv[j]), __fmul_rn(sm, c < Cs ? zs[j] : zb[j])) : kv[j];
+            r[j] = ((mb >> j) & 1u) ? q : xv[j];
+        }
+        *reinterpret_cast<float4*>(a.x + o) = make_float4(r[0], r[1], r[2], r[3]);
+    }
+}
+
 }  // namespace cindm

@@ -13,6 +13,10 @@ What runs where
     advanced on the device).  The reference's own 2-D DDIM cannot run; the semantics are defined in ``ddim_sample``.
   * DDIM with ``design_fn=ForceObjective`` under ``"standard-alpha"`` is ONE call as well (``cindm_ddpm2d_sample_ddim_force``:
     surrogate gradient + U-Net + one update that carries the guidance shift, per captured step).
+  * Replacement conditioning (``known=`` / ``known_mask=`` / ``cond=`` of the sampling calls): a known region of the state rides
+    the forward-diffusion trajectory of its clean values inside the captured step of all four library chains (known2d_kernel,
+    ``cindm_ddpm1d_set_known2d``) and comes back exactly; the reference's 2-D sampler takes no condition, the semantics are
+    defined in ``p_sample_loop`` / ``ddim_sample``.
 Training, self-conditioning, DDIM with any other ``design_fn`` / guidance, DDIM with share_noise=False and
 return_all_timesteps are outside this build's scope and raise NotImplementedError.
 """
@@ -35,10 +39,18 @@ ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"]) 
 class NoiseTape2D:
     """Explicit noise for parity runs, replacing the reference's ``sample_noise`` draws (:775-785):
     ``init`` = (state [B,1,C-3,H,W], boundary [B,nb,3,H,W]) for x_T (:895);
-    ``step_state`` [T,B,1,C-3,H,W] / ``step_boundary`` [T,B,nb,3,H,W] indexed by timestep (:807)."""
+    ``step_state`` [T,B,1,C-3,H,W] / ``step_boundary`` [T,B,nb,3,H,W] indexed by timestep (:807).
+    ``known_init`` / ``known_state`` / ``known_boundary`` (all three or none): the draws of the known region's forward
+    diffusion (``known=`` / ``cond=`` of the sampling calls), shaped and indexed like ``init`` and the step rows -- by t for
+    DDPM, by the DDIM step index for DDIM."""
 
-    def __init__(self, init, step_state, step_boundary):
+    def __init__(self, init, step_state, step_boundary, known_init=None, known_state=None, known_boundary=None):
         self.init, self.step_state, self.step_boundary = init, step_state, step_boundary
+        self.known_init, self.known_state, self.known_boundary = known_init, known_state, known_boundary
+
+
+# the seed word of the known region's counter-based draws (known2d_kernel's kKnown2dSeed): distinct from the step draws'
+KNOWN_SEED = 0x6b6e6f776e326421
 
 
 def _state_cl(s):
@@ -136,6 +148,112 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
         state = torch.randn((shape[0], 1, shape[2] - 3, shape[3], shape[4]), device=device)
         boundary = torch.randn((shape[0], shape[1], 3, shape[3], shape[4]), device=device)
         return torch.cat([state.expand(-1, shape[1], -1, -1, -1), boundary], dim=2)
+
+    # ------------------------------------------------------------------ replacement conditioning (known region)
+    def _known_region(self, shape, known, known_mask, cond, noise=None, rows=0):
+        """The known region of a sampling call as (values [B, nb, C, H, W] fp32, mask bool of that shape), or None.  Host checks
+        only (ValueError), made before any device work: shapes, ``cond=`` against ``known=``, the state channels of values and
+        mask identical over the boundary copies of a design, and the tape's known rows (``rows`` of them at least)."""
+        if known is None and cond is None:
+            if known_mask is not None:
+                raise ValueError("known_mask without known")
+            return None
+        B, nb, Cc, H, W = shape
+        k = torch.zeros(tuple(shape), dtype=torch.float32, device=(known if known is not None else cond).device)
+        m = torch.zeros(tuple(shape), dtype=torch.bool, device=k.device)
+        if known is not None:
+            if known_mask is None:
+                raise ValueError("known needs known_mask (bool, broadcastable to [B, nb, C, H, W])")
+            if tuple(known.shape) != tuple(shape):
+                raise ValueError(f"known must have the shape of the state {tuple(shape)}, got {tuple(known.shape)}")
+            if known_mask.dtype != torch.bool:
+                raise ValueError("known_mask must be a bool tensor")
+            try:
+                m = torch.broadcast_to(known_mask.to(k.device), tuple(shape)).clone()
+            except RuntimeError as e:
+                raise ValueError(f"known_mask {tuple(known_mask.shape)} does not broadcast to {tuple(shape)}") from e
+            if known_mask.dim() > len(shape):
+                raise ValueError(f"known_mask {tuple(known_mask.shape)} does not broadcast to {tuple(shape)}")
+            k = known.to(torch.float32).clone()
+        if cond is not None:
+            nc = 3 * self.cond_frames
+            if tuple(cond.shape) != (B, nc, H, W):
+                raise ValueError(f"cond must be [B, 3 * cond_frames, H, W] = {(B, nc, H, W)}, got {tuple(cond.shape)}")
+            if bool(m[:, :, :nc].any()):
+                raise ValueError("cond= and known= name the same channels (the first 3 * cond_frames): give one of them there")
+            k[:, :, :nc] = cond.to(k.device, torch.float32)[:, None]
+            m[:, :, :nc] = True
+        ms, ks = m[:, :, :-3], torch.where(m[:, :, :-3], k[:, :, :-3], torch.zeros((), device=k.device))
+        if not (bool((ms == ms[:, :1]).all()) and bool((ks == ks[:, :1]).all())):
+            raise ValueError("the state channels of known / known_mask must be identical over the boundary copies of a design "
+                             "(the chains share those channels over the boundary axis)")
+        if noise is not None:
+            parts = (noise.known_init, noise.known_state, noise.known_boundary)
+            if any(q is None for q in parts):
+                raise ValueError("a noise tape used with a known region needs known_init, known_state and known_boundary")
+            ki, kst, kb = parts
+            if (len(ki) != 2 or tuple(ki[0].shape) != (B, 1, Cc - 3, H, W) or tuple(ki[1].shape) != (B, nb, 3, H, W)
+                    or kst.dim() != 6 or kb.dim() != 6 or kst.shape[0] < rows or kb.shape[0] < rows
+                    or tuple(kst.shape[1:]) != (B, 1, Cc - 3, H, W) or tuple(kb.shape[1:]) != (B, nb, 3, H, W)):
+                raise ValueError(f"the noise tape needs known_init ([{B}, 1, {Cc - 3}, {H}, {W}], [{B}, {nb}, 3, {H}, {W}]), known_state "
+                                 f"[>= {rows}, {B}, 1, {Cc - 3}, {H}, {W}] and known_boundary [>= {rows}, {B}, {nb}, 3, {H}, {W}]")
+        return k, m
+
+    def known_replace(self, shape, x, known, known_mask, t, z=None):
+        """The definition of the known region in torch (what the library's known2d_kernel does inside the captured
+        step, and what the routes that loop in Python call): ``x[m] = q(k, t, z)`` for ``t >= 0``, ``x[m] = k`` for ``t < 0``,
+        with ``q = sqrt_alphas_cumprod[t] * k + sqrt_one_minus_alphas_cumprod[t] * z``.  x [B*nb, C, H, W] (or [B, nb, C, H, W]);
+        ``z``: a (state [B, 1, C-3, H, W], boundary [B, nb, 3, H, W]) pair -- the state draw is shared over the boundary copies --
+        or a full tensor, or None for ``sample_noise``.  Returns a new tensor shaped like x."""
+        B, nb, Cc, H, W = shape
+        t = int(t)
+        xs = x.reshape(shape)
+        k = known.reshape(shape).to(xs.device, xs.dtype)
+        m = torch.broadcast_to(known_mask.to(xs.device), tuple(shape))
+        if t < 0:
+            q = k
+        else:
+            if z is None:
+                z = self.sample_noise(shape, xs.device)
+            elif isinstance(z, (tuple, list)):
+                z = torch.cat([z[0].expand(-1, nb, -1, -1, -1), z[1]], dim=2)
+            z = z.reshape(shape).to(xs.device, xs.dtype)
+            q = self.sqrt_alphas_cumprod[t].to(xs.device) * k + self.sqrt_one_minus_alphas_cumprod[t].to(xs.device) * z
+        return torch.where(m, q, xs).reshape(x.shape)
+
+    def _known_z(self, shape, noise, row, tag, seed, sample_offset, device):
+        """The z of one overwrite on the routes that loop in Python -- the tape's known rows (``row`` None: known_init), else the
+        library's counter-based draw under the known region's seed word, keyed like known2d_kernel keys it (``tag``)."""
+        B, nb, Cc, H, W = shape
+        if noise is not None:
+            return noise.known_init if row is None else (noise.known_state[row], noise.known_boundary[row])
+        cp = self.model.padded_channels
+        z = torch.empty((B * nb, H * W, cp), dtype=torch.float32, device=device)
+        with torch.cuda.device(device):
+            _ffi.check(_ffi.lib().cindm_fill_noise2d(_ffi.ptr(z), B, nb, H * W, Cc, cp, (int(seed) ^ KNOWN_SEED) & (2 ** 64 - 1), sample_offset,
+                                                     int(tag), _ffi.current_stream(device)))
+        return from_device_layout(z, Cc, H, W)
+
+    def _known_arm(self, h, kn, shape, noise, rows, device):
+        """Arms the library handle with the known region for the next chain call (``cindm_ddpm1d_set_known2d``): values and the
+        packed mask (one byte per channel group of four) in the library's layout, the tape's known rows channel-last.  Returns
+        the device tensors, which the caller keeps alive over the chain call."""
+        B, nb, Cc, H, W = shape
+        cp = self.model.padded_channels
+        k, m = kn
+        kd = to_device_layout(k.reshape(B * nb, Cc, H, W).to(device, torch.float32), cp)
+        md = to_device_layout(m.reshape(B * nb, Cc, H, W).to(device, torch.float32), cp).reshape(B * nb, H * W, cp // 4, 4)
+        bits = (md * torch.tensor([1.0, 2.0, 4.0, 8.0], device=device)).sum(-1).to(torch.uint8).contiguous()
+        zi_s = zi_b = z_s = z_b = None
+        if noise is not None:
+            zi_s = _state_cl(noise.known_init[0].to(device, torch.float32))
+            zi_b = _boundary_cl(noise.known_init[1].to(device, torch.float32))
+            z_s = _state_cl(noise.known_state[rows].to(device, torch.float32))
+            z_b = _boundary_cl(noise.known_boundary[rows].to(device, torch.float32))
+        _ffi.check(_ffi.lib().cindm_ddpm1d_set_known2d(h, _ffi.ptr(kd), _ffi.ptr(bits), _ffi.ptr(zi_s), _ffi.ptr(zi_b), _ffi.ptr(z_s),
+                                                       _ffi.ptr(z_b), 0 if z_s is None else z_s[0].numel(),
+                                                       0 if z_b is None else z_b[0].numel(), B * nb, H * W, cp))
+        return kd, bits, zi_s, zi_b, z_s, z_b
 
     # ------------------------------------------------------------------ one reverse step
     @torch.no_grad()
@@ -303,13 +421,14 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
             return from_device_layout(rows.reshape(n * B * nb, H * W, cp), Cc, H, W).reshape(n, B, nb, Cc, H, W)
         return out, rec.collect(self._handle(), unpack)
 
-    def _chain2(self, shape, x, rec, call):
-        """One library chain on the state ``x`` (device layout, updated in place): the workspace, the recorder armed, the entry
-        ``call(L, h, ws)`` and what the sampling call returns."""
+    def _chain2(self, shape, x, rec, call, known=None):
+        """One library chain on the state ``x`` (device layout, updated in place): the workspace, the recorder and the known
+        region (``known`` = (region, tape, its rows)) armed, the entry ``call(L, h, ws)`` and what the sampling call returns."""
         B, nb, Cc, H, W = shape
         h, ws = self._prepare(B * nb, x.device)
         if rec is not None:
             rec.arm(h)
+        keep = None if known is None else self._known_arm(h, known[0], shape, known[1], known[2], x.device)      # (alive over the call)
         with torch.cuda.device(x.device):
             _ffi.check(call(_ffi.lib(), h, ws))
         return self._recorded(from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W), rec, shape)
@@ -331,17 +450,31 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
     @torch.no_grad()
     def p_sample_loop(self, shape, design_fn=None, design_guidance="standard", return_all_timesteps=None, *,
                       noise=None, seed=0, sample_offset=0, use_graph=True, t_stop=0, device=None, fused=True,
-                      return_trajectory_every=None, trajectory=("x",)):
+                      return_trajectory_every=None, trajectory=("x",), known=None, known_mask=None, cond=None):
         """:893-907.  Returns [B, nb, C, H, W].  ``noise``: a NoiseTape2D (parity runs); otherwise x_T and the
         per-step draws come from the library's counter-based generator keyed by (seed, sample_offset + design).
         ``return_trajectory_every=k`` with ``trajectory=("x",)`` / ``("x", "x0")``: returns (designs, ChainRecord) with the state
         [n_records, B, nb, C, H, W] after every k-th step and after the last one (record.py; recorded inside the captured step on the
-        library routes, cloned per step on the routes that loop in Python)."""
+        library routes, cloned per step on the routes that loop in Python).
+        Replacement conditioning (build-only; the reference's 2-D sampler takes no condition): ``known`` [B, nb, C, H, W] with
+        ``known_mask`` (bool, broadcastable to it) names a region of the state and its clean values k; ``cond`` [B, 3 * cond_frames,
+        H, W] is the convenience for "the first 3 * cond_frames channels are known on every boundary copy" (on the same channels
+        as ``known`` it is a ValueError).  With q(k, t, z) = sqrt_alphas_cumprod[t] k + sqrt_one_minus_alphas_cumprod[t] z:
+        before the first step, at t0 = T - 1, x[m] = q(k, t0, z_init); after the step at t (its update and guidance shift),
+        x[m] = q(k, t - 1, z) for t >= 1 and x[m] = k after t = 0 -- so the result carries k exactly (with ``t_stop`` > 0 the chain
+        ends at level t_stop - 1, like the rest of its state).  z is drawn like ``sample_noise`` at every step (tape rows
+        ``known_init`` / ``known_state[t]`` / ``known_boundary[t]``, else the counter-based generator under a seed word of its own).
+        This differs on purpose from the 1-D inpainting, which copies the reference: level t after the step at t, and nothing on
+        the last DDIM pair.  The state channels of known and mask must be identical over the boundary copies (ValueError).  Inside
+        the captured step on the library routes (known2d_kernel), ``known_replace`` on the routes that loop in Python; a recorder
+        records after the overwrite."""
         B, nb, Cc, H, W = shape
+        T = self.num_timesteps
+        kn = self._known_region(shape, known, known_mask, cond, noise, T)
         device = device or self.betas.device
         if device.type != "cuda":
             raise _ffi.CindmError("sampling needs a ROCm device; there is no CPU execution path")
-        T = self.num_timesteps
+        karm = None if kn is None else (kn, noise, slice(None))
         # (the device record buffer is allocated only on the routes that are library chains)
         device_rec = lambda: self._recorder(return_trajectory_every, trajectory, T - int(t_stop), shape, device, t_start=T - 1)
         x = self._x_T(shape, noise, seed, sample_offset, device)
@@ -350,7 +483,7 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
             ns, nbnd = self._tape_cl(noise, device)
             return self._chain2(shape, x, device_rec(), lambda L, h, ws: L.cindm_ddpm2d_sample(
                 h, self.model._h, _ffi.ptr(x), B, nb, share, _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, T - 1, int(t_stop),
-                _ffi.ptr(ws), ws.numel(), stream, int(use_graph)))
+                _ffi.ptr(ws), ws.numel(), stream, int(use_graph)), karm)
         from .forceunet import ForceObjective
         if isinstance(design_fn, ForceObjective) and design_guidance == "standard-alpha" and fused:
             # the library's own objective: surrogate forward + input gradient, the reverse step and the guidance shift are
@@ -360,15 +493,20 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
             ns, nbnd = self._tape_cl(noise, device)
             return self._chain2(shape, x, device_rec(), lambda L, h, ws: L.cindm_ddpm2d_sample_force(
                 h, self.model._h, fh, _ffi.ptr(x), B, nb, share, _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, T - 1, int(t_stop),
-                *fargs, _ffi.ptr(eta), _ffi.ptr(g), _ffi.ptr(ws), ws.numel(), _ffi.ptr(wsf), wsf.numel(), stream, int(use_graph)))
+                *fargs, _ffi.ptr(eta), _ffi.ptr(g), _ffi.ptr(ws), ws.numel(), _ffi.ptr(wsf), wsf.numel(), stream, int(use_graph)), karm)
         # this route loops in Python: the same record, cloned per step
         rec = None if return_trajectory_every is None else LoopRecorder(T - int(t_stop), return_trajectory_every, trajectory, t_start=T - 1)
         img = from_device_layout(x, Cc, H, W)
+        if kn is not None:
+            img = self.known_replace(shape, img, kn[0], kn[1], T - 1, self._known_z(shape, noise, None, T, seed, sample_offset, device))
         for i, t in enumerate(reversed(range(int(t_stop), T))):
             nz = None
             if noise is not None and t > 0:
                 nz = torch.cat([noise.step_state[t].expand(-1, nb, -1, -1, -1), noise.step_boundary[t]], dim=2)
             img, x_start = self.p_sample(shape, img, t, None, design_fn=design_fn, design_guidance=design_guidance, noise=nz)
+            if kn is not None:
+                img = self.known_replace(shape, img, kn[0], kn[1], t - 1,
+                                         None if t == 0 else self._known_z(shape, noise, t, t - 1, seed, sample_offset, device))
             if rec is not None:
                 rec.after(i, img, x_start)
         return self._recorded(img.reshape(B, nb, Cc, H, W), rec, shape)
@@ -385,7 +523,7 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
     @torch.no_grad()
     def ddim_sample(self, shape, design_fn=None, design_guidance="standard", return_all_timesteps=False, *, noise=None, seed=0,
                     sample_offset=0, use_graph=True, init_img=None, step_range=None, device=None, fused=True,
-                    return_trajectory_every=None, trajectory=("x",)):
+                    return_trajectory_every=None, trajectory=("x",), known=None, known_mask=None, cond=None):
         """DDIM sampling of the 2-D path (:910-949; the reference's own body cannot run, so this build defines it from its
         working pieces).  Returns [B, nb, C, H, W].  With (times, coefs) = ddim_schedule(), for each pair (t, t_next):
         (pred_noise, x_start) = model_predictions(x, t, clip_x_start=True, rederive_pred_noise=True, share_noise=True);
@@ -402,6 +540,12 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
         deterministic sampler amplifies a 1e-6 difference of the U-Net to 1e-3 over long chains).
         ``return_trajectory_every`` / ``trajectory``: as p_sample_loop, steps counted from the first step this call runs; the stream
         ``x`` only -- the 2-D DDIM update kernels have no x0 operand.
+        Replacement conditioning: ``known`` / ``known_mask`` / ``cond`` as p_sample_loop (build-only).  Before the first step this
+        call runs, at t0 = times[i0], x[m] = q(k, t0, z_init); after the step of the pair (t, t_next) -- its update and guidance
+        shift -- x[m] = q(k, t_next, z) when t_next >= 0 and x[m] = k when t_next < 0, so the result carries k exactly.  z is drawn
+        like sample_noise at every step, whatever sigma is (tape rows ``known_init`` / ``known_state[i]`` / ``known_boundary[i]`` by
+        DDIM step index).  This differs on purpose from the 1-D inpainting, which copies the reference: level t after the step at
+        t, and nothing on the last DDIM pair.  A recorder records after the overwrite.
         Refused (NotImplementedError): any other ``design_fn`` or guidance (the reference has no working guided 2-D DDIM),
         share_noise False and ``return_all_timesteps``."""
         from .forceunet import ForceObjective
@@ -417,6 +561,8 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
         if return_trajectory_every is not None and stream_mask(trajectory) & 2:
             raise NotImplementedError("trajectory 'x0' in 2-D DDIM: the DDIM update kernels have no x0 operand (the DDPM loop records it)")
         B, nb, Cc, H, W = shape
+        kn = self._known_region(shape, known, known_mask, cond, noise,
+                                (len(self.ddim_schedule()[0]) - 1) if step_range is None else int(step_range[1]))
         device = device or self.betas.device
         if device.type != "cuda":
             raise _ffi.CindmError("sampling needs a ROCm device; there is no CPU execution path")
@@ -442,11 +588,18 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
             img = from_device_layout(x, Cc, H, W)
             lrec = None if return_trajectory_every is None else \
                 LoopRecorder(i1 - i0, return_trajectory_every, trajectory, times=times[i0:i1 + 1])
+            if kn is not None:
+                img = self.known_replace(shape, img, kn[0], kn[1], times[i0], self._known_z(shape, noise, None, self.num_timesteps, seed,
+                                                                                           sample_offset, device))
             for i in range(i0, i1):
                 g = fo(img)
                 img = self.ddim_sample(shape, noise=noise, seed=seed, sample_offset=sample_offset, use_graph=use_graph, init_img=img,
                                        step_range=(i, i + 1), device=device).reshape(B * nb, Cc, H, W)
                 img = img - w[i] * g
+                if kn is not None:
+                    tn = times[i + 1]
+                    img = self.known_replace(shape, img, kn[0], kn[1], tn,
+                                             None if tn < 0 else self._known_z(shape, noise, i, tn, seed, sample_offset, device))
                 if lrec is not None:
                     lrec.after(i - i0, img)
             return self._recorded(img.reshape(B, nb, Cc, H, W), lrec, shape)
@@ -454,6 +607,7 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
         S = len(times) - 1
         rec = self._recorder(return_trajectory_every, trajectory, S, shape, device, times=times)
         ns, nbnd = self._tape_cl(noise, device, slice(i0, i1))
+        karm = None if kn is None else (kn, noise, slice(i0, i1))
         # the per-step device tables live in a caller tensor (the library allocates nothing): [S][4] coefficients + [S] time_next
         if self._ddim_tab is None or self._ddim_tab.numel() < 5 * S or self._ddim_tab.device != device:
             self._ddim_tab = torch.empty(5 * max(S, self.sampling_timesteps), dtype=torch.float32, device=device)
@@ -468,16 +622,17 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
             return self._chain2(shape, x, rec, lambda L, h, ws: L.cindm_ddpm2d_sample_ddim_force(
                 h, self.model._h, fh, _ffi.ptr(x), B, nb, share, S, tarr, _ffi.ptr(coefs), _ffi.ptr(w), _ffi.ptr(tab), tab.numel() * 4,
                 _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, *fargs, _ffi.ptr(g), _ffi.ptr(ws), ws.numel(), _ffi.ptr(wsf),
-                wsf.numel(), stream, int(use_graph)))
+                wsf.numel(), stream, int(use_graph)), karm)
         return self._chain2(shape, x, rec, lambda L, h, ws: L.cindm_ddpm2d_sample_ddim(
             h, self.model._h, _ffi.ptr(x), B, nb, share, S, tarr, _ffi.ptr(coefs), _ffi.ptr(tab), tab.numel() * 4, _ffi.ptr(ns),
-            _ffi.ptr(nbnd), seed, sample_offset, _ffi.ptr(ws), ws.numel(), stream, int(use_graph)))
+            _ffi.ptr(nbnd), seed, sample_offset, _ffi.ptr(ws), ws.numel(), stream, int(use_graph)), karm)
 
     @torch.no_grad()
     def sample(self, batch_size=16, design_fn=None, design_guidance="standard", num_boundaries=1,
                return_all_timesteps=False, **kw):
         """:960-963 (``sampling_timesteps < timesteps``: ddim_sample).  ``kw``: the build-only keywords of p_sample_loop /
-        ddim_sample, ``return_trajectory_every=`` / ``trajectory=`` among them."""
+        ddim_sample, ``return_trajectory_every=`` / ``trajectory=`` and the replacement conditioning ``known=`` / ``known_mask=`` /
+        ``cond=`` among them."""
         S = self.image_size
         shape = (batch_size, num_boundaries, self.channels, S, S)
         if self.is_ddim_sampling:

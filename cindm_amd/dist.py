@@ -170,15 +170,34 @@ def sample_multibodies_sharded(diffusion, cond, N, L, n_bodies, *, seed, group=N
     return all_gather_designs(local, total, group) if gather else local
 
 
+def shard_known2d(sample_kw, batch_size, lo, hi):
+    """``sample_kw`` with the 2-D replacement conditioning cut to the designs lo .. hi-1: ``known`` [B, nb, C, H, W] and ``cond``
+    [B, 3 * cond_frames, H, W] along their first axis; ``known_mask`` too when it carries the design axis (five dimensions, the
+    first of size B) -- a mask that broadcasts over the designs serves every rank as it is."""
+    kw = dict(sample_kw)
+    for name in ("known", "cond"):
+        v = kw.get(name)
+        if v is not None:
+            if v.shape[0] != batch_size:
+                raise ValueError(f"{name} has {v.shape[0]} designs, the call samples {batch_size}")
+            kw[name] = v[lo:hi]
+    m = kw.get("known_mask")
+    if m is not None and m.dim() == 5 and m.shape[0] == batch_size:
+        kw["known_mask"] = m[lo:hi]
+    return kw
+
+
 def sample2d_sharded(diffusion, batch_size, *, seed, num_boundaries=1, group=None, gather=True, **sample_kw):
     """2-D ``GaussianDiffusion.sample(batch_size=..., num_boundaries=...)`` with the DESIGNS partitioned over the
     process group (the boundary copies of a design stay on one rank: they share noise and predicted states).
-    Returns [batch_size, num_boundaries, C, H, W] on every rank."""
+    Returns [batch_size, num_boundaries, C, H, W] on every rank.  The replacement conditioning ``known=`` / ``known_mask=`` /
+    ``cond=`` is sliced to the rank's designs (shard_known2d)."""
     _no_trajectory(sample_kw)
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)
     else:
         rank, world = 0, 1
     lo, hi = shard_bounds(batch_size, rank, world)
+    sample_kw = shard_known2d(sample_kw, batch_size, lo, hi)
     local = diffusion.sample(batch_size=hi - lo, num_boundaries=num_boundaries, seed=seed, sample_offset=lo, **sample_kw)
     return all_gather_designs(local, batch_size, group) if gather else local

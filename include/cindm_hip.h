@@ -451,6 +451,37 @@ int  cindm_ddpm1d_set_design_tables(cindm_ddpm1d* h, const float* target, int32_
                                     const float* scale, int32_t scale_per_design,
                                     int32_t rows, int32_t n_bodies, int64_t batch);
 
+/* Replacement conditioning of the 2-D chains: a known region of the state [B * nb, H * W, CP] is held on the forward-diffusion
+ * trajectory of its clean values and returned exactly (known2d_kernel: one more node of the captured step, after the step's
+ * update, guidance shift and counter).  No reference counterpart: its 2-D sample() takes no condition; the 1-D entries keep the
+ * reference's inpainting through their own arguments.  With q(k, t, z) = sqrt_alphas_cumprod[t] k + sqrt_one_minus_alphas_cumprod[t] z
+ * (two products and a sum, each rounded once):
+ *   before the first step, which is at timestep t0:   x[m] = q(k, t0, z_init)
+ *   after a step from t to t_next (DDPM: t - 1, DDIM: times[i + 1]):   x[m] = q(k, t_next, z) if t_next >= 0, else x[m] = k
+ * so the chain's result carries k exactly on the region (a DDPM chain with t_end > 0 ends at level t_end - 1 like the rest of its
+ * state).  z is drawn like the step noise -- state channels (all but the last 3) once per design, shared by its nb images, boundary
+ * channels per image -- at every step, whatever the DDIM sigma.
+ * known: DEVICE floats [images, hw, cp], the clean values (read only where the mask is set).
+ * mask:  DEVICE bytes [images, hw, cp / 4]: bit j of a byte = channel 4 g + j of that image and pixel is known; bits of padded
+ *        channels are ignored (padding stays zero).  The state channels of known and mask must be the same for the nb images of
+ *        a design (the caller's duty; otherwise the chains lose their invariant that those channels are shared).
+ * noise_init_state [B, hw, C-3], noise_init_boundary [images, hw, 3], noise_state_steps [rows][B, hw, C-3], noise_boundary_steps
+ *        [rows][images, hw, 3] with the two row strides in floats: explicit z for parity runs, all four or none; row = t (DDPM) or
+ *        the DDIM step index, as the chains' own step tapes.  None: the counter-based generator under a seed word of its own, keyed
+ *        (seed, sample_offset + design, t_next) with the chain call's seed and sample_offset; z_init is keyed by the timestep count.
+ * cindm_ddpm1d_set_known2d arms the NEXT chain call on this handle; that call consumes the region whether it succeeds or fails, and
+ * (NULL, NULL) disarms.  Served by cindm_ddpm2d_sample / _sample_ddim / _sample_force / _sample_ddim_force, which check images ==
+ * B * nb, hw == H * W, cp == CP, the strides and the 16-byte alignment of x before they launch or copy anything; every 1-D chain
+ * entry refuses an armed region.  All buffers are the caller's, 16-byte aligned, and must stay alive and unchanged until the chain's
+ * work has finished (use_graph: when the call returns; otherwise in stream order).  Their addresses are operands of the captured node.
+ * An exchange-free re-run starts from the first rule again; a recorder records after the overwrite.  With nothing armed a chain
+ * launches exactly what it launched before this entry existed; with a region, one launch more per step and one per chain. */
+int  cindm_ddpm1d_set_known2d(cindm_ddpm1d* h, const float* known, const uint8_t* mask,
+                              const float* noise_init_state, const float* noise_init_boundary,
+                              const float* noise_state_steps, const float* noise_boundary_steps,
+                              int64_t state_step_stride, int64_t boundary_step_stride,
+                              int64_t images, int32_t hw, int32_t cp);
+
 /* ===================================================================== 2-D airfoil path
  * Replaces Unet.forward (model/diffusion_2d.py:369-408) and GaussianDiffusion.p_sample /
  * p_sample_loop (model/diffusion_2d.py:788-907) of the reference for the sampling path
