@@ -9,7 +9,9 @@
 //   upload_ddim_tables  schedule check + the DDIM loops' per-step device tables
 //   RecScope            the chain recorder: taken by every chain entry
 //   DesignTablesScope   the waypoint objective's tables: taken by every 1-D chain entry, run by the two guided ones
-//   Known2DScope        the 2-D chains' known region: taken by every chain entry, run by the four 2-D ones (bottom of this file)
+//   Known2DScope        the 2-D chains' known region: taken by every chain entry, run by the four 2-D ones
+//   Known1DScope        the 1-D chains' known region: taken by every chain entry, run by cindm_ddpm1d_sample / _sample_guided /
+//                       _sample_ddim / _sample_ddim_guided (bottom of this file)
 // On top of these, the six 1-D entries (ddpm1d_host.inc) state their own facts once in Chain1D (the workspace layout), step1_refuse /
 // chain1_refuse / guided_refuse, chain_io, ddim_tables1, loop_chain and guided_chain, and the four 2-D entries (ddpm2d_host.inc)
 // theirs in Chain2D (the workspace layout), chain2_refuse / force_refuse, ForceGuide, ddim_args2, ddpm_step2 / ddim_step2 and run_chain2.
@@ -37,6 +39,14 @@ struct Known2D {
     const int* tnext = nullptr; uint64_t seed = 0; int64_t sample_off = 0;
 };
 
+// The known region of a 1-D chain as armed by the caller (cindm_ddpm1d_set_known1d, below) and checked against the chain's state by
+// the entry (known1_begin in ddpm1d_host.inc)
+struct Known1D {
+    const float* known = nullptr; const unsigned char* mask = nullptr; int known_per_design = 0, mask_per_design = 0;
+    const float* z_init = nullptr; const float* z_step = nullptr; const float* z_recur = nullptr;
+    int64_t step_stride = 0, recur_stride = 0, batch = 0; int rows = 0, feats = 0, apply_init = 1;
+};
+
 struct cindm_ddpm1d {
     int T = 0;
     float* tab = nullptr;        // 13 tables, each [T]
@@ -55,6 +65,8 @@ struct cindm_ddpm1d {
     DesignTables dzt_armed; const DesignTables* dzt = nullptr;
     // the known region of the 2-D chains: what the next chain call will take, and the one a running 2-D chain holds (null: none)
     Known2D kn_armed; const Known2D* kn = nullptr;
+    // the known region of the 1-D chains, likewise
+    Known1D kn1_armed; const Known1D* kn1 = nullptr;
     void drop_graph() {
         if (gexec) (void)hipGraphExecDestroy(gexec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -344,5 +356,46 @@ extern "C" int cindm_ddpm1d_set_known2d(cindm_ddpm1d* h, const float* known, con
     k.known = known; k.mask = mask; k.zi_state = noise_init_state; k.zi_bound = noise_init_boundary;
     k.z_state = noise_state_steps; k.z_bound = noise_boundary_steps; k.zs_stride = state_step_stride; k.zb_stride = boundary_step_stride;
     k.images = images; k.hw = hw; k.cp = cp;
+    return 0;
+}
+
+// ---- the known region of the 1-D chains (DESIGN 4.5o) ----------------------------------------------------------------------------------
+// cindm_ddpm1d_set_known1d arms the handle; the next chain entry takes the region with Known1DScope -- so the call consumes it however
+// it ends -- and either refuses it (known1_refuse: the rollout, the Langevin chain, every 2-D chain) or checks it against its state
+// (known1_begin, ddpm1d_host.inc) and runs with it: the chain body and run_step read h->kn1 for the whole call, the re-run included.
+struct Known1DScope {
+    cindm_ddpm1d* h; Known1D k;
+    explicit Known1DScope(cindm_ddpm1d* h_) : h(h_) {
+        if (!h) return;
+        k = h->kn1_armed; h->kn1_armed = Known1D();
+    }
+    ~Known1DScope() { if (h) h->kn1 = nullptr; }
+    bool on() const { return k.known != nullptr; }
+};
+
+static int known1_refuse(const Known1DScope& ks, const char* why) {
+    if (ks.on()) return fail(std::string("known region (1-D): ") + why + "; the region was dropped");
+    return 0;
+}
+
+extern "C" int cindm_ddpm1d_set_known1d(cindm_ddpm1d* h, const float* known, int32_t known_per_design, const uint8_t* mask,
+                                        int32_t mask_per_design, const float* noise_init, const float* noise_steps,
+                                        int64_t step_stride, const float* noise_recur, int64_t recur_stride, int32_t apply_init,
+                                        int64_t batch, int32_t rows, int32_t feats) {
+    if (h) h->kn1_armed = Known1D();      // (a refused call leaves the handle disarmed)
+    REQUIRE(h, "null handle");
+    if (!known && !mask) return 0;
+    REQUIRE(known && mask, "known region (1-D): values and mask come together (NULL, NULL disarms)");
+    REQUIRE(batch >= 1 && rows >= 1 && feats >= 4 && (feats & 3) == 0, "known region (1-D): batch and rows must be >= 1, the features a multiple of 4");
+    REQUIRE(!noise_recur || noise_steps, "known region (1-D): a relaxation tape comes with a step tape");
+    REQUIRE(!noise_steps || noise_init || !apply_init, "known region (1-D): a step tape comes with the init tape (all NULL: the counter-based generator)");
+    REQUIRE(!noise_init || noise_steps, "known region (1-D): the init tape comes with a step tape");
+    REQUIRE(step_stride >= 0 && recur_stride >= 0, "known region (1-D): negative tape stride");
+    for (const void* p : {(const void*)known, (const void*)mask, (const void*)noise_init, (const void*)noise_steps, (const void*)noise_recur})
+        REQUIRE(((uintptr_t)p & 15) == 0, "known region (1-D): values, mask and tapes must be 16-byte aligned");
+    Known1D& k = h->kn1_armed;
+    k.known = known; k.mask = mask; k.known_per_design = known_per_design ? 1 : 0; k.mask_per_design = mask_per_design ? 1 : 0;
+    k.z_init = noise_init; k.z_step = noise_steps; k.z_recur = noise_recur; k.step_stride = step_stride; k.recur_stride = recur_stride;
+    k.batch = batch; k.rows = rows; k.feats = feats; k.apply_init = apply_init ? 1 : 0;
     return 0;
 }

@@ -6,15 +6,16 @@
 //   step_layout                the step workspace, [pair in | pair eps | single in | single eps | U-Net workspaces | staging | x_T | DDIM tables]
 //   Chain1D                    what every helper below is handed unchanged, that layout (computed once, by its constructor) and its slices
 //   step1_refuse               what a step refuses of its Chain1D and state
-//   run_step                   one step: [gather,] U-Net(s), update, [counter,] [record node]
+//   run_step                   one step: [gather,] U-Net(s), update, [counter,] [known node,] [record node]
+//   known1_begin, known1_node  the known region of a chain (cindm_ddpm1d_set_known1d): its check against the state, and its launch
 //   chain1_refuse, guided_refuse   what a chain entry refuses, on top of that, before it touches the device
 //   start_loop, replay_steps, run_chain_with_recovery   step state, replay (graph cached by key, ping-pong pair + odd tail, flag polls), recovery
 //   chain_io, key_common       the StepIO every chain sets the same way, and what of it a captured step embeds
 //   ddim_tables1               the DDIM preamble: per-step tables into the workspace's slice
 //   loop_steps, loop_chain     the unguided loop and the chain that is one such loop
 //   guided_step, guided_chain  the recurrence iterations of a guided step and the guided chains' tail
-// An entry is: RecScope, DesignTablesScope, Known2DScope, Chain1D, refusals, rec_begin, chain_stream, (DDIM: ddim_tables1,) chain_io plus what it
-// adds, and one call of loop_chain, guided_chain or its own body (the rollout).
+// An entry is: RecScope, DesignTablesScope, Known2DScope, Known1DScope, Chain1D, refusals, rec_begin, known1_begin, chain_stream, (DDIM:
+// ddim_tables1,) chain_io plus what it adds, and one call of loop_chain, guided_chain or its own body (the rollout).
 
 extern "C" int cindm_ddpm1d_create(const cindm_sched_desc* d, cindm_ddpm1d** out) {
     REQUIRE(d && out && d->timesteps > 0, "bad schedule descriptor");
@@ -180,6 +181,7 @@ struct StepIO {
     int state_pp;           // guided DDIM loop: x_out is the OTHER of two state buffers -- the update writes it directly (no staging, no copy)
     const float* ula_tab; int ula_L, ula_t_hi;         // Langevin loop: per-timestep (scalar, ss, std, -) rows (device), inner count, first timestep
     int rec;                // recorded chain: the recorder's stream mask on the call that ends a step (chain_record_kernel follows it), else 0
+    int kn, relax_idx;      // chain with a known region: known1d_kernel follows every update; the relaxation's index (a constant of the captured iteration)
 };
 
 // What a step refuses of its Chain1D and state (x, and cond where the descriptor prepends it): run_step's own checks
@@ -201,6 +203,49 @@ static int step1_refuse(const Chain1D& ch, const float* x, const float* cond) {
 static int prepare_step_ws(const Chain1D& ch) {
     if (unet1d_prepare_ws(ch.pair, ch.ws_pair(), ch.s.pair_rows, ch.stream) != 0) return -1;
     if (ch.s.single_rows && unet1d_prepare_ws(ch.uncond, ch.ws_single(), ch.s.single_rows, ch.stream) != 0) return -1;
+    return 0;
+}
+
+// The known region of a 1-D chain (DESIGN 4.5o): checked against the chain's state before the entry's first launch or copy, then held
+// by the handle for the whole call.  recur_iters: the iterations per step of a guided chain (a relaxation tape holds that many records
+// per row), 0 for the unguided ones.
+static int known1_begin(Known1DScope& ks, const Chain1D& ch, const float* x, int recur_iters) {
+    if (!ks.on()) return 0;
+    const Known1D& k = ks.k;
+    const int F = ch.c->n_bodies * 4;
+    if (k.batch != ch.B || k.rows != ch.Ltot() || k.feats != F)
+        return fail("known region (1-D): made for " + std::to_string(k.batch) + " designs of " + std::to_string(k.rows) + " rows x " +
+                    std::to_string(k.feats) + " features, the chain's state is " + std::to_string(ch.B) + " x " + std::to_string(ch.Ltot()) +
+                    " x " + std::to_string(F));
+    REQUIRE((((uintptr_t)x | (uintptr_t)ch.stage()) & 15) == 0, "known region (1-D): the state x and the workspace's second state buffer must be "
+                                                                "16-byte aligned (the node moves 16 bytes per lane)");
+    if (k.z_step) {
+        REQUIRE(k.step_stride >= ch.n_state() && (k.step_stride & 3) == 0, "known region (1-D): the step tape's stride is smaller than one state or no multiple of 4");
+        if (recur_iters > 1) {
+            REQUIRE(k.z_recur, "known region (1-D): a guided chain with relaxation iterations and a tape needs the relaxation tape too");
+            REQUIRE(k.recur_stride >= (int64_t)recur_iters * ch.n_state() && (k.recur_stride & 3) == 0,
+                    "known region (1-D): the relaxation tape's stride is smaller than the step's iterations x one state, or no multiple of 4");
+        }
+    }
+    ks.h->kn1 = &ks.k;
+    return 0;
+}
+
+// the known node on the buffer `x` the last launch wrote, reading the step-state slot `st` it wrote: mode 0 a step's last update,
+// 1 rule 1 (the chain body's), 2 after relaxation `relax_idx`
+static int known1_node(const Chain1D& ch, const StepIO& io, float* x, const int* st, int mode, int relax_idx) {
+    const Known1D& k = *ch.h->kn1;
+    Known1dArgs a; std::memset(&a, 0, sizeof(a));
+    a.x = x; a.known = k.known; a.mask = k.mask; a.B = ch.B; a.Ltot = ch.Ltot(); a.F = ch.c->n_bodies * 4;
+    a.known_per_design = k.known_per_design; a.mask_per_design = k.mask_per_design;
+    a.sqrt_ac = ch.h->tab + 3 * (size_t)ch.h->T; a.sqrt_1mac = ch.h->tab + 4 * (size_t)ch.h->T;
+    a.st = st; a.tnext = io.ddim_tab ? io.ddim_tnext : nullptr;
+    a.mode = mode; a.init_tag = (uint32_t)ch.h->T; a.relax_idx = relax_idx;
+    a.z_init = k.z_init; a.z_step = k.z_step; a.z_step_stride = k.step_stride;
+    a.z_recur = (k.z_step && k.z_recur) ? k.z_recur + (size_t)relax_idx * ch.n_state() : nullptr; a.z_recur_stride = k.recur_stride;
+    a.dyn = io.dyn;
+    hipLaunchKernelGGL(known1d_kernel, dim3((unsigned)((ch.n_state() / 4 + 255) / 256)), dim3(256), 0, ch.stream, a);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -317,6 +362,12 @@ static int run_step(const Chain1D& ch, const StepIO& io, int32_t t, const int32_
     }
     HIPCHK(hipGetLastError());
     if (guided && !io.state_pp) HIPCHK(hipMemcpyAsync(io.x_out, a.x_out, (size_t)ne * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    if (io.kn && h->kn1) {
+        // after the update in whichever form, the counter and the staging copy: the node writes the buffer the update wrote and reads
+        // the slot it advanced (a relaxation iteration of the guided DDPM step launches no counter: the word is still t)
+        if (known1_node(ch, io, io.x_out, io.pingpong ? h->t_dev + 4 * (1 - q) : h->t_dev, (guided && io.relax) ? 2 : 0, io.relax_idx) != 0) return -1;
+        h->last_step_launches += 1;
+    }
     if (io.rec && h->rec) {
         // after the step's last writer of the state and of the step state: a ping-pong step has just advanced the OTHER slot
         if (rec_node(h, io.x_out, io.pingpong ? 1 - q : 0, stream) != 0) return -1;
@@ -523,6 +574,10 @@ static void key_common(KeyBuilder& K, int kind, const Chain1D& ch, const StepIO&
     K(io.x)(io.cond)(io.x_out)(io.noise)(io.noise_t_stride)(io.add_noise)(io.inp_cond)(io.inp_steps)(io.inp_noise)(io.inp_noise_t_stride);
     K(io.ddim_tab)(io.ddim_tnext)(io.iso)(io.iso_steps)(io.recur_t_stride);
     K(io.rec)(io.x0_out);      // recorder on, which streams; the x0 stream's staging record is an operand of the captured update
+    if (io.kn && ch.h->kn1) {  // known region: everything the captured node embeds (nothing armed: the key is what it was)
+        const Known1D& k = *ch.h->kn1;
+        K(io.kn)(k.known)(k.mask)(k.known_per_design)(k.mask_per_design)(k.z_step)(k.step_stride)(k.z_recur)(k.recur_stride);
+    }
 }
 
 // the StepIO fields every sample loop sets the same way: in-place state, per-step tapes (or the counter noise keyed in device
@@ -536,6 +591,7 @@ static StepIO chain_io(const Chain1D& ch, float* x, const float* cond, const flo
     io.inp_noise_t_stride = ch.B * inpaint_steps * ch.c->n_bodies * 4;
     io.dyn = reinterpret_cast<const unsigned long long*>(ch.h->t_dev + 16);
     if (ch.h->rec) { io.rec = ch.h->rec->streams; io.x0_out = ch.h->rec->x0_stage; }      // (x0_out set: the update is not fused)
+    io.kn = ch.h->kn1 ? 1 : 0;
     return io;
 }
 
@@ -558,6 +614,8 @@ static int loop_steps(const Chain1D& ch, StepIO io, int kind, int t0, int nsteps
     io.dec_t = 1; io.pingpong = pp ? 1 : 0;
     start_loop(ch, t0, seed, sample_offset);
     rec_arm(ch.h, io.ddim_tab ? -1 : t0, io.ddim_tab ? 2 : 0, pp ? 4 : 0, ch.stream);
+    // (rule 1 of a known region, at the level set_counter_kernel has just written to slot 0; a recovery re-run starts from it again)
+    if (io.kn && ch.h->kn1 && ch.h->kn1->apply_init && known1_node(ch, io, io.x_out, ch.h->t_dev, 1, 0) != 0) return -1;
     KeyBuilder K;
     key_common(K, kind, ch, io);
     K(pp)(io.ula_tab)(io.ula_L)(io.ula_t_hi);
@@ -585,6 +643,7 @@ static int guided_step(const Chain1D& ch, const StepIO& io, int iters, const flo
         if (it.relax) it.rec = 0;
         it.recur_noise = recur_noise_steps ? recur_noise_steps + (size_t)r * ch.n_state() : nullptr;
         it.recur_tag = 0x10000u * (uint32_t)(r + 1);
+        it.relax_idx = r;
         if (buf) { const int p = (q * iters + r) & 1; it.parity = p; it.x = buf[p]; it.x_out = buf[1 - p]; }
         else it.dec_t = it.relax ? 0 : 1;
         if (run_step(ch, it, 0, ch.h->t_dev) != 0) return -1;
@@ -607,6 +666,7 @@ static int guided_chain(RecScope& rs, const Chain1D& ch, StepIO io, int kind, co
         if (prepare_step_ws(ch) != 0) return -1;
         start_loop(ch, t0, io.seed, io.sample_off);
         rec_arm(ch.h, pp ? -1 : t0, pp ? 2 : 0, pp ? 4 : 0, ch.stream);
+        if (io.kn && ch.h->kn1 && ch.h->kn1->apply_init && known1_node(ch, io, io.x_out, ch.h->t_dev, 1, 0) != 0) return -1;      // (rule 1)
         KeyBuilder K;
         key_common(K, kind, ch, io);
         K(*io.dz)(recur_noise_steps)(R);
@@ -629,10 +689,11 @@ extern "C" int cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_un
     RecScope rs(h);
     DesignTablesScope ts(h);
     Known2DScope ks(h);
+    Known1DScope k1(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
     if (dzt_refuse(ts) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0) return -1;
-    if (rec_begin(rs, x, nsteps, ch.n_state()) != 0) return -1;
+    if (rec_begin(rs, x, nsteps, ch.n_state()) != 0 || known1_begin(k1, ch, x, 0) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     const StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     return loop_chain(rs, ch, io, 0, (int)t_start, nsteps);
@@ -646,11 +707,12 @@ extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cin
     RecScope rs(h);
     DesignTablesScope ts(h);
     Known2DScope ks(h);
+    Known1DScope k1(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
     if (dzt_refuse(ts) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, &dd) != 0) return -1;
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    if (rec_begin(rs, x, n_steps, ch.n_state()) != 0) return -1;
+    if (rec_begin(rs, x, n_steps, ch.n_state()) != 0 || known1_begin(k1, ch, x, 0) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     if (ddim_tables1(ch, dd, io) != 0) return -1;
@@ -671,9 +733,12 @@ extern "C" int cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pa
     RecScope rs(h);
     DesignTablesScope ts(h);
     Known2DScope ks(h);
+    Known1DScope k1(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
     if (dzt_refuse(ts) != 0 || known2_refuse(ks) != 0) return -1;
+    if (known1_refuse(k1, "the autoregressive rollout draws a fresh state per segment and hands rows over between segments: a region of "
+                          "one [B, rows, F] state does not name a place in it") != 0) return -1;
     REQUIRE(!rs.on(), "recorder: the autoregressive rollout is not recorded (its step index is (segment, step)); the recorder was dropped");
     REQUIRE(h && pair && c && x && cond && cond_buf && out && times && coefs && seeds, "null argument");
     REQUIRE(c->mode == CINDM_COMPOSE_PLAIN || c->mode == CINDM_COMPOSE_MULTIBODY, "the rollout runs the plain (or multibody) prediction");
@@ -725,8 +790,11 @@ extern "C" int cindm_ddpm1d_sample_ula(cindm_ddpm1d* h, cindm_unet1d* pair, cind
     RecScope rs(h);
     DesignTablesScope ts(h);
     Known2DScope ks(h);
+    Known1DScope k1(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     if (dzt_refuse(ts) != 0 || known2_refuse(ks) != 0) return -1;
+    if (known1_refuse(k1, "the Langevin chain moves the whole state, conditioning rows included, at one noise level per timestep without a "
+                          "reverse update: the region's forward-diffusion trajectory is not defined for it") != 0) return -1;
     REQUIRE(!rs.on(), "recorder: the Langevin chain is not recorded (its step index is (timestep, inner iteration)); the recorder was dropped");
     REQUIRE(h && pair && c && x && scalar && step_size && noise_std && tab, "null argument");
     REQUIRE(c->mode == CINDM_COMPOSE_MULTIBODY && uncond, "the Langevin phase runs the multibody composition (pair + unconditioned model)");
@@ -763,10 +831,11 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
     RecScope rs(h);
     DesignTablesScope ts(h);
     Known2DScope ks(h);
+    Known1DScope k1(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
     if (known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0 || guided_refuse(ch, ts, dz, 0, initial_state_overwrite, overwrite_steps) != 0) return -1;
-    if (rec_begin(rs, x, nsteps, ch.n_state()) != 0) return -1;
+    if (rec_begin(rs, x, nsteps, ch.n_state()) != 0 || known1_begin(k1, ch, x, std::max(dz->recurrence, 1)) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     guided_io(io, dz, initial_state_overwrite, overwrite_steps);
@@ -791,12 +860,13 @@ extern "C" int cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pa
     RecScope rs(h);
     DesignTablesScope ts(h);
     Known2DScope ks(h);
+    Known1DScope k1(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
     if (known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, &dd) != 0 || guided_refuse(ch, ts, dz, 1, initial_state_overwrite, overwrite_steps) != 0) return -1;
     REQUIRE(!inpaint_cond || (inpaint_steps >= 1 && inpaint_steps <= ch.Ltot()), "bad inpaint_steps");
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    if (rec_begin(rs, x, n_steps, ch.n_state()) != 0) return -1;
+    if (rec_begin(rs, x, n_steps, ch.n_state()) != 0 || known1_begin(k1, ch, x, dz->recurrence) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     if (ddim_tables1(ch, dd, io) != 0) return -1;

@@ -311,6 +311,9 @@ extern "C" int cindm_ddpm2d_sample(cindm_ddpm1d* s, cindm_unet2d* u, float* x, i
                                    void* stream_, int32_t use_graph) {
     RecScope rs(s);
     Known2DScope ks(s);
+    Known1DScope k1(s);
+    if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
+                          "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
     if (chain2_refuse(ch, x, nullptr, t_start, t_end) != 0) return -1;
@@ -327,6 +330,9 @@ extern "C" int cindm_ddpm2d_sample_ddim(cindm_ddpm1d* s, cindm_unet2d* u, float*
                                         int64_t sample_offset, void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(s);
     Known2DScope ks(s);
+    Known1DScope k1(s);
+    if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
+                          "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const Ddim2dCall dd{n_steps, times, coefs, nullptr, tab, tab_bytes};
     if (chain2_refuse(ch, x, &dd) != 0) return -1;
@@ -351,6 +357,9 @@ extern "C" int cindm_ddpm2d_sample_force(cindm_ddpm1d* s, cindm_unet2d* u, cindm
                                          size_t ws_force_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(s);
     Known2DScope ks(s);
+    Known1DScope k1(s);
+    if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
+                          "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const ForceGuide g{f, frames, p_min, p_max, lambda_force, lambda_overlap, down_factor, sum_boundary, grad, ws_force, ws_force_bytes};
     const int nsteps = t_start - t_end + 1;
@@ -372,6 +381,9 @@ extern "C" int cindm_ddpm2d_sample_ddim_force(cindm_ddpm1d* s, cindm_unet2d* u, 
                                               size_t ws_force_bytes, void* stream_, int32_t use_graph) {
     RecScope rs(s);
     Known2DScope ks(s);
+    Known1DScope k1(s);
+    if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
+                          "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const Ddim2dCall dd{n_steps, times, coefs, weights, tab, tab_bytes};
     const ForceGuide g{f, frames, p_min, p_max, lambda_force, lambda_overlap, down_factor, sum_boundary, grad, ws_force, ws_force_bytes};

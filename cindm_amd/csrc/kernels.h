@@ -3754,6 +3754,83 @@ __global__ void compose_update_kernel(const ComposeArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Replacement conditioning of the 1-D chains (cindm_ddpm1d_set_known1d): one more node of the captured step, after the
+// step's update in whichever of its three forms (fused into ups_last_kernel, compose_update_kernel, guided), after the guided DDPM
+// step's staging copy and after the counter launch where the loop has one.  The known region (mask) of the state x [B, Ltot, F] is
+// put on the forward-diffusion trajectory of its clean values k at the level the rest of the state has just reached:
+//   x[m] = q(k, level, z) = sqrt_ac[level] k + sqrt_1mac[level] z   for level >= 0,    x[m] = k   for level < 0
+// (the two products and the sum round once each, as the torch expression does).  The level is read from the step state, never from
+// the host -- one captured node serves every step.  st is the slot the step has just written (without ping-pong: the only one):
+//   mode 0, a step's last update   DDPM: level = st[0], which the update / counter has already decremented; tape row t = level + 1
+//                                  DDIM: row = st[2] - 1, the step index just left; level = tnext[row] (st[0] is clamped at 0,
+//                                  so the last pair, whose time_next is -1, must read the table)
+//   mode 1, rule 1 (chain body)    level = st[0], the chain's first timestep; tape z_init; generator word init_tag = T
+//   mode 2, after a relaxation     level = st[0]: compose_advance / the missing counter launch keep the step on its timestep;
+//                                  tape row t (DDPM) or st[2] (DDIM), the host has offset z_recur to the relaxation's index;
+//                                  generator word t + 0x10000 (relax_idx + 1), the recurrence draws' scheme
+// z from the caller's tapes when given, else counter-based under seed ^ kKnown1dSeed keyed (sample_off + b, word, element), with
+// (seed, sample_off) from the step state's dyn words like the update: independent of how the batch is sharded.
+// One thread per body (four consecutive features, F % 4 == 0); the mask is one byte per element in the state's layout, so a thread
+// reads one 32-bit mask word: 0 returns before any other access, a body known whole is stored without being read, a partly known
+// one is blended.  16-byte loads and stores (the host checks the alignment of every buffer).  known and mask are per design or
+// shared by all designs (two flags, as the waypoint tables).
+static constexpr uint64_t kKnown1dSeed = 0x6b6e6f776e316421ull;
+struct Known1dArgs {
+    float* x; const float* known; const unsigned char* mask;
+    int64_t B; int Ltot, F;
+    int known_per_design, mask_per_design;
+    const float* sqrt_ac; const float* sqrt_1mac;
+    const int* st; const int* tnext;                        // tnext null: a DDPM chain
+    int mode; uint32_t init_tag; int relax_idx;
+    const float* z_init;                                    // [B, Ltot, F] or null
+    const float* z_step; int64_t z_step_stride;             // [rows][B, Ltot, F] or null
+    const float* z_recur; int64_t z_recur_stride;           // [rows][iters][B, Ltot, F] + relax_idx records, or null
+    const unsigned long long* dyn;                          // (seed, sample_off) of the running chain
+};
+__global__ __launch_bounds__(256) void known1d_kernel(const Known1dArgs a) {
+    const int w0 = uniform_word(a.st);
+    int level = w0, row;
+    if (a.mode == 0) {
+        if (a.tnext) { row = uniform_word(a.st + 2) - 1; level = uniform_word(a.tnext + row); }
+        else row = w0 + 1;
+    } else {
+        row = a.tnext ? uniform_word(a.st + 2) : w0;
+    }
+    const int F4 = a.F >> 2;                       // bodies
+    const int64_t per4 = (int64_t)a.Ltot * F4;
+    const int64_t i4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i4 >= a.B * per4) return;
+    const int64_t b = i4 / per4, e4 = i4 - b * per4;
+    const uint32_t mw = *reinterpret_cast<const uint32_t*>(a.mask + 4 * (a.mask_per_design ? i4 : e4));
+    if (!mw) return;
+    const bool m[4] = {(mw & 0xffu) != 0, (mw & 0xff00u) != 0, (mw & 0xff0000u) != 0, (mw & 0xff000000u) != 0};
+    const bool whole = m[0] && m[1] && m[2] && m[3];
+    const float4 k4 = *reinterpret_cast<const float4*>(a.known + 4 * (a.known_per_design ? i4 : e4));
+    const float4 x4 = whole ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(a.x + 4 * i4);
+    const float kv[4] = {k4.x, k4.y, k4.z, k4.w}, xv[4] = {x4.x, x4.y, x4.z, x4.w};
+    float r[4];
+    if (level >= 0) {
+        const float sa = uniform_float(a.sqrt_ac + level), sm = uniform_float(a.sqrt_1mac + level);
+        const float* zt = a.mode == 1 ? a.z_init : a.mode == 2 ? (a.z_recur ? a.z_recur + (size_t)row * a.z_recur_stride : nullptr)
+                                                                : (a.z_step ? a.z_step + (size_t)row * a.z_step_stride : nullptr);
+        float z[4];
+        if (zt) {
+            const float4 zv = *reinterpret_cast<const float4*>(zt + 4 * i4);
+            z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
+        } else {
+            const uint32_t word = a.mode == 1 ? a.init_tag : a.mode == 2 ? (uint32_t)level + 0x10000u * (uint32_t)(a.relax_idx + 1) : (uint32_t)level;
+            counter_normal4((uint64_t)a.dyn[0] ^ kKnown1dSeed, (uint64_t)((int64_t)a.dyn[1] + b), word, (uint32_t)e4, z);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = m[j] ? __fadd_rn(__fmul_rn(sa, kv[j]), __fmul_rn(sm, z[j])) : xv[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r[j] = m[j] ? kv[j] : xv[j];
+    }
+    *reinterpret_cast<float4*>(a.x + 4 * i4) = make_float4(r[0], r[1], r[2], r[3]);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Langevin (ULA) update of sample_compose_multibodies' first phase (sample_step_ULA, model/diffusion_1d.py:2048-2073, on the
 // composed score of gradient(), :1865-1926).  The state x [B, Ltot, F] is the WHOLE sequence -- the conditioning rows are part
 // of it and move too (c.cond_steps == 0; compose_gather_kernel gathers the pair / single-body rows from it).  Per element

@@ -44,14 +44,24 @@ class NoiseTape:
     ``autoregress_time_compose_sample`` reads a leading SEGMENT index: ``init`` [K,B,R,F] (each segment's x_T, :2299 /
     :2264) and ``step`` [K,S,B,R,F] (segment k's draw of DDIM step i, :2315 / :2280).
     ``ula`` [n_t,L,B,Lc+R,F]: the Langevin draws of ``sample_compose_multibodies`` with N > 401 (:2056), on the WHOLE state, in
-    the order they are drawn: row 0 of the first axis is timestep N - 1."""
+    the order they are drawn: row 0 of the first axis is timestep N - 1.
+    Keyword-only, the draws of a known region's forward diffusion (``known=`` of the sampling calls): ``known_init``
+    [B,L,F] (rule 1), ``known_step`` [rows,B,L,F] indexed like ``step`` (by t, or by the DDIM step index), ``known_recur``
+    [rows,iters,B,L,F] shaped like ``recur`` (record r is used after relaxation r; the last one is unused)."""
 
-    def __init__(self, init, step, recur=None, cond=None, ula=None):
+    def __init__(self, init, step, recur=None, cond=None, ula=None, *, known_init=None, known_step=None, known_recur=None):
         self.init, self.step, self.recur, self.cond, self.ula = init, step, recur, cond, ula
+        self.known_init, self.known_step, self.known_recur = known_init, known_step, known_recur
 
     def to(self, device):
         f = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()
-        return NoiseTape(f(self.init), f(self.step), f(self.recur), f(self.cond), f(self.ula))
+        return NoiseTape(f(self.init), f(self.step), f(self.recur), f(self.cond), f(self.ula), known_init=f(self.known_init),
+                         known_step=f(self.known_step), known_recur=f(self.known_recur))
+
+
+# the seed word of a known region's counter-based draws (known1d_kernel's kKnown1dSeed): distinct from the step, relaxation and
+# inpainting draws' words
+KNOWN_SEED = 0x6b6e6f776e316421
 
 
 def _exists(x):
@@ -275,6 +285,110 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
     def _f32(t, device=None):
         return None if t is None else t.detach().to(device=device or t.device, dtype=torch.float32).contiguous()
 
+    # ------------------------------------------------------------------ replacement conditioning (known region)
+    def _known_region(self, full, known, known_mask, cond, initial_state_overwrite, noise=None, rows=0, recur_iters=0, init=True):
+        """The known region of a sampling call over the state ``full`` = (B, L, F) as (values fp32, mask bool), each [B, L, F] or --
+        shared by all designs -- [L, F]; None without one.  Host checks only (ValueError), made before any device work: shapes,
+        finite values on the region, rule 5 (no row also claimed by ``cond`` inpainting or ``initial_state_overwrite``) and the
+        tape's known rows (``rows`` of them at least, ``recur_iters`` relaxation records per row for a guided chain)."""
+        if known is None:
+            if known_mask is not None:
+                raise ValueError("known_mask without known")
+            return None
+        B, L, F = full
+        if known_mask is None:
+            raise ValueError(f"known needs known_mask (bool, broadcastable to [{B}, {L}, {F}])")
+        if tuple(known.shape) not in ((B, L, F), (L, F)):
+            raise ValueError(f"known must be [{B}, {L}, {F}] (per design) or [{L}, {F}] (shared by all designs), got {tuple(known.shape)}")
+        if known_mask.dtype != torch.bool:
+            raise ValueError("known_mask must be a bool tensor")
+        if known_mask.dim() > 3:
+            raise ValueError(f"known_mask {tuple(known_mask.shape)} does not broadcast to {(B, L, F)}")
+        per_design = known_mask.dim() == 3 and known_mask.shape[0] != 1
+        try:
+            m = torch.broadcast_to(known_mask[0] if (known_mask.dim() == 3 and not per_design) else known_mask,
+                                   (B, L, F) if per_design else (L, F)).contiguous()
+        except RuntimeError as e:
+            raise ValueError(f"known_mask {tuple(known_mask.shape)} does not broadcast to {(B, L, F)}") from e
+        k = known.detach().to(torch.float32).contiguous()
+        kb, mb = torch.broadcast_tensors(k, m.to(k.device))
+        if not bool(torch.isfinite(kb[mb]).all()):
+            raise ValueError("known holds non-finite values on the region")
+        claimed = []
+        if self.conditioned_steps == 0 and cond is not None:
+            claimed.append(("cond (inpainting, conditioned_steps == 0)", cond.shape[1]))
+        if initial_state_overwrite is not None:
+            claimed.append(("initial_state_overwrite", initial_state_overwrite.shape[1]))
+        for name, n in claimed:
+            if bool(m[..., :n, :].any()):
+                raise ValueError(f"the known region touches rows 0 .. {n - 1}, which {name} claims: name each row through one mechanism")
+        if noise is not None:
+            ok = noise.known_step is not None and noise.known_step.dim() == 4 and noise.known_step.shape[0] >= rows and \
+                tuple(noise.known_step.shape[1:]) == (B, L, F)
+            ok = ok and (not init or (noise.known_init is not None and tuple(noise.known_init.shape) == (B, L, F)))
+            if recur_iters > 1:
+                kr = noise.known_recur
+                ok = ok and kr is not None and kr.dim() == 5 and kr.shape[0] >= rows and kr.shape[1] >= recur_iters and \
+                    tuple(kr.shape[2:]) == (B, L, F)
+            if not ok:
+                raise ValueError(f"a noise tape used with a known region needs known_init [{B}, {L}, {F}], known_step [>= {rows}, {B}, {L}, {F}]"
+                                 + (f" and known_recur [>= {rows}, >= {recur_iters}, {B}, {L}, {F}]" if recur_iters > 1 else ""))
+        return k, m
+
+    def known_replace(self, x, known, mask, level, z=None):
+        """The definition of the known region in torch (what the library's known1d_kernel does inside the captured step,
+        and what the routes that loop in Python call): ``x[m] = q(k, level, z)`` for ``level >= 0``, ``x[m] = k`` for ``level < 0``,
+        with ``q = sqrt_alphas_cumprod[level] * k + sqrt_one_minus_alphas_cumprod[level] * z`` -- two products and a sum, three
+        tensor operations.  x [B, L, F]; known and mask [B, L, F] or broadcastable to it; z [B, L, F] (None: ``torch.randn_like``).
+        An empty mask returns x itself; otherwise a new tensor."""
+        level = int(level)
+        m = torch.broadcast_to(mask.to(x.device), x.shape)
+        if not bool(m.any()):
+            return x
+        k = torch.broadcast_to(known.to(x.device, x.dtype), x.shape)
+        if level < 0:
+            q = k
+        else:
+            z = torch.randn_like(x) if z is None else z.to(x.device, x.dtype)
+            a = self.sqrt_alphas_cumprod[level].to(x.device) * k
+            b = self.sqrt_one_minus_alphas_cumprod[level].to(x.device) * z
+            q = a + b
+        return torch.where(m, q, x)
+
+    def _known_z(self, full, row, word, seed, sample_offset, device):
+        """The z of one overwrite on the routes that loop in Python: the tape's row when there is one, else the library's
+        counter-based draw under the known region's seed word, keyed (sample_offset + b, ``word``, element) as known1d_kernel keys it."""
+        if row is not None:
+            return row
+        z = torch.empty(full, dtype=torch.float32, device=device)
+        with torch.cuda.device(device):
+            _ffi.check(_ffi.lib().cindm_fill_normal(_ffi.ptr(z), full[0], full[1] * full[2], C.c_uint64((int(seed) ^ KNOWN_SEED) & (2 ** 64 - 1)),
+                                                    sample_offset, int(word), _ffi.current_stream(device)))
+        return z
+
+    def _known_armer(self, kn, full, noise, device, init=True):
+        """``arm(h)`` for a library chain with the region ``kn`` (None without one): every issue of the chain call arms the handle
+        again (``cindm_ddpm1d_set_known1d``; the call consumes the region).  The device tensors live as long as the closure."""
+        if kn is None:
+            return None
+        kd = kn[0].to(device)
+        md = kn[1].to(device=device, dtype=torch.uint8).contiguous()
+        zi = zs = zr = None
+        if noise is not None:
+            zi, zs, zr = noise.known_init, noise.known_step, noise.known_recur
+        B, L, F = full
+
+        def arm(h):
+            _ffi.check(_ffi.lib().cindm_ddpm1d_set_known1d(
+                h, _ffi.ptr(kd), int(kd.dim() == 3), _ffi.ptr(md), int(md.dim() == 3), _ffi.ptr(zi), _ffi.ptr(zs),
+                0 if zs is None else zs[0].numel(), _ffi.ptr(zr), 0 if zr is None else zr[0].numel(), int(init), B, L, F))
+        return arm
+
+    @staticmethod
+    def _arm_known(arm, h):
+        if arm is not None:
+            arm(h)
+
     # ------------------------------------------------------------------ reference-named helpers
     def predict_start_from_noise(self, x_t, t, noise):
         return self.sqrt_recip_alphas_cumprod[t].view(-1, 1, 1) * x_t - self.sqrt_recipm1_alphas_cumprod[t].view(-1, 1, 1) * noise
@@ -421,10 +535,11 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
 
     @torch.no_grad()
     def _guided_step(self, x, cond, t, desc, design_fn, design_guidance, initial_state_overwrite, noise, recur_noise,
-                     ddim_return=False, check=True):
+                     ddim_return=False, check=True, after_relax=None):
         """Shared body of p_sample / p_sample_compose_inside / p_sample_compose_outside.  ``ddim_return``: the
         sampling_timesteps != timesteps convention of the recurrence branch (:1372-1376): returns
-        (pred_noise + grad_design_final, x_start) of the last iteration."""
+        (pred_noise + grad_design_final, x_start) of the last iteration.  ``after_relax(r, x)``: what a known region does to the
+        state after relaxation r (all but the last iteration, whose relaxed state is never used)."""
         R = int(design_guidance.split("-")[-1]) if "recurrence" in design_guidance else 0
         x = self._f32(x)
         logvar = self.posterior_log_variance_clipped[t]
@@ -443,6 +558,8 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
                 ratio = self.alphas_cumprod / self.alphas_cumprod_prev
                 z = recur_noise[r] if recur_noise is not None else torch.randn_like(pred)
                 x = torch.sqrt(ratio)[t] * pred + torch.sqrt(1 - ratio)[t] * z
+                if after_relax is not None and r < max(R, 1) - 1:
+                    x = after_relax(r, x)
         if ddim_return:
             return eps + shift, x_start
         if t > 0:
@@ -484,14 +601,15 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
     # ------------------------------------------------------------------ loops
     @torch.no_grad()
     def _run_loop(self, img, cond, desc, t_start, t_end, *, noise_steps, seed, sample_offset, inpaint_cond,
-                  inpaint_noise_steps, use_graph=True, rec=None):
-        """The unguided reverse loop as one library call (cindm_ddpm1d_sample)."""
+                  inpaint_noise_steps, use_graph=True, rec=None, karm=None):
+        """The unguided reverse loop as one library call (cindm_ddpm1d_sample).  ``karm``: the known region's ``arm(h)`` or None."""
         B = img.shape[0]
         cond_d = self._f32(cond, img.device) if (cond is not None and self.conditioned_steps != 0) else None
         inp = self._f32(inpaint_cond, img.device)
 
         def call(h, un, ws):
             self._arm(rec, h)
+            self._arm_known(karm, h)
             with torch.cuda.device(img.device):
                 _ffi.check(_ffi.lib().cindm_ddpm1d_sample(
                     h, self.model._h, un, C.byref(desc), _ffi.ptr(img), _ffi.ptr(cond_d), _ffi.ptr(noise_steps),
@@ -502,7 +620,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
 
     @torch.no_grad()
     def _run_guided_loop(self, img, cond, desc, dz, t_start, t_end, *, noise, seed, sample_offset, inpaint_cond,
-                         initial_state_overwrite, use_graph=True, rec=None, tables=None):
+                         initial_state_overwrite, use_graph=True, rec=None, tables=None, karm=None):
         """Reverse steps t_start .. t_end guided by the built-in objective as one library call
         (cindm_ddpm1d_sample_guided); ``noise`` rows (step / recur / cond) are indexed by t.  ``tables``: the WaypointObjective
         whose descriptor ``dz`` is (modes 3 / 4): every issue of the call arms its tables."""
@@ -514,6 +632,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         def call(h, un, ws):
             self._arm(rec, h)
             self._arm_tables(tables, h, img)
+            self._arm_known(karm, h)
             with torch.cuda.device(device):
                 _ffi.check(_ffi.lib().cindm_ddpm1d_sample_guided(
                     h, self.model._h, un, C.byref(desc), C.byref(dz), _ffi.ptr(img), _ffi.ptr(cond_d),
@@ -525,7 +644,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
 
     @torch.no_grad()
     def _run_guided_ddim(self, img, cond, desc, dz, times, coefs, *, noise, seed, sample_offset, inpaint_cond,
-                         initial_state_overwrite, use_graph=True, rec=None, tables=None):
+                         initial_state_overwrite, use_graph=True, rec=None, tables=None, karm=None):
         """DDIM steps ``times[0] .. times[-2]`` guided by the built-in objective as one library call
         (cindm_ddpm1d_sample_ddim_guided); ``noise`` rows (step / recur / cond) are indexed by the position in ``times``.
         ``tables``: as _run_guided_loop."""
@@ -540,6 +659,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         def call(h, un, ws):
             self._arm(rec, h)
             self._arm_tables(tables, h, img)
+            self._arm_known(karm, h)
             with torch.cuda.device(device):
                 _ffi.check(_ffi.lib().cindm_ddpm1d_sample_ddim_guided(
                     h, self.model._h, un, C.byref(desc), C.byref(dz), _ffi.ptr(img), _ffi.ptr(cond_d), S, tarr, _ffi.ptr(carr),
@@ -566,11 +686,23 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
     def p_sample_loop(self, shape, cond, n_composed=0, compose_start_step=4, compose_n_bodies=2, compose_mode="mean",
                       design_fn=None, design_guidance="standard", initial_state_overwrite=None, initialization_mode=0,
                       initialization_img=None, *, noise=None, seed=None, sample_offset=0, use_graph=True, t_stop=0,
-                      return_trajectory_every=None, trajectory=("x",)):
+                      return_trajectory_every=None, trajectory=("x",), known=None, known_mask=None):
         """:1656-1720.  Build-only keywords: ``noise`` (NoiseTape, explicit draws), ``seed`` /
         ``sample_offset`` (counter-based generator keyed by global sample index), ``t_stop`` (truncate),
         ``return_trajectory_every=k`` with ``trajectory=("x",)`` / ``("x", "x0")``: returns (designs, ChainRecord) with the state after
-        every k-th step and after the last one (record.py; recorded inside the captured step on the library routes)."""
+        every k-th step and after the last one (record.py; recorded inside the captured step on the library routes).
+        Replacement conditioning (build-only): ``known`` [B, L_tot, F] or [L_tot, F] (shared by all designs) with
+        ``known_mask`` (bool, broadcastable to the state) names a region of the returned state and its clean values k.  With
+        q(k, l, z) = sqrt_alphas_cumprod[l] k + sqrt_one_minus_alphas_cumprod[l] z the region is set to q(k, T - 1, z_init) before the
+        first step, to q(k, t, z) after every relaxation iteration of a guided step at t, and to q(k, t - 1, z) after the step (k
+        itself after t = 0), so it comes back exactly; z per element from the tape's ``known_init`` / ``known_step[t]`` /
+        ``known_recur[t][r]``, else counter-based under a seed word of its own.  The region overwrites last and may not touch rows
+        that ``cond`` inpainting or ``initial_state_overwrite`` claim (ValueError).  Inside the captured step on the library routes
+        (known1d_kernel), ``known_replace`` on the route that loops in Python; a recorder's x stream is taken after the overwrite."""
+        full = (shape[0], shape[1] + n_composed * compose_start_step, compose_n_bodies * 4)
+        fast = design_fn is None and "recurrence" not in design_guidance and initial_state_overwrite is None
+        iters = max(int(design_guidance.split("-")[-1]) if "recurrence" in design_guidance else 0, 1)
+        kn = self._known_region(full, known, known_mask, cond, initial_state_overwrite, noise, self.num_timesteps, 0 if fast else iters)
         device = self.betas.device
         if device.type != "cuda":
             raise _ffi.CindmError("GaussianDiffusion1D is on the CPU: move it to a ROCm device; there is no CPU execution path")
@@ -580,9 +712,9 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         if noise is not None:
             noise = noise.to(device)
         B, T1 = shape[0], shape[1]
-        full = (B, T1 + n_composed * compose_start_step, compose_n_bodies * 4)
         assert compose_start_step < T1
         dz, tables = self._builtin(design_fn, design_guidance, B, full[1], compose_n_bodies)
+        karm = self._known_armer(kn, full, noise, device)
         init = self._init_state(full, device, noise, seed, sample_offset, self.num_timesteps)
         if initialization_mode == 0:
             img = init
@@ -593,7 +725,6 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         inside = "inside" in compose_mode
         desc = self._desc_for(full, compose_mode, n_composed, compose_start_step, T1, compose_n_bodies, outside=not inside)
         inpaint = cond if (self.conditioned_steps == 0 and cond is not None) else None
-        fast = design_fn is None and "recurrence" not in design_guidance and initial_state_overwrite is None
         t_first, n_steps = self.num_timesteps - 1, self.num_timesteps - int(t_stop)
         # (the device record buffer is allocated only on the routes that are library chains)
         device_rec = lambda: self._recorder(return_trajectory_every, trajectory, n_steps, full, device, t_start=t_first)
@@ -603,31 +734,40 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
             return self._recorded(self._run_guided_loop(img, cond, desc, dz, t_first, t_stop, noise=noise, seed=seed,
                                                         sample_offset=sample_offset, inpaint_cond=inpaint,
                                                         initial_state_overwrite=initial_state_overwrite, use_graph=use_graph,
-                                                        rec=rec, tables=tables), rec)
+                                                        rec=rec, tables=tables, karm=karm), rec)
         if fast:
             rec = device_rec()
             return self._recorded(self._run_loop(img, cond, desc, t_first, t_stop,
                                                  noise_steps=None if noise is None else noise.step, seed=seed,
                                                  sample_offset=sample_offset, inpaint_cond=inpaint,
                                                  inpaint_noise_steps=None if noise is None else noise.cond,
-                                                 use_graph=use_graph, rec=rec), rec)
+                                                 use_graph=use_graph, rec=rec, karm=karm), rec)
         img_T = img
         # this route loops in Python: the same record, cloned per step
         rec = None if return_trajectory_every is None else LoopRecorder(n_steps, return_trajectory_every, trajectory, t_start=t_first)
+
+        kz = lambda row, word: self._known_z(full, row, word, seed, sample_offset, device)
 
         def chain():
             # (the steps' predictions only feed the next step: the exchange flags are read once, after the last one)
             img = img_T
             if rec is not None:
                 rec.reset()
+            if kn is not None:      # rule 1
+                img = self.known_replace(img, kn[0], kn[1], t_first, kz(None if noise is None else noise.known_init, self.num_timesteps))
             for i, t in enumerate(reversed(range(t_stop, self.num_timesteps))):
                 nz = None if noise is None else noise.step[t]
                 rn = None if (noise is None or noise.recur is None) else noise.recur[t]
+                relaxed = {} if kn is None else dict(after_relax=lambda r, x, t=t: self.known_replace(
+                    x, kn[0], kn[1], t, kz(None if noise is None else noise.known_recur[t][r], t + 0x10000 * (r + 1))))
                 img, x_start = self._guided_step(img, cond, t, desc, design_fn, design_guidance, initial_state_overwrite, nz, rn,
-                                                 check=False)
+                                                 check=False, **relaxed)
                 if inpaint is not None:
                     zc = noise.cond[t] if (noise is not None and noise.cond is not None) else torch.randn_like(inpaint)
                     img[:, :inpaint.shape[1], :] = self.q_sample(self._f32(inpaint, device), t, zc)
+                if kn is not None:      # the region overwrites last, at the level the step has reached
+                    img = self.known_replace(img, kn[0], kn[1], t - 1,
+                                             None if t == 0 else kz(None if noise is None else noise.known_step[t], t - 1))
                 if rec is not None:
                     rec.after(i, img, x_start)
             return img
@@ -641,8 +781,8 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
     def sample(self, batch_size=16, cond=None, is_composing_time=False, n_composed=2, compose_start_step=4,
                compose_n_bodies=2, compose_mode="mean", design_fn=None, design_guidance="standard",
                initial_state_overwrite=None, initialization_mode=0, initialization_img=None, **build_kw):
-        """:2330-2376.  ``build_kw``: noise=, seed=, sample_offset=, use_graph=, t_stop=, return_trajectory_every=, trajectory=
-        (see p_sample_loop)."""
+        """:2330-2376.  ``build_kw``: noise=, seed=, sample_offset=, use_graph=, t_stop=, return_trajectory_every=, trajectory=,
+        known=, known_mask= (see p_sample_loop; the known region is held by the DDPM and the DDIM route alike)."""
         self.is_ddim_sampling = self.sampling_timesteps < self.num_timesteps
         if self.is_ddim_sampling:               # :2348-2363
             build_kw.pop("t_stop", None)
@@ -792,7 +932,8 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
     def ddim_sample(self, shape, cond, n_composed=None, clip_denoised=True, compose_start_step=4, compose_n_bodies=2,
                     compose_mode="mean", design_fn=None, design_guidance="standard", initial_state_overwrite=None,
                     initialization_mode=0, initialization_img=None, *, noise=None, seed=None, sample_offset=0,
-                    use_graph=True, init_img=None, step_range=None, return_trajectory_every=None, trajectory=("x",)):
+                    use_graph=True, init_img=None, step_range=None, return_trajectory_every=None, trajectory=("x",),
+                    known=None, known_mask=None):
         """:1724-1804.  Build-only keywords: ``init_img`` + ``step_range=(i0, i1)`` run DDIM steps i0 .. i1-1 from a given
         state (teacher-forced segments for parity tests: the deterministic sampler amplifies a 1e-6 perturbation of the
         U-Net to 1e-3 .. 1e-2 over 50 .. 250 steps with random-init weights -- measured on the CPU reference itself).
@@ -804,7 +945,16 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         chain (``cindm_ddpm1d_sample_ddim_guided``; counter-based draws keyed by (seed, sample_offset + b, t, element) when there
         is no tape); any other callable or guidance: each step is ``recurrence`` library predictions + the user's autograd
         gradient, and the DDIM update of the tiny state runs in torch.
-        ``return_trajectory_every`` / ``trajectory``: as p_sample_loop; steps are counted from the first step this call runs."""
+        ``return_trajectory_every`` / ``trajectory``: as p_sample_loop; steps are counted from the first step this call runs.
+        ``known`` / ``known_mask``: replacement conditioning as p_sample_loop -- q(k, times[0], z_init) before the first step (skipped
+        with ``init_img``, whose caller hands over a state that is already at its level, so that teacher-forced segments chain
+        exactly), q(k, t, z) after every relaxation iteration, q(k, times[i + 1], z) after step i, k itself after the last pair; the
+        tape's ``known_step`` / ``known_recur`` rows are indexed by the DDIM step."""
+        n_pairs = len(self.ddim_schedule()[0]) - 1
+        iters = max(int(design_guidance.split("-")[-1]) if "recurrence" in design_guidance else 0, 1)
+        kn = self._known_region(tuple(shape), known, known_mask, cond, initial_state_overwrite, noise,
+                                n_pairs if step_range is None else int(step_range[1]), 0 if design_fn is None else iters,
+                                init=init_img is None)
         device = self.betas.device
         if device.type != "cuda":
             raise _ffi.CindmError("GaussianDiffusion1D is on the CPU: move it to a ROCm device; there is no CPU execution path")
@@ -824,8 +974,12 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         times, coefs = times[i0:i1 + 1], coefs[i0:i1].contiguous()
         if noise is not None:
             sl = lambda v: None if v is None else v[i0:i1].contiguous()
-            noise = NoiseTape(noise.init, sl(noise.step), sl(noise.recur), sl(noise.cond))
+            noise = NoiseTape(noise.init, sl(noise.step), sl(noise.recur), sl(noise.cond), known_init=noise.known_init,
+                              known_step=sl(noise.known_step), known_recur=sl(noise.known_recur))
         S = len(times) - 1
+        full = tuple(img.shape)
+        karm = self._known_armer(kn, full, noise, device, init=init_img is None)
+        kz = lambda row, word: self._known_z(full, row, word, seed, sample_offset, device)
         inpaint = cond if (self.conditioned_steps == 0 and cond is not None) else None
         if design_fn is None:
             desc = self._desc_for(shape, None, clip=clip_denoised)
@@ -838,6 +992,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
 
             def call(h, un, ws):
                 self._arm(rec, h)
+                self._arm_known(karm, h)
                 with torch.cuda.device(device):
                     _ffi.check(_ffi.lib().cindm_ddpm1d_sample_ddim(
                         h, self.model._h, un, C.byref(desc), _ffi.ptr(img), _ffi.ptr(cond_d), S, tarr, _ffi.ptr(carr),
@@ -857,7 +1012,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
             return self._recorded(self._run_guided_ddim(img, cond, desc, dz, times, coefs, noise=noise, seed=seed,
                                                         sample_offset=sample_offset, inpaint_cond=inpaint,
                                                         initial_state_overwrite=initial_state_overwrite, use_graph=use_graph,
-                                                        rec=rec, tables=tables), rec)
+                                                        rec=rec, tables=tables, karm=karm), rec)
         coefs = coefs.to(device)
         img_T = img
         # this route loops in Python: the same record, cloned per step
@@ -867,10 +1022,14 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
             img = img_T
             if rec is not None:
                 rec.reset()
+            if kn is not None and init_img is None:      # rule 1
+                img = self.known_replace(img, kn[0], kn[1], times[0], kz(None if noise is None else noise.known_init, self.num_timesteps))
             for i, (t, tn) in enumerate(zip(times[:-1], times[1:])):
                 rn = None if (noise is None or noise.recur is None) else noise.recur[i]
+                relaxed = {} if kn is None else dict(after_relax=lambda r, x, i=i, t=t: self.known_replace(
+                    x, kn[0], kn[1], t, kz(None if noise is None else noise.known_recur[i][r], t + 0x10000 * (r + 1))))
                 eps, x_start = self._guided_step(img, cond, t, desc, design_fn, design_guidance, initial_state_overwrite,
-                                                 None, rn, ddim_return=True, check=False)
+                                                 None, rn, ddim_return=True, check=False, **relaxed)
                 if tn < 0:
                     img = x_start
                 else:
@@ -879,6 +1038,8 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
                     if inpaint is not None:
                         zc = noise.cond[i] if (noise is not None and noise.cond is not None) else torch.randn_like(inpaint)
                         img[:, :inpaint.shape[1], :] = self.q_sample(self._f32(inpaint, device), t, zc)
+                if kn is not None:      # the region overwrites last, at the level the step has reached (the last pair: k itself)
+                    img = self.known_replace(img, kn[0], kn[1], tn, None if tn < 0 else kz(None if noise is None else noise.known_step[i], tn))
                 if rec is not None:
                     rec.after(i, img, x_start)
             return img

@@ -138,15 +138,31 @@ def _no_trajectory(sample_kw):
                          "own sample method on each rank for return_trajectory_every=")
 
 
+def shard_known1d(sample_kw, batch_size, lo, hi):
+    """``sample_kw`` with the 1-D replacement conditioning cut to the designs lo .. hi-1: ``known`` / ``known_mask`` along their first
+    axis when they carry the design axis (three dimensions, the first of size ``batch_size``); a table shared by all designs
+    ([rows, F], or a mask that broadcasts over the designs) serves every rank as it is."""
+    kw = dict(sample_kw)
+    for name in ("known", "known_mask"):
+        v = kw.get(name)
+        if v is not None and v.dim() == 3 and v.shape[0] != 1:
+            if v.shape[0] != batch_size:
+                raise ValueError(f"{name} has {v.shape[0]} designs, the call samples {batch_size}")
+            kw[name] = v[lo:hi]
+    return kw
+
+
 def sample_sharded(diffusion, batch_size, *, seed, group=None, gather=True, cond=None, **sample_kw):
     """``diffusion.sample(batch_size=...)`` with the batch partitioned over the process group.
-    ``cond`` (if given) is the GLOBAL [batch_size, ...] tensor; each rank takes its slice."""
+    ``cond`` (if given) is the GLOBAL [batch_size, ...] tensor; each rank takes its slice, and per-design ``known=`` /
+    ``known_mask=`` tables theirs (shard_known1d)."""
     _no_trajectory(sample_kw)
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)
     else:
         rank, world = 0, 1
     lo, hi = shard_bounds(batch_size, rank, world)
+    sample_kw = shard_known1d(sample_kw, batch_size, lo, hi)
     local_cond = None if cond is None else cond[lo:hi]
     design_fn = sample_kw.get("design_fn")
     if hasattr(design_fn, "shard"):        # an objective with per-design tables (WaypointObjective): each rank takes its slice

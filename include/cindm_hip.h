@@ -482,6 +482,43 @@ int  cindm_ddpm1d_set_known2d(cindm_ddpm1d* h, const float* known, const uint8_t
                               int64_t state_step_stride, int64_t boundary_step_stride,
                               int64_t images, int32_t hw, int32_t cp);
 
+/* Replacement conditioning of the 1-D chains: a known region of the state x [B, rows, F] (the rows sample() returns; F = 4 * n_bodies)
+ * is held on the forward-diffusion trajectory of its clean values k and returned exactly (known1d_kernel: one more node of the
+ * captured step, after the update in whichever form -- fused into the U-Net's last kernel, compose_update_kernel, guided -- after the
+ * guided DDPM step's staging copy and the counter, before the record node).  No reference counterpart; inpaint_cond and
+ * initial_state_overwrite keep the reference's semantics.  With q(k, l, z) = sqrt_alphas_cumprod[l] k + sqrt_one_minus_alphas_cumprod[l] z
+ * (two products and a sum, each rounded once):
+ *   before the first step, which is at timestep t0 (apply_init != 0):   x[m] = q(k, t0, z_init)
+ *   after relaxation iteration r of a guided step at t (the state is back at level t):   x[m] = q(k, t, z)
+ *   after the step's last update, t -> t_next (DDPM: t - 1, DDIM: times[i + 1]):   x[m] = q(k, t_next, z) if t_next >= 0, else x[m] = k
+ * so the chain's result carries k exactly on the region (a DDPM chain with t_end > 0 ends at level t_end - 1 like the rest).  The
+ * level is read from the device step state, so one captured graph serves every step.  The region overwrites last: rows also claimed
+ * by inpaint_cond or initial_state_overwrite carry the region's values.
+ * known: DEVICE floats [batch | 1, rows, feats] (known_per_design != 0: one table per design; 0: one shared by all designs).
+ * mask:  DEVICE bytes of the same layout, [batch | 1, rows, feats] by mask_per_design: non-zero = the element is known.
+ * noise_init [batch, rows, feats]; noise_steps [.][batch, rows, feats] with step_stride floats between rows, row = t (DDPM) or the
+ *        DDIM step index, as the chains' own step tapes; noise_recur [.][iters][batch, rows, feats] with recur_stride floats between
+ *        rows, record r read after relaxation r (iters = the guided step's iterations, as the chains' recurrence tape): explicit z
+ *        for parity runs.  noise_steps NULL (then all three NULL): the counter-based generator under a seed word of its own, keyed
+ *        (seed, sample_offset + design, word, element) with the chain call's seed and sample_offset; word = t_next after a step,
+ *        t + 0x10000 (r + 1) after relaxation r, the timestep count for z_init.  noise_recur is needed only by a guided chain with more
+ *        than one iteration per step; noise_init only with apply_init.
+ * apply_init: 0 skips the first rule -- for a caller that hands over a state already at its level (teacher-forced DDIM segments).
+ * cindm_ddpm1d_set_known1d arms the NEXT chain call on this handle; that call consumes the region whether it succeeds or fails, and
+ * (NULL, NULL) disarms.  Served by cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided, which check batch == B,
+ * rows and feats against the state, the strides and the 16-byte alignment of x and of the workspace's second state buffer before they
+ * launch or copy anything; cindm_ddpm1d_sample_autoregress, cindm_ddpm1d_sample_ula and every 2-D chain entry refuse an armed region.
+ * All buffers are the caller's, 16-byte aligned, and must stay alive and unchanged until the chain's work has finished (use_graph:
+ * when the call returns; otherwise in stream order).  Their addresses are operands of the captured node and part of the graph's key.
+ * An exchange-free re-run starts from the first rule again; a recorder records x after the overwrite, x0 is the model's prediction.
+ * With nothing armed a chain launches exactly what it launched before this entry existed (the same cindm_ddpm1d_last_step_info
+ * count, the same graph key); with a region, one launch more per update and one per chain. */
+int  cindm_ddpm1d_set_known1d(cindm_ddpm1d* h, const float* known, int32_t known_per_design,
+                              const uint8_t* mask, int32_t mask_per_design,
+                              const float* noise_init, const float* noise_steps, int64_t step_stride,
+                              const float* noise_recur, int64_t recur_stride, int32_t apply_init,
+                              int64_t batch, int32_t rows, int32_t feats);
+
 /* ===================================================================== 2-D airfoil path
  * Replaces Unet.forward (model/diffusion_2d.py:369-408) and GaussianDiffusion.p_sample /
  * p_sample_loop (model/diffusion_2d.py:788-907) of the reference for the sampling path
