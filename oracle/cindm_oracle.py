@@ -125,7 +125,8 @@ def sinusoidal_pos_emb(t, dim):
 
 def time_mlp(sd, t, dim):
     """TemporalUnet1D.time_mlp, model/diffusion_1d.py:537-542."""
-    e = sinusoidal_pos_emb(t, dim)
+    # (.to: the same tensor for fp32 weights; oracle/f64_reference.py passes float64 ones and gets the fp32 sinusoid cast up)
+    e = sinusoidal_pos_emb(t, dim).to(sd["time_mlp.1.weight"].dtype)
     e = F.linear(e, sd["time_mlp.1.weight"], sd["time_mlp.1.bias"])
     e = F.mish(e)
     return F.linear(e, sd["time_mlp.3.weight"], sd["time_mlp.3.bias"])
@@ -983,7 +984,7 @@ def unet2d_forward(sd, x, t, taps=None):
     x = F.conv2d(x, sd["init_conv.weight"], sd["init_conv.bias"], padding=3)
     r = x
     tap("init_conv", x)
-    e = sinusoidal_pos_emb(t, dim)
+    e = sinusoidal_pos_emb(t, dim).to(sd["time_mlp.1.weight"].dtype)      # (as in time_mlp above)
     e = F.linear(e, sd["time_mlp.1.weight"], sd["time_mlp.1.bias"])
     e = F.gelu(e)
     temb = F.linear(e, sd["time_mlp.3.weight"], sd["time_mlp.3.bias"])
