@@ -22,6 +22,11 @@ struct cindm_forceunet : ModelCore {
     unsigned* err_dev = nullptr;       // raised by a timed-out exchange of fu_gn_silu_bwd_cluster_kernel (cindm_forceunet_status)
     int nx_force = 0;                  // the exchange-free re-run of a chain / gradient call is in progress
     int recovered = 0;                 // chains / calls re-run on the exchange-free derivative after a time-out
+    // option "taps": where the block outputs of the last forward / grad / vjp call lie in the caller's workspace (cindm_forceunet_tap)
+    struct Tap { size_t off_p, off_g; int C, H; };
+    std::unordered_map<std::string, Tap> taps;
+    int64_t taps_imgs = 0;
+    bool taps_grad = false;            // that call ran the backward: the gradient at every tap exists
 };
 
 // kernel-path options (cindm_forceunet_set_option), as on the U-Net handles
@@ -39,6 +44,9 @@ static const OptDef kForceUnetOpts[] = {
     {"no_exchange", 0, nullptr, OPT_RUNTIME}, // 1 = no kernel that waits for another workgroup (gn_bwd_fused behaves as 1)
     {"recover", 1, nullptr, OPT_RUNTIME},     // 0: a timed-out exchange is an error instead of an exchange-free re-run
     {"dbg", 0, nullptr, OPT_RUNTIME},         // 39: force the exchange time-out (tests)
+    // 1: every block output and its gradient stay readable after a call (cindm_forceunet_tap): a residual chain copies the gradient
+    // into the destination's own buffer instead of sharing one (same arithmetic, same workspace).  Off on every sampling path.
+    {"taps", 0, nullptr, OPT_RUNTIME},
 };
 
 extern "C" int cindm_forceunet_set_option(cindm_forceunet* h, const char* key, int32_t value) { return core_set_option(h, key, value) < 0 ? -1 : 0; }
@@ -368,6 +376,7 @@ struct FT { float* p = nullptr; float* g = nullptr; int C = 0, H = 0; bool gset 
 
 struct FuRun {
     cindm_forceunet* h; hipStream_t st; char* ws; size_t off = 0; bool dry; int64_t NI; bool want_grad;
+    bool taps = false;                 // option "taps" on an entry that serves them: pass_grad copies instead of sharing
     std::deque<FT> ts;
     std::vector<std::function<void()>> bwd;
     hipError_t err = hipSuccess;
@@ -380,9 +389,16 @@ struct FuRun {
     float beta_of(FT* t) { const float b = t->gset ? 1.f : 0.f; t->gset = true; return b; }
 
     // dst.g += src.g where src is dead after the calling backward step: the FIRST contribution to dst shares src's buffer
-    // instead of copying it (later contributions accumulate into that buffer in place; every user reads ->g when it runs)
+    // instead of copying it (later contributions accumulate into that buffer in place; every user reads ->g when it runs).
+    // With taps the first contribution is copied into dst's own buffer (every FT has one from ten()), so that src.g survives the
+    // call: copying, then accumulating the same contributions in the same order, is the same arithmetic bit for bit.
     void pass_grad(FT* src, FT* dst) {
-        if (!dst->gset) { dst->g = src->g; dst->gset = true; return; }
+        if (!dst->gset) {
+            dst->gset = true;
+            if (!taps) { dst->g = src->g; return; }
+            hipLaunchKernelGGL(fu_add_kernel, dim3(blocks(numel(src))), dim3(256), 0, st, src->g, dst->g, 0.f, numel(src));
+            return;
+        }
         hipLaunchKernelGGL(fu_add_kernel, dim3(blocks(numel(src))), dim3(256), 0, st, src->g, dst->g, 1.f, numel(src));
     }
     void conv_launch(const FuPacked& pk, bool bwd_w, const float* x, float* y, int H, float beta, bool use_bias, int unshuf_src = 0) {
@@ -704,21 +720,27 @@ struct FuRun {
 
 // forward (and, when dinp is given, the gradient of sum_img lambda |out0| + out1 with respect to the input)
 static int fu_network(cindm_forceunet* h, const float* inp, float* out, float* dinp, float lambda_force, int64_t NI,
-                      void* ws, size_t ws_bytes, hipStream_t st, bool dry, size_t* need, const float* dout = nullptr) {
+                      void* ws, size_t ws_bytes, hipStream_t st, bool dry, size_t* need, const float* dout = nullptr, bool serve_taps = false) {
     FuRun R{h, st, (char*)ws, 0, dry, NI, dinp != nullptr};
+    // serve_taps: the three entries whose workspace the caller holds (not the design gradient, which lays out its own)
+    R.taps = serve_taps && !dry && h->O("taps") != 0;
+    if (serve_taps && !dry && !h->taps.empty()) { h->taps.clear(); h->taps_imgs = 0; }
+    std::vector<std::pair<std::string, FT*>> named;      // block outputs under the reference's module names
+    const std::string top;
+    auto tap = [&](const std::string& p, const char* name, FT* t) { if (R.taps) named.emplace_back(p + name, t); return t; };
     const int n = h->d.n_mults, S = h->d.image_size;
     FT xin; xin.p = const_cast<float*>(inp); xin.g = dinp; xin.C = h->d.channels; xin.H = S;
-    FT* x = R.conv(&xin, "init_conv");
+    FT* x = tap(top, "init_conv", R.conv(&xin, "init_conv"));
     for (int ind = 0; ind < n; ++ind) {
         const std::string p = "downs." + std::to_string(ind);
-        x = R.resblock(x, p + ".0");
-        x = R.resblock(x, p + ".1");
-        x = R.linattn(x, p + ".2");
-        if (ind < n - 1) x = R.conv_unshuffled(x, p + ".3.1"); else x = R.conv(x, p + ".3");
+        x = tap(p, ".0", R.resblock(x, p + ".0"));
+        x = tap(p, ".1", R.resblock(x, p + ".1"));
+        x = tap(p, ".2", R.linattn(x, p + ".2"));
+        x = tap(p, ".3", ind < n - 1 ? R.conv_unshuffled(x, p + ".3.1") : R.conv(x, p + ".3"));
     }
-    x = R.resblock(x, "mid_block1");
-    x = R.attn(x, "mid_attn");
-    x = R.resblock(x, "mid_block2");
+    x = tap(top, "mid_block1", R.resblock(x, "mid_block1"));
+    x = tap(top, "mid_attn", R.attn(x, "mid_attn"));
+    x = tap(top, "mid_block2", R.resblock(x, "mid_block2"));
     if (need) *need = R.off + 256;
     if (dry) return 0;
     REQUIRE(R.off + 256 <= ws_bytes, "workspace too small");
@@ -731,6 +753,15 @@ static int fu_network(cindm_forceunet* h, const float* inp, float* out, float* d
     }
     R.chk();
     if (R.err != hipSuccess) return fail(std::string("ForceUnet launch: ") + hipGetErrorString(R.err));
+    if (R.taps) {
+        // taken after the backward has been issued: pass_grad redirects ->g while it runs (without taps; with them every tensor keeps
+        // the buffer ten() gave it)
+        for (const auto& nt : named) {
+            const FT* t = nt.second;
+            h->taps[nt.first] = {(size_t)(reinterpret_cast<char*>(t->p) - R.ws), t->g ? (size_t)(reinterpret_cast<char*>(t->g) - R.ws) : (size_t)0, t->C, t->H};
+        }
+        h->taps_imgs = NI; h->taps_grad = dinp != nullptr;
+    }
     return 0;
 }
 
@@ -745,14 +776,14 @@ extern "C" size_t cindm_forceunet_workspace_bytes(const cindm_forceunet* h, int6
 extern "C" int cindm_forceunet_forward(cindm_forceunet* h, const float* x, float* out, int64_t images, void* ws, size_t ws_bytes, void* stream) {
     REQUIRE(h && x && out && ws, "null argument");
     REQUIRE(h->finalized, "cindm_forceunet_finalize has not been called");
-    return fu_network(h, x, out, nullptr, 0.f, images, ws, ws_bytes, (hipStream_t)stream, false, nullptr);
+    return fu_network(h, x, out, nullptr, 0.f, images, ws, ws_bytes, (hipStream_t)stream, false, nullptr, nullptr, true);
 }
 
 extern "C" int cindm_forceunet_grad(cindm_forceunet* h, const float* x, float lambda_force, float* out, float* dx, int64_t images,
                                     void* ws, size_t ws_bytes, void* stream) {
     REQUIRE(h && x && out && dx && ws, "null argument");
     REQUIRE(h->finalized, "cindm_forceunet_finalize has not been called");
-    return fu_network(h, x, out, dx, lambda_force, images, ws, ws_bytes, (hipStream_t)stream, false, nullptr);
+    return fu_network(h, x, out, dx, lambda_force, images, ws, ws_bytes, (hipStream_t)stream, false, nullptr, nullptr, true);
 }
 
 // vector-Jacobian product: dx = d( sum_img dout[img] . out[img] ) / dx for a caller-given dout [images, 2] -- the backward of
@@ -762,10 +793,28 @@ extern "C" int cindm_forceunet_vjp(cindm_forceunet* h, const float* x, const flo
                                    void* ws, size_t ws_bytes, void* stream) {
     REQUIRE(h && x && dout && out && dx && ws, "null argument");
     REQUIRE(h->finalized, "cindm_forceunet_finalize has not been called");
-    return fu_network(h, x, out, dx, 0.f, images, ws, ws_bytes, (hipStream_t)stream, false, nullptr, dout);
+    return fu_network(h, x, out, dx, 0.f, images, ws, ws_bytes, (hipStream_t)stream, false, nullptr, dout, true);
 }
 
-// design_fn of inference/inverse_design_2d.py:208-214: grad = d force / dx + lambda_overlap * d overlap / dx, on the
+// Test hook (include/cindm_hip.h): a block output of the last forward / grad / vjp call run with option "taps" = 1, or the gradient
+// of that call's objective with respect to it, copied out of the caller's workspace.
+extern "C" int cindm_forceunet_tap(cindm_forceunet* h, const char* name, int32_t grad, int64_t images, void* ws, float* dst,
+                                   int64_t dst_cap, int64_t shape[3], void* stream) {
+    REQUIRE(h && name && ws && shape, "null argument");
+    auto it = h->taps.find(name);
+    if (it == h->taps.end()) return fail(std::string("unknown tap: ") + name);
+    REQUIRE(images == h->taps_imgs, "tap: image count differs from the last call");
+    REQUIRE(!grad || h->taps_grad, "tap: the last call was forward-only, no gradient was computed");
+    const cindm_forceunet::Tap& t = it->second;
+    const int64_t n = images * (int64_t)t.H * t.H * t.C;
+    shape[0] = images; shape[1] = (int64_t)t.H * t.H; shape[2] = t.C;
+    if (!dst) return 0;
+    REQUIRE(n <= dst_cap, "tap: destination too small");
+    HIPCHK(hipMemcpyAsync(dst, (char*)ws + (grad ? t.off_g : t.off_p), n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+// design_fn of inference/inverse_design_2d.py:208-214: grad =d force / dx + lambda_overlap * d overlap / dx, on the
 // sampler's device layout [B * nb][pixel][CP] (CP = padded channels, Cs = 3 * frames + 3 real ones)
 // fpp = frames per network pass: the surrogate sees fpp * B * nb images at once (the deep levels of one frame's 128 images
 // leave most of the GPU idle; 768 images fill it)

@@ -6,6 +6,9 @@ gradient of (summed lift / drag surrogate forces + lambda * boundary overlap) wi
 evaluated by libcindm_hip.so (forward AND input-gradient kernels) instead of ``torch.autograd.grad``.  It plugs into
 ``GaussianDiffusion.sample(design_fn=..., design_guidance="standard-alpha")`` unchanged: the 2-D convention is that
 ``design_fn(x)`` returns the gradient tensor (model/diffusion_2d.py:813)."""
+import ctypes as C
+import math
+
 import torch
 
 from . import _ffi
@@ -103,6 +106,23 @@ class ForceUnet(_ExchangeRecovery, _NativeModel):
     def input_grad(self, x, lambda_force=1.0):
         """(out [N, 2], d(sum_n lambda_force * |out[n, 0]| + out[n, 1]) / dx [N, C, H, W])."""
         return self._run(x, lambda_force)
+
+    def tap(self, name, images, grad=False):
+        """Test hook, option ``taps`` = 1: the block output ``name`` of the last ``forward`` / ``input_grad`` call (or, ``grad``, the
+        gradient of that call's objective with respect to it) as [images, C, H, W].  Names as the reference's modules: ``init_conv``,
+        ``downs.i.0`` .. ``downs.i.3``, ``mid_block1``, ``mid_attn``, ``mid_block2``."""
+        ws = self._ws
+        if ws is None:
+            raise _ffi.CindmError("tap: no forward / input_grad call has run on this model")
+        L, shape = _ffi.lib(), (C.c_int64 * 3)()
+        with torch.cuda.device(ws.device):
+            args = (self._h, name.encode(), int(bool(grad)), images, _ffi.ptr(ws))
+            _ffi.check(L.cindm_forceunet_tap(*args, None, 0, C.byref(shape), _ffi.current_stream(ws.device)))
+            n, hw, c = shape[0], shape[1], shape[2]
+            dst = torch.empty(n * hw * c, dtype=torch.float32, device=ws.device)
+            _ffi.check(L.cindm_forceunet_tap(*args, _ffi.ptr(dst), dst.numel(), C.byref(shape), _ffi.current_stream(ws.device)))
+        s = int(round(math.sqrt(hw)))
+        return dst.view(n, s, s, c).permute(0, 3, 1, 2).contiguous()
 
 
 class _ForceUnetFn(torch.autograd.Function):

@@ -664,7 +664,10 @@ int  cindm_forceunet_set_param(cindm_forceunet* h, const char* key, const float*
  * rule; "range_fallback" (read-only) = 1 when that forward switched the handle to the fp32 convolutions; "stress" > 0:
  * pseudo-random delays before the producer -> consumer hand-overs of the persistent convolution kernel (race tests; run-time);
  * "la_fused" (0 = LinearAttention sites layer by layer), "gn_bwd_fused" (0 / 1 / 2: the GroupNorm + SiLU derivative), "ws_nosplit",
- * and the run-time options "no_exchange", "recover", "dbg". */
+ * and the run-time options "no_exchange", "recover", "dbg", and "taps" (1 = the block outputs and their gradients of every
+ * cindm_forceunet_forward / _grad / _vjp call stay readable for cindm_forceunet_tap: a residual chain's gradient is copied into each
+ * tensor's own buffer instead of accumulating in one shared buffer -- out and dx bit for bit those of taps = 0, the same workspace
+ * size; off on every sampling path). */
 int  cindm_forceunet_set_option(cindm_forceunet* h, const char* key, int32_t value);
 int  cindm_forceunet_get_option(const cindm_forceunet* h, const char* key, int32_t* value);
 /* folds weight standardisation, packs forward and backward-data fragments, runs the range rule's calibration forward */
@@ -680,6 +683,13 @@ int  cindm_forceunet_grad(cindm_forceunet* h, const float* x, float lambda_force
  * runs against this model as written */
 int  cindm_forceunet_vjp(cindm_forceunet* h, const float* x, const float* dout, float* out, float* dx, int64_t images,
                          void* ws, size_t ws_bytes, void* stream);
+/* Test hook (option "taps" = 1): copy the block output `name` of the last forward / grad / vjp call (grad = 0), or the gradient of that
+ * call's objective with respect to it (grad = 1; refused after a forward-only call), out of that call's workspace `ws` into dst as
+ * [images, H*W, C]; shape receives (images, H*W, C), with dst == NULL only that.  Names as the reference's modules: init_conv,
+ * downs.i.0 .. downs.i.3, mid_block1, mid_attn, mid_block2.  cindm_airfoil_design_grad and the chains lay out a workspace of
+ * their own and serve no taps. */
+int  cindm_forceunet_tap(cindm_forceunet* h, const char* name, int32_t grad, int64_t images, void* ws, float* dst,
+                         int64_t dst_cap, int64_t shape[3], void* stream);
 /* 1 when an in-kernel exchange between workgroups of this handle's kernels (the GroupNorm derivative on whole pixel rows, option
  * gn_bwd_fused = 2) timed out since the last call -- the affected gradients are NaN, never finite and wrong --, 0 otherwise; clears
  * the flag; synchronises `stream`.  cindm_ddpm2d_sample_force reads it at the end of the chain and re-runs ONCE from the kept x_T
