@@ -118,6 +118,8 @@ SIGNATURES = {
                                            _vp, _i32, _vp, _i64, _vp, _sz, _vp, _i32]),
     "cindm_ddpm1d_sample_autoregress": (C.c_int, [_vp, _vp, _vp, C.POINTER(ComposeDesc), _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp,
                                                   _vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _i32]),
+    "cindm_ddpm1d_sample_timecompose": (C.c_int, [_vp, _vp, _vp, C.POINTER(ComposeDesc), _vp, _vp, _vp, _i32, _i32, _vp, _vp,
+                                                  _vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _i32]),
     "cindm_ddpm1d_sample_ula": (C.c_int, [_vp, _vp, _vp, C.POINTER(ComposeDesc), _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp,
                                           _u64, _i64, _i64, _vp, _sz, _vp, _i32]),
     "cindm_ddpm1d_sample_guided": (C.c_int, [_vp, _vp, _vp, C.POINTER(ComposeDesc), C.POINTER(DesignDesc), _vp, _vp, _vp, _vp,

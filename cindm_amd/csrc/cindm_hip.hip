@@ -2020,6 +2020,7 @@ extern "C" int cindm_unet1d_tap(cindm_unet1d* h, const char* name, int64_t rows,
 
 #include "chain_host.inc"
 #include "ddpm1d_host.inc"
+#include "timecompose_host.inc"
 
 // ============================================================================ 2-D airfoil path
 #include "unet2d_host.inc"

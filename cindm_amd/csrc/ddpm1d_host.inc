@@ -182,6 +182,7 @@ struct StepIO {
     const float* ula_tab; int ula_L, ula_t_hi;         // Langevin loop: per-timestep (scalar, ss, std, -) rows (device), inner count, first timestep
     int rec;                // recorded chain: the recorder's stream mask on the call that ends a step (chain_record_kernel follows it), else 0
     int kn, relax_idx;      // chain with a known region: known1d_kernel follows every update; the relaxation's index (a constant of the captured iteration)
+    const TimeComposeArgs* tc;     // parallel time composition (timecompose_host.inc): its update kernel's own operands, or null
 };
 
 // What a step refuses of its Chain1D and state (x, and cond where the descriptor prepends it): run_step's own checks
@@ -344,6 +345,11 @@ static int run_step(const Chain1D& ch, const StepIO& io, int32_t t, const int32_
         UlaArgs u;
         u.c = a; u.tab = io.ula_tab; u.L = io.ula_L; u.t_hi = io.ula_t_hi; u.noise_it_stride = io.noise_t_stride;
         hipLaunchKernelGGL(ula_update_kernel, dim3((unsigned)((ne / 4 + 255) / 256)), dim3(256), 0, stream, u);
+    } else if (io.tc) {
+        // parallel time composition: the DDIM update keyed per segment, with the hand-over of every segment's tail to the next one's condition
+        TimeComposeArgs u = *io.tc;
+        u.c = a;
+        hipLaunchKernelGGL(timecompose_update_kernel, dim3((unsigned)((ne / 4 + 255) / 256)), dim3(256), 0, stream, u);
     } else if (!pair->fused_done) hipLaunchKernelGGL(compose_update_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a);
     pair->epoch_slot = 0;
     if (uncond) uncond->epoch_slot = 0;
@@ -574,6 +580,7 @@ static void key_common(KeyBuilder& K, int kind, const Chain1D& ch, const StepIO&
     K(io.x)(io.cond)(io.x_out)(io.noise)(io.noise_t_stride)(io.add_noise)(io.inp_cond)(io.inp_steps)(io.inp_noise)(io.inp_noise_t_stride);
     K(io.ddim_tab)(io.ddim_tnext)(io.iso)(io.iso_steps)(io.recur_t_stride);
     K(io.rec)(io.x0_out);      // recorder on, which streams; the x0 stream's staging record is an operand of the captured update
+    if (io.tc) K(io.tc->cond_buf)(io.tc->seeds)(io.tc->Bseg)(io.tc->n_seg);      // (nothing set: the key is what it was)
     if (io.kn && ch.h->kn1) {  // known region: everything the captured node embeds (nothing armed: the key is what it was)
         const Known1D& k = *ch.h->kn1;
         K(io.kn)(k.known)(k.mask)(k.known_per_design)(k.mask_per_design)(k.z_step)(k.step_stride)(k.z_recur)(k.recur_stride);

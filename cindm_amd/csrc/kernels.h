@@ -3754,6 +3754,124 @@ __global__ void compose_update_kernel(const ComposeArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Parallel time composition (composing_time_sample, model/diffusion_1d.py:1807-1854): ONE unguided DDIM chain on the
+// n_seg * B rows of x [n_seg * B, Ltot, F], segment-major (row = k B + b); at the top of every step segment k + 1 is conditioned on
+// the last Lc rows of segment k's CURRENT (noisy) state (:1827-1829).  c is the step's ComposeArgs with c.B = n_seg * B rows and
+// c.cond = cond_buf, plain (mode 0) or multibody (mode 5) prediction.
+//   timecompose_update_kernel   the DDIM update of compose_update_element (same expressions, each product and sum rounded once, the
+//                               noise not re-derived) with the step noise of row (k, b) keyed (seeds[k], sample_off + b, t, element);
+//                               a thread that writes a tail row (>= Ltot - Lc) of a segment k < n_seg - 1 also writes the value into
+//                               cond_buf of row (k + 1, b): the hand-over the NEXT step reads.  The step's gather has read cond_buf
+//                               before this launch starts and nothing after it in the step reads it: no hazard inside the step.
+//   timecompose_init_kernel     x_T of every row (init tape, or fill_normal_kernel's draw under seeds[k]), the first hand-over from
+//                               it, and the caller's cond into rows 0 .. B of cond_buf.
+// One thread per four consecutive features (F % 4 == 0: they share row and position): 16-byte loads and stores, every pointer
+// 16-byte aligned (checked by the host).  Segment and design of a row by a multiply: seg_magic = ceil(2^32 / B) gives
+// floor(row / B) == (row * seg_magic) >> 32 for row, B < 2^16 (the host bounds n_seg * B by 65535).
+struct TimeComposeArgs {
+    ComposeArgs c;
+    float* cond_buf;                        // [n_seg * B, Lc, F]
+    const unsigned long long* seeds;        // device [n_seg]
+    int64_t Bseg; unsigned long long seg_magic; int n_seg;
+};
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+
+__global__ __launch_bounds__(256) void timecompose_update_kernel(const TimeComposeArgs u) {
+    const ComposeArgs& a = u.c;
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const int t = step_scalar(a.t_ptr, a.t_imm);
+    const int sidx = *a.step_idx;
+    if (i == 0) compose_advance(a, t);
+    const int64_t per = (int64_t)a.Ltot * a.F;
+    if (i >= a.B * per) return;
+    const int64_t row = i / per;
+    const int e = (int)(i - row * per);
+    const int lx = e / a.F, f = e - lx * a.F;
+    const int l = lx + a.cond_steps, Lfull = a.Ltot + a.cond_steps;
+    const int k = (int)(((unsigned long long)row * u.seg_magic) >> 32);
+    const int64_t b = row - (int64_t)k * u.Bseg;
+    const float4 xq = ld4(a.x + i);
+    const float xv[4] = {xq.x, xq.y, xq.z, xq.w};
+    float o[4];
+    if (a.mode == 0) {                       // plain: pair_eps is the model output on cat(cond, x)
+        const float4 q = ld4(a.pair_eps + ((size_t)row * Lfull + l) * a.F + f);
+        o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
+    } else {                                 // mode 5 (gradient() :1900-1922), as compose_update_element: senders in body order
+        const int body = f >> 2;
+        const int P = a.nb * (a.nb - 1) / 2;
+        float s[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int ob = 0; ob < a.nb; ++ob) {
+            if (ob == body) continue;
+            const int ii = min(body, ob), jj = max(body, ob);
+            const int64_t prow = (int64_t)pair_index(ii, jj, a.nb) * a.B + row;
+            const float4 q = ld4(a.pair_eps + (prow * a.T + l) * 8 + (body == ii ? 0 : 4));
+            s[0] += q.x; s[1] += q.y; s[2] += q.z; s[3] += q.w;
+        }
+        const float4 q = ld4(a.single_eps + (((int64_t)body * a.B + row) * a.T + l) * 4);
+        const float un[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = s[j] - a.uncond_coef * un[j];
+    }
+    const float ra = a.sqrt_recip[t], rb = a.sqrt_recipm1[t];
+    const int tn = a.ddim_tnext[sidx];
+    const float san = a.ddim_tab[4 * sidx], cc = a.ddim_tab[4 * sidx + 1], sg = a.ddim_tab[4 * sidx + 2];
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (tn >= 0) {
+        if (a.noise) { const float4 q = ld4(a.noise + (size_t)sidx * a.noise_t_stride + i); z[0] = q.x; z[1] = q.y; z[2] = q.z; z[3] = q.w; }
+        else if (sg != 0.f) {
+            const int64_t dsoff = a.dyn ? (int64_t)a.dyn[1] : a.sample_off;
+            counter_normal4((uint64_t)u.seeds[k], (uint64_t)(dsoff + b), (uint32_t)t, (uint32_t)e >> 2, z);
+        }
+    }
+    float x0[4], v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float p;
+        if (a.objective == 0) p = __fsub_rn(__fmul_rn(ra, xv[j]), __fmul_rn(rb, o[j]));
+        else if (a.objective == 1) p = o[j];
+        else p = __fsub_rn(__fmul_rn(a.sqrt_ac[t], xv[j]), __fmul_rn(a.sqrt_1mac[t], o[j]));
+        const float eps = (a.objective == 0) ? o[j] : (ra * xv[j] - p) / rb;
+        if (a.clip) p = clamp_pm1(p);
+        x0[j] = p;
+        // x_{next} = x0 * sqrt(alpha_next) + c * eps + sigma * z (:1844-1846); the last step returns x0 (:1840-1842)
+        v[j] = tn >= 0 ? __fadd_rn(__fadd_rn(__fmul_rn(p, san), __fmul_rn(cc, eps)), __fmul_rn(sg, z[j])) : p;
+    }
+    const float4 vq = make_float4(v[0], v[1], v[2], v[3]);
+    if (a.x0_out) *reinterpret_cast<float4*>(a.x0_out + i) = make_float4(x0[0], x0[1], x0[2], x0[3]);
+    *reinterpret_cast<float4*>(a.x_out + i) = vq;
+    const int lc = lx - (a.Ltot - a.cond_steps);
+    if (lc >= 0 && k + 1 < u.n_seg) *reinterpret_cast<float4*>(u.cond_buf + ((size_t)(row + u.Bseg) * a.cond_steps + lc) * a.F + f) = vq;
+}
+
+__global__ __launch_bounds__(256) void timecompose_init_kernel(float* __restrict__ x, float* __restrict__ cond_buf, const float* __restrict__ cond,
+                                                               const float* __restrict__ init_tape, const unsigned long long* __restrict__ seeds,
+                                                               int64_t Bseg, unsigned long long seg_magic, int n_seg, int R, int F, int Lc,
+                                                               int64_t off, uint32_t tag) {
+    const int64_t per = (int64_t)R * F;
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= (int64_t)n_seg * Bseg * per) return;
+    if (i < Bseg * Lc * F) *reinterpret_cast<float4*>(cond_buf + i) = ld4(cond + i);      // (rows 0 .. B: no hand-over writes them)
+    const int64_t row = i / per;
+    const int e = (int)(i - row * per);
+    const int lx = e / F, f = e - lx * F;
+    const int k = (int)(((unsigned long long)row * seg_magic) >> 32);
+    const int64_t b = row - (int64_t)k * Bseg;
+    float4 z;
+    if (init_tape) {
+        z = ld4(init_tape + i);
+    } else {       // element by element through counter_normal: bit-identical to fill_normal_kernel's x_T under seeds[k]
+        const uint64_t sd = (uint64_t)seeds[k], s = (uint64_t)(off + b);
+        z.x = counter_normal(sd, s, tag, (uint32_t)e);
+        z.y = counter_normal(sd, s, tag, (uint32_t)(e + 1));
+        z.z = counter_normal(sd, s, tag, (uint32_t)(e + 2));
+        z.w = counter_normal(sd, s, tag, (uint32_t)(e + 3));
+    }
+    *reinterpret_cast<float4*>(x + i) = z;
+    const int lc = lx - (R - Lc);
+    if (lc >= 0 && k + 1 < n_seg) *reinterpret_cast<float4*>(cond_buf + ((size_t)(row + Bseg) * Lc + lc) * F + f) = z;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Replacement conditioning of the 1-D chains (cindm_ddpm1d_set_known1d): one more node of the captured step, after the
 // step's update in whichever of its three forms (fused into ups_last_kernel, compose_update_kernel, guided), after the guided DDPM
 // step's staging copy and after the counter launch where the loop has one.  The known region (mask) of the state x [B, Ltot, F] is

@@ -16,6 +16,9 @@ What runs where
   * autoregressive time composition (``autoregress_time_compose_sample`` :2240-2327): the whole rollout -- every segment's
     DDIM chain and the hand-over of its tail to the next segment -- is ONE library call (``cindm_ddpm1d_sample_autoregress``,
     the DDIM step's captured graph replayed for every segment).
+  * parallel time composition (``composing_time_sample`` :1807-1854): all segments side by side as ONE DDIM chain on
+    (n_composed + 1) * B rows (``cindm_ddpm1d_sample_timecompose``); the update of every step also hands each segment's noisy tail
+    over to the next segment's condition.
   * the Langevin (ULA) phase of ``sample_compose_multibodies`` for N > 401 (:2002-2022, ``sample_step_ULA`` :2048-2073): ONE library
     call for the whole phase (``cindm_ddpm1d_sample_ula``: one captured Langevin iteration replayed (N - 401) * L times, timestep and
     inner index advancing on the device), then the DDPM loop above from t = 400 on the drifted conditioning rows.
@@ -31,7 +34,7 @@ from torch import nn
 from . import _ffi
 from .diffusion_base import DiffusionHandle
 from .objectives import PointObjective, WaypointObjective
-from .record import DeviceRecorder, LoopRecorder
+from .record import DeviceRecorder, LoopRecorder, record_schedule, stream_mask
 from .schedule import make_schedule, ula_schedule
 
 ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"])
@@ -100,6 +103,29 @@ def autoregress_segments(conditioned_steps, rollout_steps, n_composed, is_single
         raise ValueError(f"single-step prediction: ceil(prediction_steps / conditioned_steps) * rollout_steps = {K} * {R} != prediction_steps "
                          f"{P}: the reference's last slice assignment into its [B, {P}, F] output fails on shape")
     return K
+
+
+def time_compose_segments(conditioned_steps, image_size, n_composed):
+    """Number of segments of ``composing_time_sample`` (:1815): n_composed + 1.  Raises for the cases where the reference fails
+    or returns nothing."""
+    Lc, R = int(conditioned_steps), int(image_size)
+    if Lc == 0:
+        raise NotImplementedError("composing_time_sample with conditioned_steps == 0: the reference hands img_infered[:, -0:] (the whole "
+                                  "state) over as the next condition and its slice assignment fails on shape")
+    if int(n_composed) < 1:
+        raise ValueError(f"n_composed must be >= 1, got {n_composed}: the reference returns an empty second tensor")
+    if R < Lc:
+        raise ValueError(f"composing_time_sample with image_size {R} < conditioned_steps {Lc}: the next segment's condition "
+                         "img_infered[:, -conditioned_steps:] is shorter than the model's horizon needs")
+    return int(n_composed) + 1
+
+
+def time_compose_assemble(x, n_seg):
+    """What ``composing_time_sample`` returns (:1848-1854) from the final state x [n_seg * B, R, F], segment-major: segment 0
+    [B, R, F] and the last min(20, R) rows (the reference's literal ``-20:``) of segments 1 .. n_seg - 1, in segment order along
+    the row axis: [B, (n_seg - 1) * min(20, R), F]."""
+    B = x.shape[0] // n_seg
+    return x[:B].clone(), torch.cat([x[k * B:(k + 1) * B, -20:] for k in range(1, n_seg)], dim=1)
 
 
 class GaussianDiffusion1D(DiffusionHandle, nn.Module):
@@ -1105,3 +1131,73 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
                     tarr, _ffi.ptr(carr), sarr, _ffi.ptr(init), _ffi.ptr(step), sample_offset, B, _ffi.ptr(ws), ws.numel(),
                     _ffi.current_stream(device), int(use_graph)))
         return self._chain(img, desc, call, result=out)
+
+    # ------------------------------------------------------------------ parallel time composition
+    @torch.no_grad()
+    def composing_time_sample(self, shape, cond, clip_denoised=True, n_composed=2, *, noise=None, seed=None, sample_offset=0,
+                              use_graph=True, return_trajectory_every=None, trajectory=("x",)):
+        """:1807-1854 (the ``EBMs_compose`` method of inference/inference_1d_composing_time_steps.py, :171-178).  All
+        K = n_composed + 1 segments are denoised side by side by ONE unguided DDIM chain on K * B rows: at the top of every
+        step segment k + 1 takes the last conditioned_steps rows of segment k's current, still noisy state as its condition
+        (segment 0 keeps ``cond``); prediction and update per step are ``ddim_sample(design_fn=None)``'s (:1838-1846;
+        clip_x_start = ``clip_denoised``, eta = ddim_sampling_eta).  S sequential steps where ``autoregress_time_compose_sample``
+        takes K * S -- and another algorithm: the later segments never see a finished condition.
+        ``shape`` = (B, image_size, F) with B = cond.shape[0].  Returns (img [B, R, F], img_infered [B, n_composed * min(20, R), F]):
+        segment 0, and the last min(20, R) rows of segments 1 .. K - 1 in order (the reference's literal ``-20:``).
+        Build-only keywords as ``autoregress_time_compose_sample``: ``seed`` (segment k draws under
+        ``autoregress_segment_seeds(seed, K)[k]``: its x_T and step noise are ``ddim_sample(seed=seed_k)``'s, so ``img`` IS
+        ``ddim_sample(shape, cond, seed=seed)``), ``sample_offset``, ``use_graph``, ``noise`` = NoiseTape(init [K,B,R,F], step
+        [S,K,B,R,F], indexed by the DDIM step).  ``return_trajectory_every`` / ``trajectory``: as ``ddim_sample``; the call then
+        returns ((img, img_infered), ChainRecord) with ``.x`` / ``.x0`` [n_records, K, B, R, F].  One library call
+        (``cindm_ddpm1d_sample_timecompose``): the update of every step also performs the hand-over."""
+        Lc, R = self.conditioned_steps, self.image_size
+        K = time_compose_segments(Lc, R, n_composed)
+        if cond is None or cond.dim() != 3 or cond.shape[1] != Lc:
+            raise ValueError(f"cond must be [B, conditioned_steps = {Lc}, F], got {None if cond is None else tuple(cond.shape)}")
+        if self.model_unconditioned is None and cond.shape[2] != self.channels:      # (with it: four bodies, checked by _desc_for)
+            raise ValueError(f"cond has {cond.shape[2]} features, the model's transition_dim is {self.channels}")
+        B, F = cond.shape[0], cond.shape[2]
+        if tuple(shape) != (B, R, F):
+            raise ValueError(f"shape must be (B, image_size, F) = {(B, R, F)} for this cond and model, got {tuple(shape)}")
+        if K * B > 65535:
+            raise ValueError(f"(n_composed + 1) * B = {K * B} rows: the library chain runs at most 65535")
+        rows = (K * B, R, F)
+        desc = self._desc_for(rows, None, clip=clip_denoised)
+        times, coefs = self.ddim_schedule()
+        S = len(times) - 1
+        init = step = None
+        if noise is not None:
+            init, step = noise.init, noise.step
+            if init is None or tuple(init.shape) != (K, B, R, F) or step is None or tuple(step.shape) != (S, K, B, R, F):
+                raise ValueError(f"noise: init must be [{K}, {B}, {R}, {F}] and step [{S}, {K}, {B}, {R}, {F}] (step first, then segment)")
+        if return_trajectory_every is not None:
+            record_schedule(S, return_trajectory_every)
+            stream_mask(trajectory)
+        device = self.betas.device
+        if device.type != "cuda":
+            raise _ffi.CindmError("GaussianDiffusion1D is on the CPU: move it to a ROCm device; there is no CPU execution path")
+        if seed is None and noise is None:
+            seed = self._draw_seed()
+        seed = 0 if seed is None else int(seed)
+        if noise is not None:
+            noise = noise.to(device)
+            init, step = noise.init, noise.step
+        cond_d = self._f32(cond, device)
+        x = torch.empty(rows, dtype=torch.float32, device=device)
+        cond_buf = torch.empty((K * B, Lc, F), dtype=torch.float32, device=device)
+        tarr = (C.c_int32 * (S + 1))(*times)
+        carr = coefs.contiguous()
+        sarr = (C.c_uint64 * K)(*autoregress_segment_seeds(seed, K))
+        rec = self._recorder(return_trajectory_every, trajectory, S, rows, device, times=times)
+
+        def call(h, un, ws):
+            self._arm(rec, h)
+            with torch.cuda.device(device):
+                _ffi.check(_ffi.lib().cindm_ddpm1d_sample_timecompose(
+                    h, self.model._h, un, C.byref(desc), _ffi.ptr(x), _ffi.ptr(cond_d), _ffi.ptr(cond_buf), K, S, tarr,
+                    _ffi.ptr(carr), sarr, _ffi.ptr(init), _ffi.ptr(step), sample_offset, B, _ffi.ptr(ws), ws.numel(),
+                    _ffi.current_stream(device), int(use_graph)))
+        out = time_compose_assemble(self._chain(x, desc, call), K)
+        if rec is None:
+            return out
+        return out, rec.collect(self._handle(), lambda r: r.reshape((r.shape[0], K, B, R, F)))

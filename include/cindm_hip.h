@@ -357,6 +357,41 @@ int  cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_
                                      int64_t sample_offset, int64_t B, void* ws, size_t ws_bytes,
                                      void* stream, int32_t use_graph);
 
+/* Parallel time composition (composing_time_sample, model/diffusion_1d.py:1807-1854; the "EBMs_compose" method of
+ * inference/inference_1d_composing_time_steps.py:171-178): ONE unguided DDIM chain on the n_seg * B rows of x [n_seg * B, R, F],
+ * segment-major (row k * B + b), R = the state length the descriptor implies, c->cond_steps = Lc >= 1, R >= Lc, n_seg >= 2,
+ * n_seg * B <= 65535; plain or multibody prediction, as cindm_ddpm1d_sample_autoregress.  Per DDIM step i,
+ * (t, t_next) = (times[i], times[i+1]):
+ *   cond_buf[(k+1) * B + b] = x[k * B + b, R - Lc : R]  for k = 0 .. n_seg - 2: the CURRENT, still noisy state (:1827-1829);
+ *   rows 0 .. B of cond_buf [n_seg * B, Lc, F] hold the caller's cond [B, Lc, F] and never change;
+ *   (eps, x_start) = model_predictions(x, cond_buf, t): one U-Net evaluation on all n_seg * B rows of cat(cond_buf, x), x_start
+ *   clamped when c->clip_denoised, eps the model's prediction, not re-derived (:1838);
+ *   x = x_start * sqrt(alpha_next) + c * eps + sigma * z_i, each product and sum rounded once; x = x_start when t_next < 0.
+ * So the chain takes n_steps sequential steps where the autoregressive rollout takes n_seg * n_steps, and segments k >= 1 see a
+ * noisy condition throughout: a different algorithm, not a faster form of the rollout.  On return x holds all n_seg final states
+ * (the caller assembles the reference's (img, img_infered) pair from it) and cond_buf the last hand-over.
+ * times / coefs as cindm_ddpm1d_sample_ddim.  seeds is a HOST array [n_seg]: segment k's x_T is the cindm_fill_normal draw
+ * (seeds[k], sample_offset + b, step_tag = timesteps) and the step noise of row (k, b) is keyed (seeds[k], sample_offset + b, t,
+ * element of [R, F]) -- the rule of cindm_ddpm1d_sample_autoregress, so a design's result depends neither on B nor on how a batch
+ * is partitioned, and segment 0 computes what cindm_ddpm1d_sample_ddim(seed = seeds[0]) computes on cond.  init_tape
+ * [n_seg, B, R, F] and noise_steps [n_steps, n_seg, B, R, F] (indexed by the STEP index, read whenever t_next >= 0), when given,
+ * replace those draws.  x, cond, cond_buf and the tapes must be 16-byte aligned (the update moves 16 bytes per lane).
+ * One launch per step does the update AND the hand-over (timecompose_update_kernel: a thread that writes a tail row of segment
+ * k < n_seg - 1 also writes it into cond_buf of segment k + 1; the step's U-Net input was gathered from cond_buf before that
+ * launch); one more launch before the first step draws x_T, hands over from it and copies cond.  A chain like the others: one
+ * captured step graph, replayed (use_graph = 0 streams the same launches); an exchange time-out re-runs the whole chain once on
+ * the exchange-free kernels; the range rule applies; cindm_ddpm1d_last_chain_info answers for it; cindm_ddpm1d_set_recorder is
+ * served with a record of [n_seg * B, R, F] per step i = 0 .. n_steps - 1 (both streams).  An armed known region or armed design
+ * tables are refused.  ws as cindm_ddpm1d_sample with cindm_ddpm1d_workspace_bytes(h, pair, uncond, c, n_seg * B): nothing is
+ * allocated (the segment seeds are kept in the workspace's second state buffer). */
+int  cindm_ddpm1d_sample_timecompose(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond,
+                                     const cindm_compose_desc* c, float* x, const float* cond,
+                                     float* cond_buf, int32_t n_seg, int32_t n_steps,
+                                     const int32_t* times, const float* coefs, const uint64_t* seeds,
+                                     const float* init_tape, const float* noise_steps,
+                                     int64_t sample_offset, int64_t B, void* ws, size_t ws_bytes,
+                                     void* stream, int32_t use_graph);
+
 /* Langevin (ULA) phase of sample_compose_multibodies (model/diffusion_1d.py:2002-2022 -> sample_step_ULA :2048-2073 on the
  * composed score of gradient() :1865-1926): for t = t_start, t_start-1, ..., t_end, L times
  *   eps = composed noise of gradient(x, t)       (CINDM_COMPOSE_MULTIBODY with c->uncond_coef; both U-Nets see timestep t)
