@@ -114,3 +114,31 @@ static bool max_abs_in_fp16_window(const Param& p) {
     for (float v : p.host) M = std::max(M, std::fabs(v));
     return !(M > 32768.0f || (M < 1.0f / 4096.0f && M > 0.f) || !(M == M));
 }
+
+// The synthetic calibration batch of the range rule (both U-Nets): `n` elements of a unit-variance bell (sum of four uniforms,
+// |v| < 3.5) drawn from `seed`, zero in the padding channels (element i is data when i % CP < C); fwd(t, x, eps, ws) runs one
+// forward per timestep in {0, T/2, T-1}.  *finite = false when a forward failed or an eps element is inf / nan.
+template <typename Fwd>
+static int calibrate_at_finalize(size_t n, int C, int CP, uint32_t seed, int T, size_t wsb, hipStream_t stream, Fwd fwd, bool* finite) {
+    std::vector<float> hx(n, 0.f), he(n);
+    uint32_t st = seed;
+    for (size_t i = 0; i < n; ++i) {
+        if ((int)(i % CP) >= C) continue;
+        float a = 0.f;
+        for (int k = 0; k < 4; ++k) { st = st * 1664525u + 1013904223u; a += (float)(st >> 8) * (1.0f / 16777216.0f) - 0.5f; }
+        hx[i] = a * 1.7320508f;
+    }
+    float *dx = nullptr, *de = nullptr; void* ws = nullptr;
+    HIPCHK(hipMalloc((void**)&dx, n * 4)); HIPCHK(hipMalloc((void**)&de, n * 4)); HIPCHK(hipMalloc(&ws, wsb));
+    HIPCHK(hipMemcpyAsync(dx, hx.data(), n * 4, hipMemcpyHostToDevice, stream));
+    *finite = true;
+    for (int t : {0, T / 2, T - 1}) {
+        if (fwd(t, dx, de, ws) != 0) { *finite = false; break; }
+        HIPCHK(hipMemcpyAsync(he.data(), de, n * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        for (float v : he) if (!std::isfinite(v)) { *finite = false; break; }
+        if (!*finite) break;
+    }
+    (void)hipFree(dx); (void)hipFree(de); (void)hipFree(ws);
+    return 0;
+}

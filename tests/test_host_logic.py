@@ -248,7 +248,7 @@ def test_no_allocation_outside_create_finalize_destroy():
     allowed = re.compile(r"(_create|_destroy|_finalize|finalize_pack|_phase_prof_enable)$")
     csrc = os.path.join(ROOT, "cindm_amd", "csrc")
     seen = 0
-    for fn in ("cindm_hip.hip", "unet2d_host.inc", "forceunet_host.inc", "ddpm2d_host.inc", "handle_core.inc", "chain_host.inc",
+    for fn in ("cindm_hip.hip", "unet1d_host.inc", "unet2d_host.inc", "forceunet_host.inc", "ddpm2d_host.inc", "handle_core.inc", "chain_host.inc",
                "ddpm1d_host.inc"):
         cur = None
         for i, line in enumerate(open(os.path.join(csrc, fn)).read().split("\n"), 1):
