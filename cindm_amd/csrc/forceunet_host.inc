@@ -135,23 +135,27 @@ extern "C" int cindm_forceunet_set_param(cindm_forceunet* h, const char* key, co
 
 // conv weight [Co][Ci][KS][KS] -> forward fragments Wp[tap][kc][ntq][lane][NB] and the backward-data ones (input <->
 // output channels swapped, taps flipped).  WeightStandardizedConv2d (:111-124) is folded here (biased variance, eps 1e-5).
+static std::vector<float> fu_ws_folded(const Param& w) {
+    const int Co = (int)w.shape[0];
+    std::vector<float> W(w.host);
+    const size_t per = w.numel / Co;
+    for (int o = 0; o < Co; ++o) {
+        double m = 0.0;
+        for (size_t i = 0; i < per; ++i) m += W[o * per + i];
+        m /= (double)per;
+        const float mf = (float)m;
+        double v = 0.0;
+        for (size_t i = 0; i < per; ++i) { const double dd = (double)W[o * per + i] - m; v += dd * dd; }
+        const float rs = 1.0f / sqrtf((float)(v / (double)per) + 1e-5f);
+        for (size_t i = 0; i < per; ++i) W[o * per + i] = (W[o * per + i] - mf) * rs;
+    }
+    return W;
+}
+
 static void fu_pack_conv(cindm_forceunet* h, BlobBuilder& bb, const std::string& prefix, bool ws) {
     const Param& w = h->params[h->index.at(prefix + ".weight")];
     const int Co = (int)w.shape[0], Ci = (int)w.shape[1], KS = (int)w.shape[2], T = KS * KS;
-    std::vector<float> W(w.host);
-    if (ws) {
-        const size_t per = (size_t)Ci * T;
-        for (int o = 0; o < Co; ++o) {
-            double m = 0.0;
-            for (size_t i = 0; i < per; ++i) m += W[o * per + i];
-            m /= (double)per;
-            const float mf = (float)m;
-            double v = 0.0;
-            for (size_t i = 0; i < per; ++i) { const double dd = (double)W[o * per + i] - m; v += dd * dd; }
-            const float rs = 1.0f / sqrtf((float)(v / (double)per) + 1e-5f);
-            for (size_t i = 0; i < per; ++i) W[o * per + i] = (W[o * per + i] - mf) * rs;
-        }
-    }
+    std::vector<float> W = ws ? fu_ws_folded(w) : w.host;
     const bool unshuf = KS == 1 && prefix.size() > 4 && prefix.compare(prefix.size() - 4, 4, ".3.1") == 0;
     if (unshuf) {
         // the 1x1 behind 'b c (h p1) (w p2) -> b (c p1 p2) h w': input channel c*4 + p moves to p*C + c, so that the kernels
@@ -340,12 +344,22 @@ extern "C" int cindm_forceunet_finalize(cindm_forceunet* h, void* stream) {
     h->opt["range_fallback"] = 0;
     if (h->fwd_h3 && h->O("auto_range")) {
         // weight window of the range rule (as cindm_unet1d_finalize): the convolutions that are NOT weight-standardised feed
-        // the un-normalised residual stream, whose scale the split-fp16 3x3 convolutions then see as their input.  A tiny
-        // weight (stream below fp16's normal range: the hi plane would flush, silently) or a huge one switches the forward
-        // convolutions to the exact fp32 kernel; the input-gradient ones rescale by the gradient's maximum and need no rule.
+        // the un-normalised residual stream, whose scale the split-fp16 3x3 convolutions then see as their input.  fp16
+        // subnormals survive pack, staging and MFMA (measured at max|w| = 2^-12, where a quarter of the hi plane and most of
+        // the lo plane are subnormal: tests/test_gpu_f64_range.py, DESIGN 4.8), so nothing flushes inside the window; below
+        // it hi and lo run out of subnormal bits together -- a silent loss -- and above it hi overflows.  A weight outside
+        // switches the forward convolutions to the exact fp32 kernel.  The input-gradient ones rescale the gradient by its
+        // maximum and reuse the weight planes, which the window already covers: held to the same budget at both edges there.
         for (const auto& p : h->params) {
             if (p.shape.size() != 4 || p.name.find(".proj.") != std::string::npos) continue;
-            if (!max_abs_in_fp16_window(p)) { h->fwd_h3 = false; h->opt["range_fallback"] = 1; break; }
+            if (!max_abs_in_fp16_window(p.host)) { h->fwd_h3 = false; h->opt["range_fallback"] = 1; break; }
+        }
+        // The weight-standardised convolutions are the ones that RUN on the split-fp16 kernels, on the planes of the FOLDED
+        // weights.  Those are O(1) only while a filter's variance is well above the fold's 1e-5: tiny .proj. weights fold to
+        // tiny tensors (x 2^-24: max 5e-7 .. 9e-7, planes 3e-5 off), and the same window applies to them.
+        for (const auto& p : h->params) {
+            if (!h->fwd_h3 || p.shape.size() != 4 || p.name.find(".proj.") == std::string::npos) continue;
+            if (!max_abs_in_fp16_window(fu_ws_folded(p))) { h->fwd_h3 = false; h->opt["range_fallback"] = 1; break; }
         }
     }
     if (h->fwd_h3 && h->O("auto_range")) {

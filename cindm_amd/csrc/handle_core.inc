@@ -109,9 +109,9 @@ static int core_set_option(ModelCore* h, const char* key, int32_t value) {
 // The weight window of the range rule of the split-fp16 products (hi = fp16(w), lo = fp16((w - hi) * 2^11)): every element
 // of a weight tensor is represented to 2^-24 of the tensor's largest magnitude M as long as 2^-12 <= M <= 2^15 (below, hi
 // and lo fall into fp16's subnormals together; above, hi overflows).  An all-zero tensor is inside; nan is outside.
-static bool max_abs_in_fp16_window(const Param& p) {
+static bool max_abs_in_fp16_window(const std::vector<float>& w) {
     float M = 0.f;
-    for (float v : p.host) M = std::max(M, std::fabs(v));
+    for (float v : w) M = std::max(M, std::fabs(v));
     return !(M > 32768.0f || (M < 1.0f / 4096.0f && M > 0.f) || !(M == M));
 }
 

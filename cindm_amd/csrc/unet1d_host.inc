@@ -1639,7 +1639,7 @@ static int unet1d_finalize_pack(cindm_unet1d* h, void* stream_) {
     if (h->use_h3 && h->O("auto_range")) {
         for (const auto& p : h->params) {
             if (p.shape.size() < 2 || p.name.find("time_mlp") != std::string::npos) continue;      // time path: fp32 kernels at finalize
-            if (!max_abs_in_fp16_window(p)) { h->use_h3 = false; h->opt["range_fallback"] = 1; break; }
+            if (!max_abs_in_fp16_window(p.host)) { h->use_h3 = false; h->opt["range_fallback"] = 1; break; }
         }
     }
     h->packed.clear(); h->vec_off.clear(); h->tb_off.clear();

@@ -195,22 +195,28 @@ static const Param& P2(const cindm_unet2d* h, const std::string& k) { return h->
 // kind: CONV_3X3 / CONV_1X1_WIDE (every 1x1) / CONV_UP2 (3x3 over the x2 upsampled source) / CONV_UNSHUF (weight [Co][4C][1][1]) /
 // CONV_STEM7; ws: weight standardisation (WeightStandardizedConv2d :116-124, folded here once: biased variance over
 // (Ci, kh, kw), eps 1e-5); split: channels of the first of two concatenated sources.
+// WeightStandardizedConv2d folded into the weights (biased variance, eps 1e-5): what the kernels multiply by.  With
+// var << 1e-5 the result is (w - mean) / sqrt(1e-5), as small as the checkpoint's own weights: the range rule looks at it.
+static std::vector<float> ws_folded2(const Param& w) {
+    const int Co = (int)w.shape[0];
+    std::vector<float> wv(w.host);
+    const size_t per = w.numel / Co;
+    for (int o = 0; o < Co; ++o) {
+        float* p = wv.data() + (size_t)o * per;
+        double m = 0; for (size_t i = 0; i < per; ++i) m += p[i];
+        const float mean = (float)(m / per);
+        double v = 0; for (size_t i = 0; i < per; ++i) { const double dd = (double)p[i] - mean; v += dd * dd; }
+        const float var = (float)(v / per);
+        const float rs = 1.0f / sqrtf(var + 1e-5f);
+        for (size_t i = 0; i < per; ++i) p[i] = (p[i] - mean) * rs;
+    }
+    return wv;
+}
+
 static int pack_conv2d(cindm_unet2d* h, BlobBuilder& bb, const std::string& prefix, int kind, bool ws, int split) {
     const Param& w = P2(h, prefix + ".weight");
     const int Co = (int)w.shape[0], Ci = (int)w.shape[1], k = (int)w.shape[2];
-    std::vector<float> wv(w.host);
-    if (ws) {
-        const size_t per = (size_t)Ci * k * k;
-        for (int o = 0; o < Co; ++o) {
-            float* p = wv.data() + (size_t)o * per;
-            double m = 0; for (size_t i = 0; i < per; ++i) m += p[i];
-            const float mean = (float)(m / per);
-            double v = 0; for (size_t i = 0; i < per; ++i) { const double dd = (double)p[i] - mean; v += dd * dd; }
-            const float var = (float)(v / per);
-            const float rs = 1.0f / sqrtf(var + 1e-5f);
-            for (size_t i = 0; i < per; ++i) p[i] = (p[i] - mean) * rs;
-        }
-    }
+    const std::vector<float> wv = ws ? ws_folded2(w) : w.host;
     Packed2 pk; pk.kind = kind;
     if (kind == CONV_1X1_WIDE) {
         // [n-tile of 64][q = k-step / 4][thread = wave*64 + lane][4 k-steps]: the A fragment of conv1x1_wide_kernel,
@@ -952,13 +958,15 @@ static int unet2d_finalize_pack(cindm_unet2d* h, void* stream_) {
     }
     BlobBuilder bb;
     h->use_h3 = !h->O("mfma_f32") && !h->force_f32;
-    // range rule of the split-fp16 products, as in cindm_unet1d_finalize (weight-standardised convolutions are O(1)
-    // by construction and need no check)
+    // range rule of the split-fp16 products, as in cindm_unet1d_finalize.  The weight-standardised convolutions (.proj.) are
+    // checked as the kernels see them, folded: they are O(1) only while a filter's variance is well above the fold's 1e-5;
+    // a checkpoint of tiny .proj. weights folds to tiny tensors (x 2^-24: max 5e-7 .. 9e-7) whose planes lose 3e-5 of them.
     h->opt["range_fallback"] = h->force_f32 ? 2 : 0;
     if (h->use_h3 && h->O("auto_range")) {
         for (const auto& p : h->params) {
-            if (p.shape.size() != 4 || p.name.find(".proj.") != std::string::npos) continue;
-            if (!max_abs_in_fp16_window(p)) { h->use_h3 = false; h->opt["range_fallback"] = 1; break; }
+            if (p.shape.size() != 4) continue;
+            const bool ws = p.name.find(".proj.") != std::string::npos;
+            if (!(ws ? max_abs_in_fp16_window(ws_folded2(p)) : max_abs_in_fp16_window(p.host))) { h->use_h3 = false; h->opt["range_fallback"] = 1; break; }
         }
     }
     h->packed.clear(); h->lin.clear(); h->vec_off.clear(); h->tt_off.clear();
