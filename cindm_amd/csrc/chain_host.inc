@@ -1,7 +1,7 @@
 // The chain driver: what every sampling entry (cindm_ddpm1d_sample*, cindm_ddpm2d_sample*) does around its own step.
 // Textually included by cindm_hip.hip after the 1-D U-Net's host code and before ddpm1d_host.inc and the 2-D host files; each piece
 // exists once.
-//   RecSpec, DesignTables, cindm_ddpm1d, KeyBuilder   the schedule handle both sides run on, with what a chain call arms on it
+//   RecSpec, DesignTables, QuadTables, cindm_ddpm1d, KeyBuilder   the schedule handle both sides run on, with what a chain call arms on it
 //   chain_stream        which stream a chain runs on
 //   stream_steps        the eager loop
 //   graph_capture/_run  capture a step functor into an instantiated graph; launch it n times and synchronise
@@ -9,6 +9,7 @@
 //   upload_ddim_tables  schedule check + the DDIM loops' per-step device tables
 //   RecScope            the chain recorder: taken by every chain entry
 //   DesignTablesScope   the waypoint objective's tables: taken by every 1-D chain entry, run by the two guided ones
+//   QuadTablesScope     the quadratic objective's tables: taken by every chain entry, run by the two guided 1-D ones
 //   Known2DScope        the 2-D chains' known region: taken by every chain entry, run by the four 2-D ones
 //   Known1DScope        the 1-D chains' known region: taken by every chain entry, run by cindm_ddpm1d_sample / _sample_guided /
 //                       _sample_ddim / _sample_ddim_guided (bottom of this file)
@@ -28,6 +29,12 @@ struct RecSpec {
 struct DesignTables {
     const float* target = nullptr; const float* scale = nullptr; int target_per_design = 0, scale_per_design = 0;
     int rows = 0, n_bodies = 0; int64_t batch = 0;
+};
+
+// The quadratic objective's device tables as armed by the caller (cindm_ddpm1d_set_design_quadratic, below)
+struct QuadTables {
+    const float* S = nullptr; const float* h = nullptr; int S_per_design = 0, h_per_design = 0;
+    int rows = 0, features = 0; int64_t batch = 0;
 };
 
 // The known region of a 2-D chain as armed by the caller (cindm_ddpm1d_set_known2d, below: known .. cp) and as one chain runs it
@@ -63,6 +70,8 @@ struct cindm_ddpm1d {
     RecSpec rec_armed; const RecSpec* rec = nullptr; int rec_info[4] = {0, 0, 0, 0};
     // the design tables: what the next chain call will take, and the ones a running guided chain reads (null: none)
     DesignTables dzt_armed; const DesignTables* dzt = nullptr;
+    // the quadratic objective's tables, likewise
+    QuadTables qdt_armed; const QuadTables* qdt = nullptr;
     // the known region of the 2-D chains: what the next chain call will take, and the one a running 2-D chain holds (null: none)
     Known2D kn_armed; const Known2D* kn = nullptr;
     // the known region of the 1-D chains, likewise
@@ -283,6 +292,11 @@ static int dzt_refuse(const DesignTablesScope& ts) {
 
 static int dzt_begin(DesignTablesScope& ts, const cindm_design_desc* dz, int Ltot, int n_bodies, int64_t B) {
     const DesignTables& t = ts.t;
+    if (dz->mode == 5) {
+        REQUIRE(!ts.on(), "design tables (target, scale) are armed but the descriptor's mode is 5, which reads the quadratic tables of "
+                          "cindm_ddpm1d_set_design_quadratic; the tables were dropped");
+        return 0;
+    }
     if (dz->mode != 3 && dz->mode != 4) {
         REQUIRE(!ts.on(), "design tables are armed but the descriptor's mode is 1 / 2 (the point objective, which reads none); the tables were dropped");
         return 0;
@@ -314,6 +328,64 @@ extern "C" int cindm_ddpm1d_set_design_tables(cindm_ddpm1d* h, const float* targ
     DesignTables& t = h->dzt_armed;
     t.target = target; t.scale = scale; t.target_per_design = target_per_design ? 1 : 0; t.scale_per_design = scale_per_design ? 1 : 0;
     t.rows = rows; t.n_bodies = n_bodies; t.batch = batch;
+    return 0;
+}
+
+// ---- the quadratic objective's tables (DESIGN 4.5q) ------------------------------------------------------------------------------------
+// cindm_ddpm1d_set_design_quadratic arms the handle; the next chain entry -- 1-D or 2-D -- takes the tables with QuadTablesScope, so the
+// call consumes them however it ends, and either refuses them (qdt_refuse: every chain that is not guided) or checks them against its
+// descriptor and state (qdt_begin) and runs with them: run_step reads h->qdt for the whole call, the re-run included.
+struct QuadTablesScope {
+    cindm_ddpm1d* h; QuadTables t;
+    explicit QuadTablesScope(cindm_ddpm1d* h_) : h(h_) {
+        if (!h) return;
+        t = h->qdt_armed; h->qdt_armed = QuadTables();
+    }
+    ~QuadTablesScope() { if (h) h->qdt = nullptr; }
+    bool on() const { return t.S != nullptr; }
+};
+
+static int qdt_refuse(const QuadTablesScope& qs) {
+    REQUIRE(!qs.on(), "quadratic design tables: only the guided 1-D chains (cindm_ddpm1d_sample_guided / _sample_ddim_guided) read them; the tables were dropped");
+    return 0;
+}
+
+// x, x2: the state buffers the guided update reads a row of as float4 (x2: the guided DDIM chain's second buffer, or null)
+static int qdt_begin(QuadTablesScope& qs, const cindm_design_desc* dz, int Ltot, int n_bodies, int64_t B, const float* x, const float* x2) {
+    const QuadTables& t = qs.t;
+    if (dz->mode != 5) {
+        REQUIRE(!qs.on(), "quadratic design tables are armed but the descriptor's mode is 1 .. 4 (the point and waypoint objectives, which do "
+                          "not read them); the tables were dropped");
+        return 0;
+    }
+    REQUIRE(qs.on(), "design objective mode 5 reads S and h from tables: arm them with cindm_ddpm1d_set_design_quadratic before the chain call");
+    if (t.rows != Ltot)
+        return fail("quadratic design tables: " + std::to_string(t.rows) + " rows, the state has " + std::to_string(Ltot));
+    if (t.features != 4 * n_bodies)
+        return fail("quadratic design tables: " + std::to_string(t.features) + " features, the composition's state has " + std::to_string(4 * n_bodies));
+    if (t.batch != B)
+        return fail("quadratic design tables: made for a batch of " + std::to_string(t.batch) + ", the chain runs " + std::to_string(B));
+    REQUIRE((((uintptr_t)t.S | (uintptr_t)t.h) & 15) == 0, "quadratic design tables: S and h must be 16-byte aligned");
+    REQUIRE((((uintptr_t)x | (uintptr_t)x2) & 15) == 0, "quadratic design tables: the state x must be 16-byte aligned (the update reads its rows 16 bytes at a time)");
+    qs.h->qdt = &qs.t;
+    return 0;
+}
+
+static void qdt_key(KeyBuilder& K, const cindm_ddpm1d* h) {
+    if (h->qdt) K(h->qdt->S)(h->qdt->h)(h->qdt->S_per_design)(h->qdt->h_per_design);
+}
+
+extern "C" int cindm_ddpm1d_set_design_quadratic(cindm_ddpm1d* h, const float* S, int32_t S_per_design, const float* hvec,
+                                                 int32_t h_per_design, int32_t rows, int32_t features, int64_t batch) {
+    if (h) h->qdt_armed = QuadTables();      // (a refused call leaves the handle disarmed)
+    REQUIRE(h, "null handle");
+    if (!S && !hvec) return 0;
+    REQUIRE(S && hvec, "quadratic design tables: S and h come together (NULL, NULL disarms)");
+    REQUIRE(rows >= 1 && batch >= 1, "quadratic design tables: rows and batch must be >= 1");
+    REQUIRE(features >= 4 && features <= 32 && (features & 3) == 0, "quadratic design tables: features must be a multiple of 4 in 4 .. 32");
+    QuadTables& t = h->qdt_armed;
+    t.S = S; t.h = hvec; t.S_per_design = S_per_design ? 1 : 0; t.h_per_design = h_per_design ? 1 : 0;
+    t.rows = rows; t.features = features; t.batch = batch;
     return 0;
 }
 

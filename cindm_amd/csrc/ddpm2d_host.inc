@@ -312,6 +312,8 @@ extern "C" int cindm_ddpm2d_sample(cindm_ddpm1d* s, cindm_unet2d* u, float* x, i
     RecScope rs(s);
     Known2DScope ks(s);
     Known1DScope k1(s);
+    QuadTablesScope qs(s);
+    if (qdt_refuse(qs) != 0) return -1;
     if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
                           "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
@@ -331,6 +333,8 @@ extern "C" int cindm_ddpm2d_sample_ddim(cindm_ddpm1d* s, cindm_unet2d* u, float*
     RecScope rs(s);
     Known2DScope ks(s);
     Known1DScope k1(s);
+    QuadTablesScope qs(s);
+    if (qdt_refuse(qs) != 0) return -1;
     if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
                           "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
@@ -358,6 +362,8 @@ extern "C" int cindm_ddpm2d_sample_force(cindm_ddpm1d* s, cindm_unet2d* u, cindm
     RecScope rs(s);
     Known2DScope ks(s);
     Known1DScope k1(s);
+    QuadTablesScope qs(s);
+    if (qdt_refuse(qs) != 0) return -1;
     if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
                           "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
@@ -382,6 +388,8 @@ extern "C" int cindm_ddpm2d_sample_ddim_force(cindm_ddpm1d* s, cindm_unet2d* u, 
     RecScope rs(s);
     Known2DScope ks(s);
     Known1DScope k1(s);
+    QuadTablesScope qs(s);
+    if (qdt_refuse(qs) != 0) return -1;
     if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
                           "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);

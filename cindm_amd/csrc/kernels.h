@@ -2552,11 +2552,14 @@ struct ComposeArgs {
     // The waypoint objective (modes 3 / 4) reads a target per (design | all designs, row, body) and a non-negative scale per
     // (design | all designs, row, body) from device tables instead; their addresses share the storage of the point objective's
     // scalars, so the struct -- which sits by value in the kernarg of ups_last_kernel and its fused forms -- keeps its size.
-    int dz_mode;                 // 0 off; bits 0-2: 1 "L2", 2 "L2square" (point), 3 "L2", 4 "L2square" (tables); kDzTargetPerDesign, kDzScalePerDesign
+    // The quadratic objective (mode 5) reads S [B | 1, Ltot, F, F] and h [B | 1, Ltot, F] from device tables through the same two words
+    // and the same two per-design bits; its gradient is compiled into compose_update_quad_kernel only.
+    int dz_mode;                 // 0 off; bits 0-2: 1 "L2", 2 "L2square" (point), 3 "L2", 4 "L2square" (tables), 5 quadratic (tables); kDzTargetPerDesign, kDzScalePerDesign
     int dz_alpha;                // 1: scale the gradient by eta_t = beta_t / sqrt(alphas_cumprod_prev_t) (standard-alpha)
     union {
         struct { int dz_last_n; float dz_coef, dz_tx, dz_ty; };              // modes 1, 2
         struct { const float* dz_target; const float* dz_scale; };           // modes 3, 4: [B | 1, Ltot, nb, 2] and [B | 1, Ltot, nb]
+        struct { const float* dz_S; const float* dz_h; };                    // mode 5: [B | 1, Ltot, F, F] (kDzTargetPerDesign) and [B | 1, Ltot, F] (kDzScalePerDesign)
     };
     float dz_tc;
     int relax;                   // this launch is a relaxation iteration (:1365-1367): x <- a_t pred + b_t z' (guided DDIM: and the step state stays)
@@ -2580,7 +2583,8 @@ __device__ __forceinline__ void compose_advance(const ComposeArgs& a, int t) {
     if (a.ep_next0) a.ep_next0[0] = a.ep_cur0[0] + 1;
     if (a.ep_next1) a.ep_next1[0] = a.ep_cur1[0] + 1;
 }
-// the update of state element i = (b * Ltot + row) * F + f (compose_update_kernel's body)
+// the update of state element i = (b * Ltot + row) * F + f (compose_update_kernel's body; compose_update_body<true> is
+// compose_update_quad_kernel's: the same update with the quadratic objective's gradient in place of the position objectives')
 __device__ void compose_update_element(const ComposeArgs& a, int64_t i);
 __device__ __forceinline__ void counter_normal4(uint64_t seed, uint64_t sample, uint32_t step, uint32_t elem4, float (&z)[4]);
 // x_{t-1} of one element of a PLAIN single-model step from the model output o (compose_update_element's mode 0 followed
@@ -3538,7 +3542,9 @@ __global__ void compose_gather_kernel(const ComposeArgs a) {
 }
 
 // One thread per state element (b, l, f) of the FULL sequence (cond rows skipped on output).
-__device__ void compose_update_element(const ComposeArgs& a, int64_t i) {
+// kQuad: the guided branch evaluates the quadratic objective (dz_mode 5) on all four components of a body; false: every other mode.
+template <bool kQuad>
+__device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_t i) {
     const int Lfull = a.Ltot + a.cond_steps;
     const int t = step_scalar(a.t_ptr, a.t_imm);
     const int sidx = a.ddim_tab ? *a.step_idx : 0;
@@ -3636,8 +3642,25 @@ __device__ void compose_update_element(const ComposeArgs& a, int64_t i) {
         // too this is the guided DDIM loop: relaxation iterations as below, the last iteration is the DDIM update on (eps + g, x0).
         float g = 0.f;
         const int dzm = a.dz_mode & kDzModeMask;
+        if constexpr (kQuad) {
+            // quadratic objective: g = (sum_f' S[l, f, f'] x[b, l, f']) - h[l, f], from 0.f in ascending f', every product and sum rounded
+            // once, h subtracted last.  F % 4 == 0 and 16-byte aligned tables and states (qdt_begin): both rows are read as float4.
+            const int64_t bS = (a.dz_mode & kDzTargetPerDesign) ? b : 0, bh = (a.dz_mode & kDzScalePerDesign) ? b : 0;
+            const int64_t srow = (bS * a.Ltot + lx) * a.F + f;
+            const float4* sp = reinterpret_cast<const float4*>(a.dz_S + srow * a.F);
+            const float4* xp = reinterpret_cast<const float4*>(a.x + (i - f));
+            float acc = 0.f;
+            for (int k = 0; k < (a.F >> 2); ++k) {
+                const float4 sv = sp[k], xq = xp[k];
+                acc = __fadd_rn(acc, __fmul_rn(sv.x, xq.x)); acc = __fadd_rn(acc, __fmul_rn(sv.y, xq.y));
+                acc = __fadd_rn(acc, __fmul_rn(sv.z, xq.z)); acc = __fadd_rn(acc, __fmul_rn(sv.w, xq.w));
+            }
+            g = __fsub_rn(acc, a.dz_h[(bh * a.Ltot + lx) * a.F + f]);
+        }
         if (comp < 2) {
-            if (dzm >= 3) {
+            if constexpr (kQuad) {
+                // (the position objectives of modes 1 - 4 are not part of this instantiation; the time-consistency term below is)
+            } else if (dzm >= 3) {
                 // table objective: the point branch's expressions with the scale and the target read per (design | all, row, body)
                 const int64_t bs = (a.dz_mode & kDzScalePerDesign) ? b : 0, bt = (a.dz_mode & kDzTargetPerDesign) ? b : 0;
                 const float s = a.dz_scale[(bs * a.Ltot + lx) * a.nb + body];
@@ -3749,8 +3772,16 @@ __device__ void compose_update_element(const ComposeArgs& a, int64_t i) {
     }
 }
 
+__device__ void compose_update_element(const ComposeArgs& a, int64_t i) { compose_update_body<false>(a, i); }
+
 __global__ void compose_update_kernel(const ComposeArgs a) {
     compose_update_element(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// the guided update with the quadratic objective (dz_mode 5): an instantiation of its own, so that compose_update_kernel is the code
+// it was (DESIGN 4.5q has both kernels' resource usage)
+__global__ void compose_update_quad_kernel(const ComposeArgs a) {
+    compose_update_body<true>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------

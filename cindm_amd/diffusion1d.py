@@ -9,8 +9,8 @@ What runs where
   * ``design_fn`` guidance is a user Python callable: its gradient is taken by PyTorch autograd
     between two library calls per step, exactly where the reference takes it.
   * DDIM (``sampling_timesteps < timesteps``, ``ddim_sample`` :1724-1804): unguided = ONE library call
-    (``cindm_ddpm1d_sample_ddim``, same captured-step replay with per-step coefficient tables); guided by a ``PointObjective``
-    or a ``WaypointObjective`` ("standard" / "standard-alpha" with ``-recurrence-N``) = ONE library call too (``cindm_ddpm1d_sample_ddim_guided``: relaxation
+    (``cindm_ddpm1d_sample_ddim``, same captured-step replay with per-step coefficient tables); guided by a ``PointObjective``,
+    a ``WaypointObjective`` or a ``QuadraticObjective`` ("standard" / "standard-alpha" with ``-recurrence-N``) = ONE library call too (``cindm_ddpm1d_sample_ddim_guided``: relaxation
     iterations and the DDIM update of (eps + grad, x_start) inside the captured step, state and step state ping-ponged); guided by
     any other callable or guidance (recurrence guidance) = library predictions + the user's gradient per step.
   * autoregressive time composition (``autoregress_time_compose_sample`` :2240-2327): the whole rollout -- every segment's
@@ -33,7 +33,7 @@ from torch import nn
 
 from . import _ffi
 from .diffusion_base import DiffusionHandle
-from .objectives import PointObjective, WaypointObjective
+from .objectives import PointObjective, QuadraticObjective, WaypointObjective
 from .record import DeviceRecorder, LoopRecorder, record_schedule, stream_mask
 from .schedule import make_schedule, ula_schedule
 
@@ -274,16 +274,17 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
 
     @staticmethod
     def _arm_tables(obj, h, img):
-        """A WaypointObjective's tables, armed like the recorder: the guided chain call consumes them, so every issue arms again."""
+        """A WaypointObjective's or QuadraticObjective's tables, armed like the recorder: the guided chain call consumes them, so every
+        issue arms again."""
         if obj is not None:
             obj.arm(h, img.shape[0], img.device)
 
     @staticmethod
     def _builtin(design_fn, design_guidance, B, L, n_bodies):
         """(descriptor, tables) when ``design_fn`` under ``design_guidance`` runs inside the captured step -- a PointObjective whose
-        last_n_step fits the state, or a WaypointObjective -- else (None, None).  A WaypointObjective whose tables do not fit the
-        state [B, L, 4 * n_bodies] is a ValueError on every route, before any device work."""
-        if isinstance(design_fn, WaypointObjective):
+        last_n_step fits the state, a WaypointObjective or a QuadraticObjective -- else (None, None).  A table objective whose tables
+        do not fit the state [B, L, 4 * n_bodies] is a ValueError on every route, before any device work."""
+        if isinstance(design_fn, (WaypointObjective, QuadraticObjective)):
             design_fn.check_state(B, L, n_bodies)
             dz = design_fn.descriptor(design_guidance)
             return dz, (design_fn if dz is not None else None)
@@ -649,7 +650,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
                          initial_state_overwrite, use_graph=True, rec=None, tables=None, karm=None):
         """Reverse steps t_start .. t_end guided by the built-in objective as one library call
         (cindm_ddpm1d_sample_guided); ``noise`` rows (step / recur / cond) are indexed by t.  ``tables``: the WaypointObjective
-        whose descriptor ``dz`` is (modes 3 / 4): every issue of the call arms its tables."""
+        or QuadraticObjective whose descriptor ``dz`` is (modes 3 / 4, 5): every issue of the call arms its tables."""
         device, B = img.device, img.shape[0]
         cond_d = self._f32(cond, device) if (cond is not None and self.conditioned_steps != 0) else None
         inp = self._f32(inpaint_cond, device)
@@ -967,7 +968,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         Without ``design_fn`` the whole loop is one library call (``cindm_ddpm1d_sample_ddim``); as in the reference the
         prediction then ignores the compose keywords (:1755).  With ``design_fn`` (recurrence guidance only -- the
         reference's non-recurrence branch does not return a noise prediction, :1283) the prediction honours them.  A
-        ``PointObjective`` (last_n_step <= L) or ``WaypointObjective`` under "standard" / "standard-alpha" ``-recurrence-N`` (N >= 1) runs as one library
+        ``PointObjective`` (last_n_step <= L), ``WaypointObjective`` or ``QuadraticObjective`` under "standard" / "standard-alpha" ``-recurrence-N`` (N >= 1) runs as one library
         chain (``cindm_ddpm1d_sample_ddim_guided``; counter-based draws keyed by (seed, sample_offset + b, t, element) when there
         is no tape); any other callable or guidance: each step is ``recurrence`` library predictions + the user's autograd
         gradient, and the DDIM update of the tiny state runs in torch.

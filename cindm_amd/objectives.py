@@ -13,7 +13,14 @@ library chain in the same way (``cindm_ddpm1d_sample_ddim_guided``).
 weight per (design | all designs, row, body).  It covers what the point objective cannot say -- a target per body, a waypoint at an
 intermediate row, a sweep of targets and coefficients over the designs of one batch (the reference script loops over such a sweep
 call by call, :283-315) -- and takes the same two library chains: the update kernel reads the two tables from device memory
-(``cindm_ddpm1d_set_design_tables``, descriptor modes 3 / 4)."""
+(``cindm_ddpm1d_set_design_tables``, descriptor modes 3 / 4).
+
+``QuadraticObjective`` is the table form of everything that is linear-quadratic in the features of one row: a symmetric ``S`` and a
+vector ``h`` per (design | all designs, row), value ``1/2 x^T S x - h^T x`` summed over rows and designs.  A velocity at the end
+("arrive and stop"), a relation between bodies ("0 and 1 meet", "keep 2 and 3 apart" with a negative weight), the centre of mass or the
+total momentum at a row and any weighted least-squares mix of these are such tables (``from_residuals`` builds them from residuals
+``a^T x - r``).  Its gradient acts on all four components of a body -- the first built-in objective whose does -- and takes the same
+two library chains (``cindm_ddpm1d_set_design_quadratic``, descriptor mode 5: the guided update compiled with this gradient)."""
 import copy
 
 import torch
@@ -234,3 +241,177 @@ class WaypointObjective:
         batch = B if self.per_design is None else self.per_design
         _ffi.check(_ffi.lib().cindm_ddpm1d_set_design_tables(handle, _ffi.ptr(target), int(target.dim() == 4), _ffi.ptr(scale),
                                                             int(scale.dim() == 3), self.rows, self.n_bodies, batch))
+
+
+class QuadraticObjective:
+    """``S`` [L, F, F] or [B, L, F, F]: a symmetric matrix per row (exactly: S[.., f, g] == S[.., g, f]); ``h`` [L, F] or [B, L, F].
+    F = 4 * n_bodies, a multiple of 4 up to 32.  The value for pos [B, L, F] is
+
+        sum_b sum_l ( 1/2 pos[b, l]^T S[b | 0, l] pos[b, l] - h[b | 0, l]^T pos[b, l] )  + the time-consistency term of PointObjective
+
+    and its gradient at (b, l, f) is (sum_f' S[l, f, f'] pos[b, l, f']) - h[l, f] on every feature, velocities included (+ the
+    time-consistency term on the position features).  S need not be positive: a negative weight pushes away."""
+
+    def __init__(self, S, h, *, time_consistency_coef=0.0):
+        S = torch.as_tensor(S).detach().to("cpu", torch.float32).contiguous()
+        h = torch.as_tensor(h).detach().to("cpu", torch.float32).contiguous()
+        if S.dim() not in (3, 4) or S.shape[-1] != S.shape[-2]:
+            raise ValueError(f"S must be [L, F, F] or [B, L, F, F], not {tuple(S.shape)}")
+        if h.dim() not in (2, 3):
+            raise ValueError(f"h must be [L, F] or [B, L, F], not {tuple(h.shape)}")
+        F = S.shape[-1]
+        if F < 4 or F % 4 != 0 or F > 32:
+            raise ValueError(f"F = {F}: the features of a row are 4 per body, a multiple of 4 in 4 .. 32")
+        if tuple(S.shape[-3:-1]) != tuple(h.shape[-2:]) or 0 in S.shape or 0 in h.shape:
+            raise ValueError(f"S {tuple(S.shape)} and h {tuple(h.shape)} disagree on (L, F)")
+        if S.dim() == 4 and h.dim() == 3 and S.shape[0] != h.shape[0]:
+            raise ValueError(f"S is for {S.shape[0]} designs, h for {h.shape[0]}")
+        if not bool(torch.isfinite(S).all()) or not bool(torch.isfinite(h).all()):
+            raise ValueError("S and h must be finite")
+        if not torch.equal(S, S.transpose(-1, -2)):
+            raise ValueError("S must be symmetric, exactly (from_residuals builds such tables; or pass (S + S^T) / 2)")
+        self.S, self.h = S, h
+        self.time_consistency_coef = float(time_consistency_coef)
+        self._dev = {}
+
+    @classmethod
+    def from_residuals(cls, rows, A, r, weight, L, F, *, time_consistency_coef=0.0):
+        """The least-squares form: residual m is ``A[m]^T pos[:, rows[m]] - r[m]`` with weight ``weight[m]`` (any sign), and the value
+        is 1/2 sum_m weight[m] residual_m^2 up to its constant 1/2 sum_m weight[m] r[m]^2.  ``rows`` [M] ints in 0 .. L-1; ``A`` [M, F],
+        ``r`` [M], ``weight`` [M], each optionally with a leading designs axis B (then the tables it enters are per design).
+        S_l = sum w a a^T and h_l = sum w r a are accumulated in float64 and cast to fp32 once: S is exactly symmetric."""
+        L, F = int(L), int(F)
+        rows = torch.as_tensor(rows, dtype=torch.int64).reshape(-1)
+        M = rows.numel()
+        A, r, w = (torch.as_tensor(v).detach().to("cpu", torch.float64) for v in (A, r, weight))
+        if M and (int(rows.min()) < 0 or int(rows.max()) >= L):
+            raise ValueError(f"rows outside 0 .. L - 1 = {L - 1}")
+        if A.dim() not in (2, 3) or tuple(A.shape[-2:]) != (M, F):
+            raise ValueError(f"A must be [M, F] or [B, M, F] with M = {M}, F = {F}, not {tuple(A.shape)}")
+        for name, v in (("r", r), ("weight", w)):
+            if v.dim() not in (1, 2) or v.shape[-1] != M:
+                raise ValueError(f"{name} must be [M] or [B, M] with M = {M}, not {tuple(v.shape)}")
+        nB = {v.shape[0] for v, d in ((A, 3), (r, 2), (w, 2)) if v.dim() == d}
+        if len(nB) > 1:
+            raise ValueError(f"A, r and weight disagree on the number of designs: {sorted(nB)}")
+        B = nB.pop() if nB else None
+        lead = lambda *vs: any(v.dim() == d for v, d in vs)
+        # (a a^T first: its (f, g) and (g, f) entries are the same product, and both are scaled and summed in the same order)
+        wa2 = w[..., None, None] * (A[..., :, None] * A[..., None, :])          # [B |, M, F, F]
+        wra = (w * r)[..., None] * A                                            # [B |, M, F]
+        if lead((A, 3), (w, 2)):
+            S = torch.zeros((B, L, F, F), dtype=torch.float64).index_add_(1, rows, wa2.expand(B, M, F, F))
+        else:
+            S = torch.zeros((L, F, F), dtype=torch.float64).index_add_(0, rows, wa2)
+        if B is not None:
+            hh = torch.zeros((B, L, F), dtype=torch.float64).index_add_(1, rows, wra.expand(B, M, F))
+        else:
+            hh = torch.zeros((L, F), dtype=torch.float64).index_add_(0, rows, wra)
+        return cls(S.to(torch.float32), hh.to(torch.float32), time_consistency_coef=time_consistency_coef)
+
+    # ------------------------------------------------------------------ shapes
+    @property
+    def rows(self):
+        return self.h.shape[-2]
+
+    @property
+    def features(self):
+        return self.h.shape[-1]
+
+    @property
+    def per_design(self):
+        """Designs the per-design tables are for, or None when both tables are shared by every design."""
+        if self.S.dim() == 4:
+            return self.S.shape[0]
+        return self.h.shape[0] if self.h.dim() == 3 else None
+
+    def check_state(self, B, L, n_bodies):
+        """ValueError unless the tables fit a state [B, L, 4 * n_bodies]."""
+        if self.rows != L:
+            raise ValueError(f"QuadraticObjective: tables of {self.rows} rows, the state has {L}")
+        if self.features != 4 * n_bodies:
+            raise ValueError(f"QuadraticObjective: tables of {self.features} features, the state has {4 * n_bodies}")
+        if self.per_design is not None and self.per_design != B:
+            raise ValueError(f"QuadraticObjective: per-design tables for {self.per_design} designs, the batch has {B} "
+                             "(shard(lo, hi) slices them for a part of the batch)")
+
+    def shard(self, lo, hi):
+        """The objective of designs lo .. hi-1: per-design tables sliced, tables shared by every design passed through."""
+        o = copy.copy(self)
+        o.S = self.S[lo:hi].contiguous() if self.S.dim() == 4 else self.S
+        o.h = self.h[lo:hi].contiguous() if self.h.dim() == 3 else self.h
+        o._dev = {}
+        return o
+
+    def tables(self, device):
+        """(S, h): the two contiguous fp32 tensors on ``device`` (cached per device) the kernel reads."""
+        device = torch.device(device)
+        if device not in self._dev:
+            self._dev[device] = (self.S.to(device).contiguous(), self.h.to(device).contiguous())
+        return self._dev[device]
+
+    # ------------------------------------------------------------------ value and gradient
+    def _time_consistency(self, pos, n_bodies):
+        idx = torch.cat([torch.arange(ii * 4, ii * 4 + 2) for ii in range(n_bodies)]).to(pos.device)
+        return (pos[:, 1:, idx] - pos[:, :-1, idx]).square().sum(-1).mean(-1).sum() * self.time_consistency_coef
+
+    def __call__(self, pos):
+        """pos: [B, L, F] -> scalar loss (summed over the batch)."""
+        B, L, F = pos.shape
+        self.check_state(B, L, F // 4)
+        S, h = self.S.to(pos), self.h.to(pos)
+        Sx = (S @ pos.unsqueeze(-1)).squeeze(-1)
+        total = 0.5 * (pos * Sx).sum() - (h * pos).sum()
+        if self.time_consistency_coef > 0 and L > 1:
+            total = total + self._time_consistency(pos, F // 4)
+        return total
+
+    def closed_form_grad(self, pos):
+        """The gradient of ``__call__`` as compose_update_quad_kernel evaluates it, operation for operation: per element (b, l, f)
+            acc = 0;  acc = acc + S[l, f, f'] * pos[b, l, f']  for f' = 0 .. F-1 (each product and each sum rounded once);  g = acc - h[l, f];
+            on position features  g = g + ((tc * 2) * lap) / (L - 1),  lap = (x_l - x_{l-1}) [l >= 1] - (x_{l+1} - x_l) [l + 1 < L]."""
+        B, L, F = pos.shape
+        self.check_state(B, L, F // 4)
+        S, h = self.S.to(pos), self.h.to(pos)
+        acc = torch.zeros_like(pos)
+        for fp in range(F):
+            acc = acc + S[..., :, fp] * pos[..., fp:fp + 1]
+        g = acc - h
+        if self.time_consistency_coef > 0 and L > 1:
+            x = pos.reshape(B, L, F // 4, 4)[..., :2]
+            lap = torch.zeros_like(x)
+            lap[:, 1:] += x[:, 1:] - x[:, :-1]
+            lap[:, :-1] -= x[:, 1:] - x[:, :-1]
+            g = g.reshape(B, L, F // 4, 4).clone()
+            g[..., :2] = g[..., :2] + self.time_consistency_coef * 2.0 * lap / float(L - 1)
+            g = g.reshape(B, L, F)
+        return g
+
+    def descriptor(self, design_guidance):
+        """cindm_design_desc (mode 5: the tables are armed per call) for this objective under ``design_guidance``, or None when that
+        guidance needs the generic (autograd) path."""
+        g = design_guidance
+        rec = 0
+        if "recurrence" in g:
+            try:
+                rec = int(g.split("-")[-1])
+            except ValueError:
+                return None
+            g = g[:g.index("-recurrence")]
+            if rec < 1:
+                return None
+        if g not in ("standard", "standard-alpha"):
+            return None
+        d = _ffi.DesignDesc()
+        d.mode = 5
+        d.alpha = int(g == "standard-alpha")
+        d.recurrence, d.time_consistency_coef = rec, self.time_consistency_coef
+        return d
+
+    def arm(self, handle, B, device):
+        """Arms the next guided chain call on ``handle`` (a cindm_ddpm1d) with this objective's tables, for a batch of ``B`` designs
+        (per-design tables declare their own extent: the chain call refuses another batch)."""
+        S, h = self.tables(device)
+        batch = B if self.per_design is None else self.per_design
+        _ffi.check(_ffi.lib().cindm_ddpm1d_set_design_quadratic(handle, _ffi.ptr(S), int(S.dim() == 4), _ffi.ptr(h), int(h.dim() == 3),
+                                                               self.rows, self.features, batch))

@@ -265,9 +265,12 @@ int  cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* unco
  * whose gradient with respect to the state is evaluated in closed form inside the update kernel.
  * Modes 3 / 4 are the waypoint objective, the same two norms read from device tables (cindm_ddpm1d_set_design_tables below):
  *   sum_b sum_l sum_j scale[b | 0, l, j] * || pos[b, l, 4j : 4j+2] - target[b | 0, l, j] ||_2     (mode 4: ||.||_2^2)
- *   (+ the time-consistency term); in these modes last_n_step, coef and pos_target are not read. */
+ *   (+ the time-consistency term); in these modes last_n_step, coef and pos_target are not read.
+ * Mode 5 is the quadratic objective, read from device tables as well (cindm_ddpm1d_set_design_quadratic below):
+ *   sum_b sum_l ( 1/2 x[b, l]^T S[b | 0, l] x[b, l] - h[b | 0, l]^T x[b, l] )     over all F = 4 * n_bodies features of a row
+ *   (+ the time-consistency term, on the position channels); last_n_step, coef and pos_target are not read either. */
 typedef struct {
-    int32_t mode;               /* 1 = "L2", 2 = "L2square"; 3 = table "L2", 4 = table "L2square" */
+    int32_t mode;               /* 1 = "L2", 2 = "L2square"; 3 = table "L2", 4 = table "L2square"; 5 = quadratic tables */
     int32_t alpha;              /* 0: "standard" (gradient as is), 1: "standard-alpha" (x eta_t)   :1243-1248 */
     int32_t recurrence;         /* 0: non-recurrence branch; N >= 1: "-recurrence-N"                :1284-1370 */
     int32_t last_n_step;
@@ -485,6 +488,30 @@ int  cindm_ddpm1d_recorder_info(const cindm_ddpm1d* h, int32_t info[4]);
 int  cindm_ddpm1d_set_design_tables(cindm_ddpm1d* h, const float* target, int32_t target_per_design,
                                     const float* scale, int32_t scale_per_design,
                                     int32_t rows, int32_t n_bodies, int64_t batch);
+
+/* The quadratic objective's tables (cindm_design_desc mode 5).  No reference counterpart.  Everything that is linear-quadratic in the
+ * features of one row -- a velocity target, a relation between bodies, the centre of mass or the total momentum at a row, any weighted
+ * least-squares mix of such terms -- is one (S, h) pair per row; the gradient acts on all four components of a body.
+ * S:    DEVICE floats [batch, rows, features, features] when S_per_design, else [rows, features, features] shared by every design;
+ *       every S[.., l] symmetric.  features = 4 * n_bodies, a multiple of 4 in 4 .. 32.
+ * hvec: DEVICE floats [batch, rows, features] when h_per_design, else [rows, features].
+ * The update kernel (compose_update_quad_kernel, the guided update compiled with this gradient) evaluates at element (b, l, f)
+ *   g = (sum_{f' = 0 .. features - 1} S[l, f, f'] * x[b, l, f']) - hvec[l, f]
+ * from 0.f in ascending f', every product and every sum rounded once to fp32 (no contraction), the subtraction last; then the
+ * time-consistency term on the position features, the standard-alpha factor and the rest of the guided update as for modes 1 - 4.
+ * cindm_ddpm1d_set_design_quadratic arms the NEXT chain call on this handle; that call consumes the tables whether it succeeds or
+ * fails, and (NULL, NULL) disarms.  cindm_ddpm1d_sample_guided / _sample_ddim_guided check rows == L_tot, features == 4 * c->n_bodies,
+ * batch == B and that S, hvec and the state x are 16-byte aligned (rows of S and of x are read 16 bytes at a time) before they launch
+ * or copy anything.  They refuse mode 5 with nothing armed, armed quadratic tables with modes 1 - 4, and the tables of
+ * cindm_ddpm1d_set_design_tables with mode 5; every other chain entry -- the unguided 1-D chains, the rollout, the time composition,
+ * the Langevin chain and all 2-D chains -- refuses armed quadratic tables and says why.  Lifetime as for the waypoint tables: they
+ * must stay alive and unchanged until the chain's work has finished -- with use_graph that is when the call returns (it
+ * synchronises; an exchange-free re-run inside the call reads them again); with use_graph = 0 the steps are only enqueued on the
+ * caller's stream, so the tables must outlive that stream's work (free or overwrite them after a synchronise, or in stream order).
+ * The two addresses and the two flags are operands of the captured update: a call with other tables captures its step again. */
+int  cindm_ddpm1d_set_design_quadratic(cindm_ddpm1d* h, const float* S, int32_t S_per_design,
+                                       const float* hvec, int32_t h_per_design,
+                                       int32_t rows, int32_t features, int64_t batch);
 
 /* Replacement conditioning of the 2-D chains: a known region of the state [B * nb, H * W, CP] is held on the forward-diffusion
  * trajectory of its clean values and returned exactly (known2d_kernel: one more node of the captured step, after the step's
