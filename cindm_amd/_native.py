@@ -50,7 +50,6 @@ class _NativeModel(nn.Module):
         self._range_checked = False      # the range guard has checked a result of the current pack (TemporalUnet1D)
         self._py_recovered = 0           # exchange-free re-runs driven from Python (_ExchangeRecovery)
         self._ws = None
-        self._ws_n = 0
         name = C.create_string_buffer(256)
         shape = (C.c_int64 * 4)()
         nd = C.c_int()
@@ -149,10 +148,10 @@ class _NativeModel(nn.Module):
         return self._option(key)
 
     def workspace(self, n, device):
-        """The cached workspace for ``n`` rows / images (reallocated when it is too small or on another device)."""
-        if self._ws is None or self._ws_n < n or self._ws.device != device:
-            self._ws = torch.empty(self._c("workspace_bytes")(self._h, n), dtype=torch.uint8, device=device)
-            self._ws_n = n
+        """The cached workspace for ``n`` rows / images (reallocated when it holds fewer bytes than ``n`` needs, or on another device)."""
+        need = self._c("workspace_bytes")(self._h, n)      # not monotonic in n: fewer rows can select a plan with larger staging
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
         return self._ws
 
 

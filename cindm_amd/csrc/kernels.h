@@ -3592,18 +3592,28 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
         mean = post_mean(x0);
     } else if (a.mode == 1 || a.mode == 2 || a.mode == 4) {
         // eps aggregated over senders then windows (model/diffusion_1d.py:994-999, :1457-1458)
+        // noise_sum sums each pair's pred_noise -- under pred_x0 / pred_v the one re-derived from that pair's own x_start (:1021, :1027,
+        // :1442-1443) -- and x_start is predict_start_from_noise of the sum whatever the objective (:1459).  One window of one pair has one
+        // term: there predict_start_from_noise undoes the re-derivation, x_start is the pair's own, and the step stays the plain one bit
+        // for bit (the identities outside == inside == plain, and the update ups_last_kernel fuses for every direct mode).
+        const bool per_pair_eps = a.mode == 4 && a.objective != 0 && !(a.W == 1 && a.nb == 2);
         float tot = 0.f;
         for (int kk = 0; kk < a.W; ++kk) {
             const int lw = l - kk * a.cs;
             if (lw < 0 || lw >= a.T) continue;
             float s = 0.f;
-            for (int o = 0; o < a.nb; ++o) if (o != body) s += pair_eps_at(kk, o, lw);
+            for (int o = 0; o < a.nb; ++o) {
+                if (o == body) continue;
+                float e = pair_eps_at(kk, o, lw);
+                if (per_pair_eps) e = (ra * xv - x0_of(e)) / rb;
+                s += e;
+            }
             if (a.mode == 1) s /= (float)(a.nb - 1);
             tot += s;
         }
         const float o = (a.mode == 1) ? tot / (float)cover : tot / ((float)cover / (float)a.W);
-        x0 = x0_of(o);
-        eps = (a.objective == 0) ? o : (ra * xv - x0) / rb;
+        x0 = per_pair_eps ? __fsub_rn(__fmul_rn(ra, xv), __fmul_rn(rb, o)) : x0_of(o);
+        eps = (a.objective == 0 || per_pair_eps) ? o : (ra * xv - x0) / rb;
         if (a.clip) x0 = clamp_pm1(x0);
         mean = post_mean(x0);
     } else if (a.mode == 3) {
@@ -3617,8 +3627,9 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
                 if (o == body) continue;
                 const float e = pair_eps_at(kk, o, lw);
                 float x0e = x0_of(e);
+                const float ee = (a.objective == 0) ? e : (ra * xv - x0e) / rb;      // the pair's pred_noise (:1021, :1027: from its unclamped x_start)
                 if (a.clip) x0e = clamp_pm1(x0e);
-                sm += post_mean(x0e); sx += x0e; se += e;
+                sm += post_mean(x0e); sx += x0e; se += ee;
             }
             tm += sm / (float)(a.nb - 1); tx += sx / (float)(a.nb - 1); te += se / (float)(a.nb - 1);
         }

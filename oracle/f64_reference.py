@@ -100,3 +100,245 @@ def row_err(a, ref):
 def e32(o32, ref):
     """The fp32 oracle's own error at one tap: the largest ``row_err`` over the rows compared."""
     return float(row_err(o32, ref).max())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Composition: from given U-Net outputs to (model_mean, x_start, pred_noise), in float64, with the magnitude of every output
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Written from the reference (model/diffusion_1d.py:959-1031 the inside branch and the three objectives, :1033-1044 p_mean_variance,
+# :1436-1463 the two outside aggregations, :1865-1982 gradient()) and from cindm_oracle's restatement of it: per (window, pair) tensor
+# indexing into a [W, B, L, sender, receiver, 4] tensor, as there, on float64.  It evaluates no network: the pair and single-body
+# outputs are arguments, so a comparison with the library on the library's own outputs measures gather + aggregation + update alone.
+
+COMPOSE_MODES = ("plain", "mean-inside", "sum-inside", "mean", "noise_sum", "multibody")       # the library's modes 0 .. 5, in order
+U24 = 2.0 ** -24            # one fp32 rounding, relative
+BOUND_SLACK = 4             # divisions counted as one rounding, the cast of E, second-order terms
+
+
+class ComposeCase:
+    """What a compose descriptor carries.  ``mode`` is a name of COMPOSE_MODES; ``objective`` a name; ``uncond_coef`` the weight of
+    the single-body prediction in ``multibody`` (1.4 with four bodies, 1 with three, :1900 / :1958)."""
+
+    def __init__(self, mode, n_bodies=2, n_windows=1, compose_start_step=0, window=24, cond_steps=0, objective="pred_noise", clip=True,
+                 uncond_coef=1.4):
+        assert mode in COMPOSE_MODES and objective in ("pred_noise", "pred_x0", "pred_v")
+        self.mode, self.n_bodies, self.n_windows, self.compose_start_step, self.window = mode, n_bodies, n_windows, compose_start_step, window
+        self.cond_steps, self.objective, self.clip, self.uncond_coef = cond_steps, objective, bool(clip), uncond_coef
+
+    @property
+    def full_len(self):
+        return self.window + (self.n_windows - 1) * self.compose_start_step
+
+    @property
+    def state_len(self):
+        return self.full_len - self.cond_steps
+
+    def replace(self, **kw):
+        c = ComposeCase.__new__(ComposeCase)
+        c.__dict__.update(self.__dict__)
+        c.__dict__.update(kw)
+        return c
+
+
+def compose_pairs(nb):
+    """(0,1),(0,2),..,(1,2),..: slot 0 (features 0-3 of a pair row) is the lower-numbered body, slot 1 (features 4-7) the other."""
+    return [(i, j) for i in range(nb) for j in range(i + 1, nb)]
+
+
+def _compose_full(desc, x, cond):
+    """cat(cond, x) (:956-957) and the refusals: what neither the reference nor the library evaluates."""
+    if desc.mode in ("mean", "noise_sum") and desc.cond_steps > 0:
+        # the reference hands the FULL-width cond to every 8-feature window (:1428-1430 -> :957): torch.cat raises for nb > 2, and
+        # for nb = 2 the 28-row input fails in the U-Net's skip connections.  The library refuses the descriptor.
+        raise ValueError("outside composition with conditioned_steps > 0 is not supported")
+    if desc.cond_steps > 0:
+        assert cond is not None and cond.shape[1] == desc.cond_steps
+        x = torch.cat([cond, x], dim=1)
+    assert x.shape[1] == desc.full_len and x.shape[2] == 4 * desc.n_bodies, (tuple(x.shape), desc.full_len, desc.n_bodies)
+    return x
+
+
+def compose_rows(desc, x, cond=None):
+    """Which rows the U-Nets see: -> (pair_in [W * P * B, window, 8], single_in [nb * B, window, 4] | None).  Pair rows are
+    window-major, then pair (``compose_pairs``), then batch; single-body rows (``multibody`` only) are body-major.  ``plain``: the
+    one row block cat(cond, x), whatever its width."""
+    full = _compose_full(desc, x, cond)
+    if desc.mode == "plain":
+        return full.contiguous(), None
+    rows = []
+    for kk in range(desc.n_windows):
+        lo = kk * desc.compose_start_step
+        for ii, jj in compose_pairs(desc.n_bodies):
+            rows.append(torch.cat([full[:, lo:lo + desc.window, 4 * ii:4 * ii + 4], full[:, lo:lo + desc.window, 4 * jj:4 * jj + 4]], dim=2))
+    single = None
+    if desc.mode == "multibody":
+        single = torch.cat([full[:, :, 4 * i:4 * i + 4] for i in range(desc.n_bodies)], dim=0).contiguous()
+    return torch.cat(rows, dim=0).contiguous(), single
+
+
+def compose_cover(desc):
+    """[full_len] int64: how many windows hold each row of cat(cond, x) (mask_aggr.sum(0), :975-978)."""
+    c = torch.zeros(desc.full_len, dtype=torch.long)
+    for kk in range(desc.n_windows):
+        c[kk * desc.compose_start_step: kk * desc.compose_start_step + desc.window] += 1
+    return c
+
+
+def compose_roundings(mode, nb, cover, objective):
+    """n_e: the fp32 roundings on the longest path to one element of (mean, x_start, pred_noise), counted on the reference's
+    formulas.  ``cover`` (windows that hold the element's row) may be a tensor.  With S = nb - 1 senders:
+
+      x0(out)     predict_start_from_noise / _from_v: two products and a sum, 3; pred_x0: the output itself, 0           -> nx
+      eps(out)    pred_noise: the output, 0; else predict_noise_from_start on that x0: product, difference, quotient      -> nx + 3
+      mean(x0)    q_posterior: two products and a sum                                                                     -> + 3
+      agg(n)      n roundings per scattered term, then S adds over senders, [/ (nb - 1)], ``cover`` adds over windows, one division;
+                  mean over senders and the sum forms' divisor mask.mean(0) = cover / W are one rounding each             -> n + S + cover + 2
+
+      plain        out is the model's                 out: 0
+      mean-inside  out = agg(0)                        out: S + cover + 2          sum-inside: the same count (divisor for mean)
+      multibody    out = sum_S - coef * single         out: S + 2  (S adds, a product, a difference; no window, no division)
+                   then  x_start: out + nx,  pred_noise: out (pred_noise) | out + nx + 3,  mean: out + nx + 3
+      noise_sum    eps = agg(eps(out) per pair), x_start = predict_start_from_noise(eps): + 3 whatever the objective (:1459), mean: + 3 more
+      mean         every output is agg() of the per-pair value: x_start agg(nx), pred_noise agg(0 | nx + 3), mean agg(nx + 3); the
+                   clamp sits inside the sum and is 1-Lipschitz: it adds no rounding.
+
+    A contracted FMA removes a rounding, never adds one."""
+    S = nb - 1
+    nx = 0 if objective == "pred_x0" else 3
+    ne = 0 if objective == "pred_noise" else nx + 3
+    agg = S + cover + 2
+    if mode == "mean":
+        return {"x_start": nx + agg, "pred_noise": ne + agg, "mean": nx + 3 + agg}
+    if mode == "noise_sum":
+        return {"pred_noise": ne + agg, "x_start": ne + agg + 3, "mean": ne + agg + 6}
+    out = 0 * cover if mode == "plain" else (S + 2 + 0 * cover if mode == "multibody" else agg)
+    return {"x_start": out + nx, "pred_noise": out + ne, "mean": out + nx + 3}
+
+
+def compose_bound(desc, A):
+    """(n_e + BOUND_SLACK) * 2^-24 * A_e per output: what one fp32 evaluation of the composition may differ from float64 by."""
+    n = compose_roundings(desc.mode, desc.n_bodies, compose_cover(desc)[desc.cond_steps:].double().view(1, -1, 1), desc.objective)
+    return {k: (n[k] + BOUND_SLACK) * U24 * A[k] for k in A}
+
+
+def compose_predict_f64(tab, desc, x, cond, t, pair_eps, single_eps=None, _mut=None):
+    """(mean, x_start, pred_noise, A), all float64, of p_mean_variance (:1033-1044) / the aggregation of p_sample_compose_outside
+    (:1410-1463) / gradient() (:1865-1982) followed by the objective's conversions (:1010-1027), on GIVEN U-Net outputs:
+
+      tab         the fp32 schedule of ``cindm_oracle.make_schedule`` (its entries are cast exactly)
+      x, cond     [B, state_len, F], [B, cond_steps, F] | None;  t an int
+      pair_eps    [W, P, B, window, 8] the pair model's outputs (``plain``: [1, 1, B, full_len, F], the model's on cat(cond, x))
+      single_eps  [nb, B, window, 4], ``multibody`` only
+
+    ``A`` = {"mean", "x_start", "pred_noise"}: each output's expression with every term replaced by its absolute value and every
+    difference by a sum -- the magnitude a rounding acts on.  The clamp: where the unclamped float64 x_start lies outside [-1, 1]
+    by more than its own bound, every fp32 evaluation within that bound clamps too, both values are +-1 exactly and the magnitude
+    passes as min(., 1); elsewhere the clamp is 1-Lipschitz and hands the unclamped value's error on, so the magnitude passes
+    unchanged (tests/test_compose_f64_host.py shows that min(., 1) everywhere is no bound: the fp32 oracle exceeds it).
+
+    pred_noise of ``mean`` (the reference computes pred_noise_ele per pair, :1428, and drops it): the same average as the other two.
+    ``_mut``: the host test's mutations of this function (tests/test_compose_f64_host.py), None for the reference."""
+    mut = _mut or ()
+    full = _compose_full(desc, x.double(), None if cond is None else cond.double())
+    nb, W, cs, T, F = desc.n_bodies, desc.n_windows, desc.compose_start_step, desc.window, 4 * desc.n_bodies
+    B, L = full.shape[0], full.shape[1]
+    c = lambda name: float(tab[name][t].double())
+    ra, rb, sa, sb = c("sqrt_recip_alphas_cumprod"), c("sqrt_recipm1_alphas_cumprod"), c("sqrt_alphas_cumprod"), c("sqrt_one_minus_alphas_cumprod")
+    c1, c2 = c("posterior_mean_coef1"), c("posterior_mean_coef2")
+    obj = desc.objective
+    nrd = compose_roundings(desc.mode, nb, compose_cover(desc).double().view(1, -1, 1), obj)
+
+    # every quantity below is a pair (value, magnitude)
+    def x0_of(out, xx):
+        o, ao = out
+        if obj == "pred_noise":
+            return ra * xx - rb * o, ra * xx.abs() + rb * ao
+        if obj == "pred_x0":
+            return o, ao
+        return sa * xx - sb * o, sa * xx.abs() + sb * ao
+
+    def eps_of(out, x0, xx):
+        if obj == "pred_noise":
+            return out
+        return (ra * xx - x0[0]) / rb, (ra * xx.abs() + x0[1]) / rb
+
+    def clamp(x0, n):
+        if not desc.clip:
+            return x0
+        v, a = x0
+        sure = v.abs() >= 1.0 + (n + BOUND_SLACK) * U24 * a
+        if "min_clamp" in mut:                # min(., 1) on every element: not a bound (see above)
+            sure = torch.ones_like(sure)
+        return v.clamp(-1.0, 1.0), torch.where(sure, a.clamp(max=1.0), a)
+
+    def post_mean(x0, xx):
+        return c1 * x0[0] + c2 * xx, c1 * x0[1] + c2 * xx.abs()
+
+    def aggregate(per_pair, sum_form):
+        """per_pair(kk, p, xw) -> (value, magnitude) [B, T, 8] of pair p in window kk; scatter to [W, B, L, sender, receiver, 4], sum
+        over senders [/ (nb - 1)], sum over windows, divide by the mask's sum | mean over windows (:989-999, :1437-1458)."""
+        agg = [torch.zeros((W, B, L, nb, nb, 4), dtype=torch.float64) for _ in range(2)]
+        mask = torch.zeros((W, B, L, F), dtype=torch.float64)
+        for kk in range(W):
+            lo = kk * cs
+            mask[kk, :, lo:lo + T] = 1.0
+            for p, (ii, jj) in enumerate(compose_pairs(nb)):
+                index = torch.cat([torch.arange(ii * 4, (ii + 1) * 4), torch.arange(jj * 4, (jj + 1) * 4)])
+                for a, v in zip(agg, per_pair(kk, p - 1 if ("pair_index" in mut and nb >= 3 and p > 0) else p, full[:, lo:lo + T, index])):
+                    lo4, hi4 = (v[..., 4:], v[..., :4]) if "slot" in mut else (v[..., :4], v[..., 4:])
+                    a[kk, :, lo:lo + T, jj, ii] = lo4
+                    a[kk, :, lo:lo + T, ii, jj] = hi4
+        senders = nb if "nb" in mut else nb - 1
+        cover, n_win = mask.sum(0), float(W)
+        if "cover" in mut:
+            cover, n_win = torch.full_like(cover, float(W)), cover.clamp(min=1.0)
+        out = []
+        for a in agg:
+            a = a.sum(-3).flatten(start_dim=3)
+            out.append(a.sum(0) / (cover / n_win) if sum_form else (a / senders).sum(0) / cover)
+        return tuple(out)
+
+    E = pair_eps.double()
+    pair = lambda kk, p: (E[kk, p], E[kk, p].abs())
+
+    if desc.mode == "mean":
+        def per_pair(kk, p, xw):
+            x0 = x0_of(pair(kk, p), xw)
+            ee = eps_of(pair(kk, p), x0, xw)
+            if "clamp_after" not in mut:
+                x0 = clamp(x0, 0 if obj == "pred_x0" else 3)
+            return x0, ee, post_mean(x0, xw)
+        parts = [[], [], []]
+        for k in range(3):
+            parts[k] = aggregate(lambda kk, p, xw, k=k: per_pair(kk, p, xw)[k], False)
+        x0, eps, mean = parts
+        if "clamp_after" in mut:
+            x0 = clamp(x0, nrd["x_start"])
+            mean = post_mean(x0, full)
+    elif desc.mode == "noise_sum":
+        eps = aggregate(lambda kk, p, xw: eps_of(pair(kk, p), x0_of(pair(kk, p), xw), xw), True)
+        x0 = clamp((ra * full - rb * eps[0], ra * full.abs() + rb * eps[1]), nrd["x_start"])        # :1459, whatever the objective
+        mean = post_mean(x0, full)
+    else:
+        if desc.mode == "plain":
+            assert E.shape[:2] == (1, 1)
+            out = pair(0, 0)
+        elif desc.mode == "multibody":
+            assert W == 1 and T == L
+            s = aggregate(lambda kk, p, xw: pair(kk, p), True)            # one window: the divisor is 1
+            U = single_eps.double()
+            u = torch.cat([U[i] for i in range(nb)], dim=2)               # [B, L, nb * 4], body-major features
+            coef = _as_f32(desc.uncond_coef)
+            out = s[0] - coef * u, s[1] + coef * u.abs()
+        else:
+            out = aggregate(lambda kk, p, xw: pair(kk, p), desc.mode == "sum-inside")
+        if "cond_offset" in mut:              # windows indexed by the state's row lx instead of the full sequence's l = lx + cond_steps
+            out = tuple(torch.roll(v, desc.cond_steps, dims=1) for v in out)
+        x0u = x0_of(out, full)
+        eps = eps_of(out, x0u, full)                                      # from the unclamped x_start (:1012-1027: clip_x_start is off)
+        x0 = clamp(x0u, nrd["x_start"])
+        mean = post_mean(x0, full)
+    k = desc.cond_steps
+    vals = [v[0][:, k:] for v in (mean, x0, eps)]
+    A = {name: v[1][:, k:] for name, v in (("mean", mean), ("x_start", x0), ("pred_noise", eps))}
+    return vals[0], vals[1], vals[2], A
