@@ -251,7 +251,7 @@ struct Src {
     const float* stats;   // GN: [Bp][8][P][2] (mean, M2);  LN: [rows][P][2]
     int P;                // partials per statistic
     int gw;               // GN group width (channels per group)
-    float cnt;            // elements per partial (GN: L*min(gw,32); LN: 32)
+    float cnt;            // elements per partial (GN: L*gcd(gw,32); LN: 32)
     const float* gamma;   // [C] (GN weight / LN g)
     const float* beta;    // [C] (GN bias) or null
     const float* tb;      // per-timestep bias table base (already offset to this layer) or null
@@ -327,9 +327,17 @@ __device__ __forceinline__ void merge_stats(const float* st, int P, float cnt, f
     rstd = 1.0f / sqrtf(M2 / (cnt * (float)P) + eps);
 }
 
+// GroupNorm groups of 3 * 2^k channels (GroupNorm(8, C) at C = 96 m: 12, 24, 48 or 96 wide): the template parameter G3 of
+// the GEMM kernels.  Such a group is neither inside one 32-column tile nor made of whole tiles, so its statistics are kept
+// per SEGMENT of seg = gcd(gw, 32) = min(2^k, 32) adjacent channels: a segment straddles neither a tile nor a group, every
+// group is gw / seg (= 3 up to gw = 96) segments of equal count Lout * seg, and the consumers merge them as they merge the
+// whole-tile partials of the wide power-of-two groups (merge_stats).  The channel -> group map is a division by gw: a shift
+// by k, then x / 3 == (x * 43691) >> 17 (exact for x < 2^16).  The instantiations with G3 = false are the shift code they were.
+__device__ __forceinline__ int g3_group(int c, int k) { return (int)(((unsigned)(c >> k) * 43691u) >> 17); }
+
 // Shared epilogue of the GEMM kernels: cross-wave K reduction through LDS, bias, optional "+ Mish(GroupNorm(y))"
 // and "+ residual" terms, store, and (mean, M2) statistics of the output tile (GroupNorm / LayerNorm partials).
-template <bool HAS_ACC>
+template <bool HAS_ACC, bool G3 = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[3][2], float (*Red)[TM * LDR], const float* tabE,
                                               bool skip_stats) {
     constexpr int T = HAS_ACC ? 1 : 0;
@@ -388,7 +396,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[3]
             const size_t grow = (size_t)b0 * a.Lout + r;
             if (a.e_y) {
                 const int s = (r * a.lout_magic) >> 16;
-                const int ti = (s * 8 + (gn >> (31 - __builtin_clz(a.e_gw)))) * 2;
+                int ti;
+                if constexpr (G3) ti = (s * 8 + g3_group(gn, __builtin_ctz(a.e_gw))) * 2;
+                else ti = (s * 8 + (gn >> (31 - __builtin_clz(a.e_gw)))) * 2;
                 v += mish_f((ey[q] - tabE[ti]) * tabE[ti + 1] * eg + eb);
             }
             if (!a.act_gamma) {
@@ -448,8 +458,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[3]
         // Thread (n = tid & 31, rq = tid >> 5) accumulates column n over the rows of samples rq, rq + 8, ... as sums
         // of (x - K) and (x - K)^2 around a pivot K taken from the data (one pass, no cancellation); the gwt columns
         // of a group are adjacent lanes and are combined on the DPP network in a fixed order.
-        const int gwt = min(a.so_gw, TN);             // group columns inside this tile (power of two)
-        const int P = max(1, a.so_gw / TN);           // partials per statistic
+        // G3: one partial per segment of gcd(gw, 32) columns, P = gw / segment partials per statistic
+        const int gwt = G3 ? min(a.so_gw & -a.so_gw, TN) : min(a.so_gw, TN);      // columns per partial inside this tile (power of two)
+        const int P = G3 ? a.so_gw / gwt : max(1, a.so_gw / TN);                  // partials per statistic
         const float ne = (float)(a.Lout * gwt), inv_ne = 1.0f / ne;
         for (int sidx = rq; sidx < a.spt; sidx += 8) {
             const float* col = &Red[0][sidx * a.Lout * LDR + n];
@@ -458,9 +469,15 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[3]
             for (int l = 0; l < a.Lout; ++l) { const float d = col[l * LDR] - K; s1 += d; s2 += d * d; }
             s1 = seg_total(s1, gwt);
             s2 = seg_total(s2, gwt);
-            if ((n & (gwt - 1)) == gwt - 1 && sidx < ns) {
-                const int g = (n0 + n) >> (31 - __builtin_clz(a.so_gw));
-                const int p = (n0 / TN) & (P - 1);
+            if ((n & (gwt - 1)) == gwt - 1 && sidx < ns && (!G3 || nok)) {
+                int g, p;
+                if constexpr (G3) {
+                    g = g3_group(n0 + n, __builtin_ctz(a.so_gw));
+                    p = (n0 + n - g * a.so_gw) >> (31 - __builtin_clz(gwt));
+                } else {
+                    g = (n0 + n) >> (31 - __builtin_clz(a.so_gw));
+                    p = (n0 / TN) & (P - 1);
+                }
                 float* o = a.stats_out + (((size_t)(b0 + sidx) * 8 + g) * P + p) * 2;
                 o[0] = K + s1 * inv_ne;
                 o[1] = fmaxf(s2 - s1 * s1 * inv_ne, 0.f);
@@ -490,7 +507,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[3]
 // after the multiply; one barrier per stage.  The loop body is BRANCH-FREE (clamped addresses + selects,
 // the tail re-loads the last stage) so that hipcc keeps counted vmcnt waits instead of draining at every
 // join.  KC is 32 for the tap-ful convolutions and 64/128 for 1x1 layers (same bytes in flight per stage).
-template <int T, int KC, int ROWS, int MODE, int DBG = 0>
+template <int T, int KC, int ROWS, int MODE, int DBG = 0, bool G3 = false>
 __global__ __launch_bounds__(256) void conv_gemm_kernel(const GemmArgs a) {
     constexpr int TT = T > 0 ? T : 1;
     constexpr int LDAK = KC + 2;            // LDS row pitch: 2*row + k spreads 16 rows x 2 k over 32 banks
@@ -621,7 +638,8 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const GemmArgs a) {
         int srow8[NP];                       // (sample of staged row) * 8, for the GN table
 #pragma unroll
         for (int p = 0; p < NP; ++p) srow8[p] = ((min(r0 + RPP * p, rows_in - 1) * a.lin_magic) >> 16) * 8;
-        const int gw_shift = 31 - __builtin_clz(a.src[0].gw | 1);      // group widths are powers of two (host checks)
+        // group widths are powers of two, or (G3) 3 * 2^gw_shift (host checks)
+        const int gw_shift = G3 ? __builtin_ctz(a.src[0].gw | 0x40000000) : 31 - __builtin_clz(a.src[0].gw | 1);
 
         auto store_a = [&](int ch, int buf, const float4 (&av)[NP]) {
             int cl, C, ld;
@@ -635,7 +653,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const GemmArgs a) {
                 const int r = r0 + RPP * p;
                 float4 v = av[p];
                 if constexpr (MODE == SRC_GN_MISH) {
-                    const int ti = (srow8[p] + (clc >> gw_shift)) * 2;
+                    const int ti = (srow8[p] + (G3 ? g3_group(clc, gw_shift) : (clc >> gw_shift))) * 2;
                     const float m = tabA[ti], rs = tabA[ti + 1];
                     v.x = mish_f((v.x - m) * rs * g.x + bt.x) + tb.x;
                     v.y = mish_f((v.y - m) * rs * g.y + bt.y) + tb.y;
@@ -723,7 +741,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const GemmArgs a) {
         __syncthreads();
     }
 
-    gemm_epilogue<(T > 0)>(a, acc, Red, tabE, DBG == 8);
+    gemm_epilogue<(T > 0), G3>(a, acc, Red, tabE, DBG == 8);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -742,7 +760,7 @@ constexpr float H3_SCALE = 2048.0f, H3_INV = 1.0f / 2048.0f;
 
 // ABL (timing ablations of the main loop, wrong results): 1 no weight reloads, 2 no MFMAs, 3 no activation restaging
 // (and no per-stage barrier), 4 = 1 + 3, 5 no LDS fragment reads
-template <int T, int ROWS, int MODE, bool RES = false, int ABL = 0>
+template <int T, int ROWS, int MODE, bool RES = false, int ABL = 0, bool G3 = false>
 __global__ __launch_bounds__(256) void conv_gemm_h3_kernel(const GemmArgs a) {
     constexpr int KC = 128;
     constexpr int PITCH = 272;              // bytes per LDS row per plane: 128 halfs + 16 B pad
@@ -883,7 +901,7 @@ __global__ __launch_bounds__(256) void conv_gemm_h3_kernel(const GemmArgs a) {
     int srow8[NP];
 #pragma unroll
     for (int p = 0; p < NP; ++p) srow8[p] = ((min(r0 + RPP * p, rows_in - 1) * a.lin_magic) >> 16) * 8;
-    const int gw_shift = 31 - __builtin_clz(a.src[0].gw | 1);
+    const int gw_shift = G3 ? __builtin_ctz(a.src[0].gw | 0x40000000) : 31 - __builtin_clz(a.src[0].gw | 1);
 
     auto store_a = [&](int ch, int buf, int p_lo, int p_hi) {      // staging rows [p_lo, p_hi) of the NP per thread
         int cl, C, ld;
@@ -897,7 +915,7 @@ __global__ __launch_bounds__(256) void conv_gemm_h3_kernel(const GemmArgs a) {
             const int r = r0 + RPP * p;
             float4 v = areg[p];
             if constexpr (MODE == SRC_GN_MISH) {
-                const int ti = (srow8[p] + (clc >> gw_shift)) * 2;
+                const int ti = (srow8[p] + (G3 ? g3_group(clc, gw_shift) : (clc >> gw_shift))) * 2;
                 const float m = tabA[ti], rs = tabA[ti + 1];
                 v.x = mish_f((v.x - m) * rs * g.x + bt.x) + tb.x;
                 v.y = mish_f((v.y - m) * rs * g.y + bt.y) + tb.y;
@@ -992,7 +1010,7 @@ __global__ __launch_bounds__(256) void conv_gemm_h3_kernel(const GemmArgs a) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = accM[i][j] + accL[i][j] * H3_INV;
     if (a.dbg == 9) { if (acc[0][0][0] == 123.456f) a.out[0] = 1.f; return; }      // no epilogue
-    gemm_epilogue<true>(a, acc, Red, tabE, a.dbg == 8);
+    gemm_epilogue<true, G3>(a, acc, Red, tabE, a.dbg == 8);
     if constexpr (RES) {
         // second output: out2 = W2 . x + bias2 (plain epilogue: reduce, bias, store)
 #pragma unroll

@@ -182,7 +182,9 @@ extern "C" int cindm_unet1d_get_option(const cindm_unet1d* h, const char* key, i
 extern "C" int cindm_unet1d_create(const cindm_unet1d_desc* desc, cindm_unet1d** out) {
     REQUIRE(desc && out, "null argument");
     REQUIRE(desc->n_mults >= 1 && desc->n_mults <= 8, "n_mults out of range");
-    REQUIRE(desc->dim >= 32 && (desc->dim & (desc->dim - 1)) == 0, "dim must be a power of two >= 32");
+    // 96: GroupNorm groups of 3 * 2^k channels, served by the generic tier (kernels.h, g3_group); every accepted width makes
+    // every level's group width dim * m / 8 a multiple of 4
+    REQUIRE(desc->dim == 96 || (desc->dim >= 32 && (desc->dim & (desc->dim - 1)) == 0), "dim must be a power of two >= 32 or 96");
     for (int i = 0; i < desc->n_mults; ++i)
         REQUIRE(desc->dim_mults[i] >= 1 && (desc->dim_mults[i] & (desc->dim_mults[i] - 1)) == 0, "dim_mults must be powers of two");
     REQUIRE(desc->transition_dim % 4 == 0 && desc->transition_dim >= 4 && desc->transition_dim <= 32,
@@ -758,14 +760,35 @@ struct Emitter {
             if (prof && !dry) { prof->back().gx = grid.x; prof->back().gy = grid.y; prof->back().nstage = T ? a.CinP / a.KC : 0; }
         }
         const int mode = a.src[0].mode;
+        // a GroupNorm width of 3 * 2^k (dim = 96) in what this launch produces, normalises on load or adds in its epilogue: the G3
+        // instantiations (kernels.h, g3_group).  Producer-side activation needs whole groups in a tile: never at these widths.
+        auto g3w = [](int gw) { return gw > 0 && (gw & (gw - 1)) != 0; };
+        const bool g3 = (a.stats_out && g3w(a.so_gw)) || (mode == SRC_GN_MISH && g3w(a.src[0].gw)) || (a.e_y && g3w(a.e_gw));
 #define CINDM_LAUNCH(T_, KC_, ROWS_, MODE_) KLAUNCH((*this), (conv_gemm_kernel<T_, KC_, ROWS_, MODE_>), grid, dim3(256), 0, a)
+#define CINDM_LAUNCH_G3(T_, KC_, ROWS_, MODE_) KLAUNCH((*this), (conv_gemm_kernel<T_, KC_, ROWS_, MODE_, 0, true>), grid, dim3(256), 0, a)
+#define CINDM_LAUNCH_H3_G3(MODE_, RES_) KLAUNCH((*this), (conv_gemm_h3_kernel<5, 48, MODE_, RES_, 0, true>), grid, dim3(256), 0, a)
         bool ok = true;
         // profile mode: the (idempotent) launch is repeated inside one event bracket so that the ~6 us cost of the
         // bracket itself is amortised; the reported time is bracket / prof_reps
         for (int rep = 0; rep < (prof ? prof_reps : 1); ++rep) {
         const int dbg_h3 = h ? h->O("dbg") : 0;
         const_cast<GemmArgs&>(a).dbg = a.h3 ? dbg_h3 : 0;
-        if (a.h3 && T == 5 && mode == SRC_PLAIN && a.W2) KLAUNCH((*this), (conv_gemm_h3_kernel<5, 48, SRC_PLAIN, true>), grid, dim3(256), 0, a);
+        if (g3) {
+            // the launches of emit_rtb's three-launch form and of emit_head, on the split-fp16 and on the fp32-MFMA path
+            if (a.act_gamma) ok = false;
+            else if (a.h3 && T == 5 && mode == SRC_PLAIN && a.W2) CINDM_LAUNCH_H3_G3(SRC_PLAIN, true);
+            else if (a.h3 && T == 5 && mode == SRC_PLAIN) CINDM_LAUNCH_H3_G3(SRC_PLAIN, false);
+            else if (a.h3 && T == 5 && mode == SRC_GN_MISH) CINDM_LAUNCH_H3_G3(SRC_GN_MISH, false);
+            else if (a.h3) ok = false;
+            else if (T == 0) CINDM_LAUNCH_G3(0, 32, 48, SRC_PLAIN);
+            else if (T == 5 && mode == SRC_PLAIN) CINDM_LAUNCH_G3(5, 32, 48, SRC_PLAIN);
+            else if (T == 5 && mode == SRC_GN_MISH) CINDM_LAUNCH_G3(5, 32, 48, SRC_GN_MISH);
+            else if (T == 1 && a.KC == 128 && mode == SRC_PLAIN) CINDM_LAUNCH_G3(1, 128, 48, SRC_PLAIN);
+            else if (T == 1 && a.KC == 64 && mode == SRC_PLAIN) CINDM_LAUNCH_G3(1, 64, 48, SRC_PLAIN);
+            else if (T == 1 && a.KC == 64 && mode == SRC_GN_MISH) CINDM_LAUNCH_G3(1, 64, 48, SRC_GN_MISH);
+            else ok = false;
+        }
+        else if (a.h3 && T == 5 && mode == SRC_PLAIN && a.W2) KLAUNCH((*this), (conv_gemm_h3_kernel<5, 48, SRC_PLAIN, true>), grid, dim3(256), 0, a);
         else if (a.h3 && T == 5 && mode == SRC_PLAIN && dbg_h3 >= 21 && dbg_h3 <= 25) {
             if (dbg_h3 == 21) KLAUNCH((*this), (conv_gemm_h3_kernel<5, 48, SRC_PLAIN, false, 1>), grid, dim3(256), 0, a);
             else if (dbg_h3 == 22) KLAUNCH((*this), (conv_gemm_h3_kernel<5, 48, SRC_PLAIN, false, 2>), grid, dim3(256), 0, a);
@@ -810,6 +833,8 @@ struct Emitter {
         } else ok = false;
         }
 #undef CINDM_LAUNCH
+#undef CINDM_LAUNCH_G3
+#undef CINDM_LAUNCH_H3_G3
         if (!ok) err = hipErrorInvalidValue;
         prof_end();
         note_error();
@@ -1024,6 +1049,18 @@ static Ten emit_rtb_dconv(Emitter& E, const std::string& p, const Ten& x0, const
     return out;
 }
 
+// GroupNorm(8, C) partial statistics of an [*, L, C] tensor as the GEMM kernels write and merge them (kernels.h): one (mean, M2)
+// partial per (sample, group, segment of seg = gcd(gw, 32) channels) -- the whole group up to gw = 32, its 32-column tiles at the wider
+// powers of two, and at gw = 3 * 2^k (dim = 96: 12, 24, 48, 96) three segments of 4, 8, 16, 32 channels that straddle neither a tile
+// nor a group.  tile_local: whole groups inside a 32-column tile, which is what producer-side activation ("local_gn") needs.
+struct GnPart { int gw, P; float cnt; bool tile_local; };
+static GnPart gn_part(int C, int L) {
+    const int gw = C / 8;
+    int seg = gw & -gw;
+    if (seg > TN) seg = TN;
+    return {gw, gw / seg, (float)(L * seg), gw == seg};
+}
+
 // ResidualTemporalBlock (model/diffusion_1d.py:483-511) as three launches:
 //   A: y0 = conv5(x) + b0                      (+ GroupNorm partial stats of y0)
 //   B: y1 = conv5(Mish(GN(y0)) + tbias_t) + b1 (normalise-on-load; + stats of y1)
@@ -1032,8 +1069,10 @@ static Ten emit_rtb(Emitter& E, const std::string& p, const Ten& x0, const Ten* 
     cindm_unet1d* h = E.h;
     if (!want_ln && dconv_applicable(h, p, x0, x1, cout)) return emit_rtb_dconv(E, p, x0, x1, cout);
     const int Bp = (int)E.rows, L = x0.L;
-    const int gw = cout / 8, Pn = gw > TN ? gw / TN : 1;
-    const float cnt = (float)(L * (gw < TN ? gw : TN));
+    const GnPart gp = gn_part(cout, L);
+    const int gw = gp.gw, Pn = gp.P;
+    const float cnt = gp.cnt;
+    if (gw % 4 && E.err == hipSuccess) E.err = hipErrorInvalidValue;      // the loaders' float4 of four adjacent channels lies in one group
     const Packed& w0 = h->packed.at(p + ".blocks.0.block.0");
     const Packed& w1 = h->packed.at(p + ".blocks.1.block.0");
     Ten out = E.ten(L, cout), y0 = E.ten(L, cout), y1 = E.ten(L, cout);
@@ -1042,7 +1081,7 @@ static Ten emit_rtb(Emitter& E, const std::string& p, const Ten& x0, const Ten* 
     float* st1 = E.tmp((size_t)Bp * 8 * Pn * 2, k1);
     GemmArgs a;
     // GroupNorm groups inside one 32-column tile (cout <= 256): the producers normalise + activate their own output
-    const bool local_gn = gw <= TN && h->O("local_gn");
+    const bool local_gn = gp.tile_local && h->O("local_gn");
     auto rc = h->packed.find(p + ".residual_conv");
     const bool identity = rc == h->packed.end();
     // the 1x1 residual_conv rides on launch A's centre tap (split-fp16 kernel only): r = Wr . x + br
@@ -1529,8 +1568,9 @@ struct Fwd {
     // final_conv: Conv1dBlock(dim, dim, 5) then Conv1d(dim, F, 1) (:605-608)
     void emit_head() {
         const int Bp = (int)E.rows, L = cur.L, C = h->d.dim;
-        const int gw = C / 8, Pn = gw > TN ? gw / TN : 1;
-        const float cnt = (float)(L * (gw < TN ? gw : TN));
+        const GnPart gp = gn_part(C, L);
+        const int gw = gp.gw, Pn = gp.P;
+        const float cnt = gp.cnt;
         Ten y0 = E.ten(L, C);
         float* st0 = E.alloc((size_t)Bp * 8 * Pn * 2);
         GemmArgs a;

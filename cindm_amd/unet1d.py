@@ -30,6 +30,10 @@ class TemporalUnet1D(_ExchangeRecovery, _NativeModel):
     """Drop-in for ``TemporalUnet1D(horizon, transition_dim, cond_dim, dim=64,
     dim_mults=(1, 2, 4, 8), attention=False)`` (model/diffusion_1d.py:519-527).
 
+    ``dim``: a power of two >= 32, or 96 (the reference's ``--Unet_dim 96`` checkpoint); ``dim_mults``: powers of
+    two.  dim 64 runs the fused level / deep-block / attention-site kernels; every other width, 96 included, runs
+    the generic convolution and attention kernels (more launches per forward, the same results contract).
+
     Extra keyword ``timesteps`` (default 1000) sizes the per-timestep bias table that replaces
     the time-embedding MLP at run time."""
 

@@ -59,9 +59,12 @@ int cindm_ws_prof_read(unsigned long long* dst);
 typedef struct {
     int32_t horizon;          /* TemporalUnet1D(horizon=...)           :521 */
     int32_t transition_dim;   /* n_bodies * 4 features                 :522 */
-    int32_t dim;              /* base width, 64                        :524 */
+    int32_t dim;              /* base width: a power of two >= 32 (64: the n-body checkpoints), or 96 (the
+                                 "Unet_dim-96" checkpoint; GroupNorm groups of 12 / 24 / 48 / 96 channels, served by the
+                                 generic kernels only: three launches per block and per attention site).  Any other width
+                                 is refused at create with "dim must be a power of two >= 32 or 96"      :524 */
     int32_t n_mults;          /* len(dim_mults), <= 8                  :525 */
-    int32_t dim_mults[8];
+    int32_t dim_mults[8];     /* powers of two */
     int32_t attention;        /* 0/1                                   :526 */
     int32_t timesteps;        /* size of the per-timestep bias table (diffusion T, 1000) */
 } cindm_unet1d_desc;
