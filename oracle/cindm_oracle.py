@@ -1187,7 +1187,8 @@ def model_predictions_2d(d, shape, x, t, clip_x_start=False, rederive_pred_noise
     B, nb = shape[0], shape[1]
     T = d.tab
     tt = torch.full((x.shape[0],), t, dtype=torch.long)
-    out = unet2d_forward(d.sd, x, tt)
+    model = getattr(d, "model", None)         # a stand-in for the U-Net (tests/test_step2d_f64_host.py), as Diffusion1D.model is
+    out = unet2d_forward(d.sd, x, tt) if model is None else model(x, tt)
     if d.objective == "pred_noise":
         eps = out
         if share_noise:

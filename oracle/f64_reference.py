@@ -1,4 +1,5 @@
-"""Float64 reference of the two U-Net forwards and of ForceUnet with its input gradient, and the per-row error budget the HIP kernels are held to.
+"""Float64 reference of the two U-Net forwards and of ForceUnet with its input gradient, and the per-row error budget the HIP kernels are held to;
+further down, the 1-D composition and the 2-D reverse step on GIVEN U-Net outputs, with a per-element bound.
 
 TEST INFRASTRUCTURE ONLY, like ``cindm_oracle``: a checker for the HIP path, imported by ``tests/`` alone.
 
@@ -342,3 +343,163 @@ def compose_predict_f64(tab, desc, x, cond, t, pair_eps, single_eps=None, _mut=N
     vals = [v[0][:, k:] for v in (mean, x0, eps)]
     A = {name: v[1][:, k:] for name, v in (("mean", mean), ("x_start", x0), ("pred_noise", eps))}
     return vals[0], vals[1], vals[2], A
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The 2-D reverse step: from given U-Net outputs to (model_mean, x_start, pred_noise) and to the next state, in float64, with the
+# magnitude of every output
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Written from the reference (model/diffusion_2d.py:712-725 share_states_over_boundaries, :727-754 model_predictions, :757-773
+# p_mean_variance, :775-785 sample_noise, :804-808 p_sample) and from cindm_oracle's restatement of it (model_predictions_2d,
+# p_sample_2d), on float64.  It evaluates no network: E is an argument, so a comparison with the library on the library's own E
+# measures sharing + conversion + clamp + update alone.  The DDIM form follows the project's own definition (the docstring of
+# cindm_amd.GaussianDiffusion.ddim_sample): the reference's 2-D ddim_sample cannot run.
+
+STEP2D_ENTRIES = ("p_mean_variance", "model_predictions")
+
+
+def step2d_roundings(nb, objective, *, share_noise, clip, rederive=False, entry="p_mean_variance"):
+    """n_e: the fp32 roundings on the longest path to one element of (mean, x_start, pred_noise), counted on the reference's
+    formulas (the state channels: a boundary channel is shared nowhere and has ``nb`` fewer per share, which the bound does not use):
+
+      share(nb)     nb - 1 adds and the division (the sum form counts the same)                                      -> nb
+      x0(out)       predict_start_from_noise / _from_v: two products and a difference, 3; pred_x0: the output, 0     -> nx
+      eps(x0)       predict_noise_from_start: product, difference, quotient                                          -> + 3
+      mean(x0)      q_posterior: two products and a sum                                                              -> + 3
+
+      model_predictions   pred_noise: out = share(E) | E;  x_start = out + 3;  pred_noise = out, or x_start + 3 when clip_x_start and
+                          rederive_pred_noise.   pred_x0 / pred_v: nothing is shared; x_start = nx, pred_noise = nx + 3
+      p_mean_variance     model_predictions(share_noise=self.share_noise) without clip; the clamp adds nothing; share_noise False:
+                          x_start + nb, then mean = x_start + 3 + nb;  else mean = x_start + 3
+
+    ``"x_start_pre"`` is x_start before p_mean_variance's share, the count the clamp's own bound is taken with.  ``mean`` is None for
+    ``model_predictions``.  A contracted FMA removes a rounding, never adds one."""
+    assert entry in STEP2D_ENTRIES and objective in ("pred_noise", "pred_x0", "pred_v")
+    nx = 0 if objective == "pred_x0" else 3
+    out = nb if (objective == "pred_noise" and share_noise) else 0
+    pre = out + nx
+    if entry == "model_predictions":
+        eps = (pre + 3 if (clip and rederive) else out) if objective == "pred_noise" else nx + 3
+        return {"x_start_pre": pre, "x_start": pre, "pred_noise": eps, "mean": None}
+    eps = out if objective == "pred_noise" else nx + 3
+    late = 0 if share_noise else nb
+    return {"x_start_pre": pre, "x_start": pre + late, "pred_noise": eps, "mean": pre + late + 3 + late}
+
+
+def step2d_bound(n, A):
+    """(n_e + BOUND_SLACK) * 2^-24 * A_e: what one fp32 evaluation may differ from float64 by, per element."""
+    return (n + BOUND_SLACK) * U24 * A
+
+
+def step2d_predict_f64(tab, shape, x, t, E, *, objective, share_noise, use_average_share, clip, rederive=False,
+                       entry="p_mean_variance", _mut=None):
+    """(mean, x_start, pred_noise, A), all float64 [B * nb, C, H, W], of ``GaussianDiffusion.p_mean_variance`` (:757-773; the
+    constructor's ``share_noise``, ``clip`` = clip_denoised) or ``model_predictions`` (:727-754; ``share_noise`` the call's argument,
+    ``clip`` = clip_x_start, ``rederive`` = rederive_pred_noise; mean is None) on a GIVEN model output:
+
+      tab     the fp32 schedule of ``cindm_oracle.make_schedule`` (its entries are cast exactly)
+      shape   (B, nb, C, H, W);  x, E [B * nb, C, H, W] (image b * nb + k is boundary copy k of design b);  t an int
+
+    pred_noise of p_mean_variance is the one its model_predictions call returns (clip_x_start off): the shared output, or the noise
+    re-derived from the UNCLAMPED x_start under pred_x0 / pred_v.
+
+    ``A`` = {"mean", "x_start", "pred_noise"}: each output's expression with every term replaced by its absolute value and every
+    difference by a sum, built as ``compose_predict_f64`` builds it.  The clamp: where the unclamped float64 x_start lies outside
+    [-1, 1] by more than its own bound, every fp32 evaluation within that bound clamps too and the magnitude passes as min(., 1);
+    elsewhere the clamp is 1-Lipschitz and the magnitude passes unchanged.
+
+    ``_mut``: the host test's mutations of this function (tests/test_step2d_f64_host.py), None for the reference."""
+    assert entry in STEP2D_ENTRIES
+    mut = _mut or ()
+    B, nb, C, H, W = shape
+    x, E = x.double().reshape(B * nb, C, H, W), E.double().reshape(B * nb, C, H, W)
+    if "x_copy0" in mut:                          # (f) every copy reads the x of copy 0
+        x = x.reshape(B, nb, C, H, W)[:, :1].expand(-1, nb, -1, -1, -1).reshape(B * nb, C, H, W)
+    ax = x.abs()
+    c = lambda name: float(tab[name][t].double())
+    ra, rb, sa, sb = c("sqrt_recip_alphas_cumprod"), c("sqrt_recipm1_alphas_cumprod"), c("sqrt_alphas_cumprod"), c("sqrt_one_minus_alphas_cumprod")
+    c1, c2 = c("posterior_mean_coef1"), c("posterior_mean_coef2")
+    nrd = step2d_roundings(nb, objective, share_noise=share_noise, clip=clip, rederive=rederive, entry=entry)
+    avg = bool(use_average_share) != ("mean_sum" in mut)            # (b) mean where sum is asked, and the reverse
+    Cs = C if "seam" in mut else C - 3                              # (c) boundary channels shared too
+
+    # every quantity below is a pair (value, magnitude)
+    def share(p):
+        out = []
+        for v in p:
+            groups = (1, B * nb) if "all_images" in mut else (B, nb)        # (a) share over all B * nb images
+            s = v[:, :Cs].reshape(groups[0], groups[1], Cs, H, W)
+            s = s.mean(dim=1, keepdim=True) if avg else s.sum(dim=1, keepdim=True)
+            v = v.clone()
+            v[:, :Cs] = s.expand(-1, groups[1], -1, -1, -1).reshape(B * nb, Cs, H, W)
+            out.append(v)
+        return tuple(out)
+
+    def clamp(p, n):
+        v, a = p
+        sure = v.abs() >= 1.0 + (n + BOUND_SLACK) * U24 * a
+        return v.clamp(-1.0, 1.0), torch.where(sure, a.clamp(max=1.0), a)
+
+    def eps_of(x0):
+        return (ra * x - x0[0]) / rb, (ra * ax + x0[1]) / rb
+
+    out = (E, E.abs())
+    if share_noise and (objective == "pred_noise" or "share_x0v" in mut):       # (i) pred_x0 / pred_v: the output shared inside
+        out = share(out)
+    if objective == "pred_noise":
+        x0u = (ra * x - rb * out[0], ra * ax + rb * out[1])
+    elif objective == "pred_x0":
+        x0u = out
+    else:
+        x0u = (sa * x - sb * out[0], sa * ax + sb * out[1])
+
+    if entry == "model_predictions":
+        x0 = clamp(x0u, nrd["x_start_pre"]) if clip else x0u
+        if objective == "pred_noise":
+            eps = out
+            if clip and rederive and "raw_eps" not in mut:          # (h) the raw shared output where the re-derived noise belongs
+                eps = eps_of(x0u if "rederive_unclamped" in mut else x0)        # (g) re-derived from the unclamped x_start
+        else:
+            eps = eps_of(x0u if "rederive_unclamped" in mut else x0)
+        return None, x0[0], eps[0], {"mean": None, "x_start": x0[1], "pred_noise": eps[1]}
+
+    eps = out if objective == "pred_noise" else eps_of(x0u)
+    x0 = x0u
+    if clip and "clamp_after" not in mut:
+        x0 = clamp(x0, nrd["x_start_pre"])
+    if not share_noise:
+        x0 = share(x0)
+    if clip and "clamp_after" in mut:             # (d) clamp after sharing x_start instead of before
+        x0 = clamp(x0, nrd["x_start"])
+    mean = (c1 * x0[0] + c2 * x, c1 * x0[1] + c2 * ax)
+    if not share_noise and "mean_unshared" not in mut:              # (e) the posterior mean not shared again
+        mean = share(mean)
+    return mean[0], x0[0], eps[0], {"mean": mean[1], "x_start": x0[1], "pred_noise": eps[1]}
+
+
+def step2d_update_f64(form, base, A, n, *, z=None, t=None, logvar=None, eps=None, A_eps=None, n_eps=None, row=None, last=False,
+                      w=None, g=None):
+    """The next state from the predictions, in float64 -> (state, A, n_e), three forms:
+
+      "ddpm"    base = model_mean: mean + exp(0.5 logvar) z (p_sample :804-808; ``logvar`` the fp32 table entry at ``t``, ``z`` the
+                draw of sample_noise) -- 4 more roundings (the half, the exponential, the product, the sum) for t > 0; at t = 0 the
+                state IS the mean, nothing is added
+      "ddim"    base = x_start, ``eps`` the noise re-derived from it: x0 sqrt(alpha_next) + c eps + sigma z with ``row`` = the fp32
+                (sqrt(alpha_next), c, sigma) of ``ddim_schedule()``, cast exactly -- 5 more roundings (three products, two sums) on
+                the longer of the two paths; ``last`` (time_next < 0): the state IS x_start
+      "guided"  base = a state: base - w g (``w`` the fp32 guidance weight, ``g`` a given gradient) -- 2 more roundings, A += |w g|"""
+    base, A = base.double(), A.double()
+    if form == "ddpm":
+        if t == 0:
+            return base, A, n
+        sz = torch.exp(0.5 * logvar.double()) * z.double()
+        return base + sz, A + sz.abs(), n + 4
+    if form == "ddim":
+        if last:
+            return base, A, n
+        san, cc, sg = (float(v.double()) for v in row[:3])
+        sz = sg * z.double()
+        return base * san + cc * eps.double() + sz, A * abs(san) + abs(cc) * A_eps.double() + sz.abs(), max(n, n_eps) + 5
+    assert form == "guided"
+    wg = float(torch.as_tensor(w).double()) * g.double()
+    return base - wg, A + wg.abs(), n + 2
