@@ -74,6 +74,7 @@ SIGNATURES = {
     "cindm_ddpm1d_set_design_quadratic": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i64]),
     "cindm_ddpm1d_set_known2d": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32]),
     "cindm_ddpm1d_set_known1d": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i64, _i32, _i32]),
+    "cindm_ddpm1d_set_multistep": (C.c_int, [_vp, _vp, _i32, _vp, _i64]),
     "cindm_forceunet_status": (C.c_int, [_vp, _vp]),
     "cindm_forceunet_recovered": (C.c_int, [_vp]),
     "cindm_comm_unique_id": (C.c_int, [_vp]),

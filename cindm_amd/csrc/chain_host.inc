@@ -12,7 +12,9 @@
 //   QuadTablesScope     the quadratic objective's tables: taken by every chain entry, run by the two guided 1-D ones
 //   Known2DScope        the 2-D chains' known region: taken by every chain entry, run by the four 2-D ones
 //   Known1DScope        the 1-D chains' known region: taken by every chain entry, run by cindm_ddpm1d_sample / _sample_guided /
-//                       _sample_ddim / _sample_ddim_guided (bottom of this file)
+//                       _sample_ddim / _sample_ddim_guided
+//   MultistepScope      the second-order multistep solver: taken by every chain entry, run by cindm_ddpm1d_sample_ddim /
+//                       _sample_ddim_guided and cindm_ddpm2d_sample_ddim / _sample_ddim_force (bottom of this file)
 // On top of these, the six 1-D entries (ddpm1d_host.inc) state their own facts once in Chain1D (the workspace layout), step1_refuse /
 // chain1_refuse / guided_refuse, chain_io, ddim_tables1, loop_chain and guided_chain, and the four 2-D entries (ddpm2d_host.inc)
 // theirs in Chain2D (the workspace layout), chain2_refuse / force_refuse, ForceGuide, ddim_args2, ddpm_step2 / ddim_step2 and run_chain2.
@@ -54,6 +56,12 @@ struct Known1D {
     int64_t step_stride = 0, recur_stride = 0, batch = 0; int rows = 0, feats = 0, apply_init = 1;
 };
 
+// The second-order multistep solver as armed by the caller (cindm_ddpm1d_set_multistep, bottom of this file): the per-step kappa
+// (a host copy: the entry puts it beside its DDIM tables) and the caller's history buffer, shaped like the chain's state
+struct Multistep {
+    std::vector<float> kappa; float* hist = nullptr; int64_t hist_floats = 0;
+};
+
 struct cindm_ddpm1d {
     int T = 0;
     float* tab = nullptr;        // 13 tables, each [T]
@@ -76,6 +84,8 @@ struct cindm_ddpm1d {
     Known2D kn_armed; const Known2D* kn = nullptr;
     // the known region of the 1-D chains, likewise
     Known1D kn1_armed; const Known1D* kn1 = nullptr;
+    // the multistep solver: what the next chain call will take, and the one a running DDIM chain applies (null: none)
+    Multistep ms_armed; const Multistep* ms = nullptr;
     void drop_graph() {
         if (gexec) (void)hipGraphExecDestroy(gexec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -469,5 +479,58 @@ extern "C" int cindm_ddpm1d_set_known1d(cindm_ddpm1d* h, const float* known, int
     k.known = known; k.mask = mask; k.known_per_design = known_per_design ? 1 : 0; k.mask_per_design = mask_per_design ? 1 : 0;
     k.z_init = noise_init; k.z_step = noise_steps; k.z_recur = noise_recur; k.step_stride = step_stride; k.recur_stride = recur_stride;
     k.batch = batch; k.rows = rows; k.feats = feats; k.apply_init = apply_init ? 1 : 0;
+    return 0;
+}
+
+// ---- the second-order multistep solver (DESIGN 4.5r) -----------------------------------------------------------------------------------
+// cindm_ddpm1d_set_multistep arms the handle; the next chain entry takes the solver with MultistepScope -- so the call consumes it
+// however it ends -- and either refuses it (ms_refuse: every chain that is not one of the four DDIM chains) or checks it against its
+// schedule and state (ms_begin) and runs with it: the DDIM update of step i adds kappa[i] (X_i - X_{i-1}) to its value and writes X_i
+// to the history.  kappa[i] == 0 does not read the history: the first step of a chain, and of its recovery re-run, needs none.
+struct MultistepScope {
+    cindm_ddpm1d* h; Multistep m;
+    explicit MultistepScope(cindm_ddpm1d* h_) : h(h_) {
+        if (!h) return;
+        m = std::move(h->ms_armed); h->ms_armed = Multistep();
+    }
+    ~MultistepScope() { if (h) h->ms = nullptr; }
+    bool on() const { return m.hist != nullptr; }
+};
+
+static int ms_refuse(const MultistepScope& ms) {
+    REQUIRE(!ms.on(), "multistep solver: only the DDIM chains (cindm_ddpm1d_sample_ddim / _sample_ddim_guided, cindm_ddpm2d_sample_ddim / "
+                      "_sample_ddim_force) run it; the solver was dropped");
+    return 0;
+}
+
+// n_steps, coefs: the DDIM call's; state_floats, x, x2: the chain's state (x2: a second state buffer the update may read, or null)
+static int ms_begin(MultistepScope& ms, int32_t n_steps, const float* coefs, int64_t state_floats, const float* x, const float* x2 = nullptr) {
+    if (!ms.on()) return 0;
+    const Multistep& m = ms.m;
+    if ((int64_t)m.kappa.size() != (int64_t)n_steps)
+        return fail("multistep solver: armed for " + std::to_string(m.kappa.size()) + " steps, the chain runs " + std::to_string(n_steps));
+    if (m.hist_floats != state_floats)
+        return fail("multistep solver: the history holds " + std::to_string(m.hist_floats) + " floats, the chain's state " + std::to_string(state_floats));
+    for (int i = 0; i < n_steps; ++i)
+        REQUIRE(coefs[3 * i + 2] == 0.f, "multistep solver: every step's sigma must be zero (ddim_sampling_eta = 0: the solver is deterministic)");
+    REQUIRE(m.hist != x && m.hist != x2, "multistep solver: the history may not be a state buffer of the chain");
+    ms.h->ms = &ms.m;
+    return 0;
+}
+
+// (nothing armed: the key is what it was)
+static void ms_key(KeyBuilder& K, const cindm_ddpm1d* h) {
+    if (h->ms) K(1)(h->ms->hist);
+}
+
+extern "C" int cindm_ddpm1d_set_multistep(cindm_ddpm1d* h, const float* kappa_host, int32_t n_steps, float* hist, int64_t hist_floats) {
+    if (h) h->ms_armed = Multistep();      // (a refused call leaves the handle disarmed)
+    REQUIRE(h, "null handle");
+    if (!kappa_host) return 0;
+    REQUIRE(n_steps >= 1, "multistep solver: n_steps must be >= 1");
+    REQUIRE(hist && hist_floats > 0 && ((uintptr_t)hist & 15) == 0, "multistep solver: the history must be 16-byte aligned and not empty");
+    for (int i = 0; i < n_steps; ++i) REQUIRE(std::isfinite(kappa_host[i]), "multistep solver: kappa must be finite");
+    Multistep& m = h->ms_armed;
+    m.kappa.assign(kappa_host, kappa_host + n_steps); m.hist = hist; m.hist_floats = hist_floats;
     return 0;
 }

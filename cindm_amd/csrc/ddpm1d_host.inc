@@ -14,8 +14,8 @@
 //   ddim_tables1               the DDIM preamble: per-step tables into the workspace's slice
 //   loop_steps, loop_chain     the unguided loop and the chain that is one such loop
 //   guided_step, guided_chain  the recurrence iterations of a guided step and the guided chains' tail
-// An entry is: RecScope, DesignTablesScope, Known2DScope, Known1DScope, QuadTablesScope, Chain1D, refusals, rec_begin, known1_begin, chain_stream, (DDIM:
-// ddim_tables1,) chain_io plus what it adds, and one call of loop_chain, guided_chain or its own body (the rollout).
+// An entry is: RecScope, DesignTablesScope, Known2DScope, Known1DScope, QuadTablesScope, MultistepScope, Chain1D, refusals, rec_begin, known1_begin,
+// (DDIM: ms_begin,) chain_stream, (DDIM: ddim_tables1,) chain_io plus what it adds, and one call of loop_chain, guided_chain or its own body (the rollout).
 
 extern "C" int cindm_ddpm1d_create(const cindm_sched_desc* d, cindm_ddpm1d** out) {
     REQUIRE(d && out && d->timesteps > 0, "bad schedule descriptor");
@@ -183,6 +183,7 @@ struct StepIO {
     int rec;                // recorded chain: the recorder's stream mask on the call that ends a step (chain_record_kernel follows it), else 0
     int kn, relax_idx;      // chain with a known region: known1d_kernel follows every update; the relaxation's index (a constant of the captured iteration)
     const TimeComposeArgs* tc;     // parallel time composition (timecompose_host.inc): its update kernel's own operands, or null
+    float* ms_hist;         // DDIM chain with the multistep solver: the history its update reads and writes (kappa rides in the table rows), or null
 };
 
 // What a step refuses of its Chain1D and state (x, and cond where the descriptor prepends it): run_step's own checks
@@ -331,7 +332,7 @@ static int run_step(const Chain1D& ch, const StepIO& io, int32_t t, const int32_
     // the plain one (the bitwise identities outside(mean) == inside == plain are GPU tests) and all of them fuse.
     const bool can_fuse = c->mode >= CINDM_COMPOSE_PLAIN && c->mode <= 4 && s.direct && !s.single_rows && !guided && (!io.ddim_tab || c->objective == 0) &&
                           io.x_out == io.x && !io.mean_out && !io.x0_out && !io.eps_out && !io.inp_cond && pair->O("fuse_update") &&
-                          (a.F & 3) == 0;
+                          (a.F & 3) == 0 && !io.ms_hist;
     pair->fused_done = false;
     pair->fuse_upd = can_fuse ? &a : nullptr;
     const int frc = cindm_unet1d_forward(pair, unet_in, t, t_dev, ch.pair_eps(), s.pair_rows, ch.ws_pair(), ch.ws_pair_bytes(), stream);
@@ -354,6 +355,10 @@ static int run_step(const Chain1D& ch, const StepIO& io, int32_t t, const int32_
         TimeComposeArgs u = *io.tc;
         u.c = a;
         hipLaunchKernelGGL(timecompose_update_kernel, dim3((unsigned)((ne / 4 + 255) / 256)), dim3(256), 0, stream, u);
+    } else if (io.ms_hist && io.ddim_tab && !(guided && io.relax)) {
+        // the multistep solver's update (never fused; a relaxation iteration is not an update and keeps the kernels below)
+        if ((a.dz_mode & kDzModeMask) == 5) hipLaunchKernelGGL(compose_update_ms_quad_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a, io.ms_hist);
+        else hipLaunchKernelGGL(compose_update_ms_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a, io.ms_hist);
     } else if ((a.dz_mode & kDzModeMask) == 5) {      // (guided: never fused)
         hipLaunchKernelGGL(compose_update_quad_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a);
     } else if (!pair->fused_done) hipLaunchKernelGGL(compose_update_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a);
@@ -559,6 +564,9 @@ static int run_chain_with_recovery(const Chain1D& ch, float* x, Body body) {
     if (!pair->O("recover") || (uncond && !uncond->O("recover")))
         return fail("an in-kernel exchange between workgroups timed out (foreign load on the device kept a partner workgroup from becoming "
                     "resident); option recover = 0: the chain is not re-run");
+    if (h->ms && h->ms->kappa[0] != 0.f)
+        return fail("an in-kernel exchange between workgroups timed out, and the chain's first step reads a multistep history that the run "
+                    "has overwritten: restore the history and call again");
     HIPCHK(hipMemcpyAsync(x, ch.xT(), bytes, hipMemcpyDeviceToDevice, stream));
     pair->no_xchg_force = 1; ++pair->recovered;
     if (uncond) { uncond->no_xchg_force = 1; ++uncond->recovered; }
@@ -593,6 +601,7 @@ static void key_common(KeyBuilder& K, int kind, const Chain1D& ch, const StepIO&
         const Known1D& k = *ch.h->kn1;
         K(io.kn)(k.known)(k.mask)(k.known_per_design)(k.mask_per_design)(k.z_step)(k.step_stride)(k.z_recur)(k.recur_stride);
     }
+    if (io.ms_hist) ms_key(K, ch.h);      // multistep solver: the history is an operand of the captured update
 }
 
 // the StepIO fields every sample loop sets the same way: in-place state, per-step tapes (or the counter noise keyed in device
@@ -614,8 +623,10 @@ static StepIO chain_io(const Chain1D& ch, float* x, const float* cond, const flo
 // timestep: chain1_refuse has bounded n_steps by that) and io reads them from there.
 static int ddim_tables1(const Chain1D& ch, const Ddim1Call& dd, StepIO& io) {
     int* tn_dev = nullptr;
-    if (upload_ddim_tables(ch.h->T, dd.n_steps, dd.times, dd.coefs, ch.ddim_tab(), ch.stream, &tn_dev) != 0) return -1;
-    io.ddim_tab = ch.ddim_tab(); io.ddim_tnext = tn_dev;
+    // (a chain that took the multistep solver: kappa rides in the rows' fourth word, which is free in 1-D)
+    const Multistep* ms = ch.h->ms;
+    if (upload_ddim_tables(ch.h->T, dd.n_steps, dd.times, dd.coefs, ch.ddim_tab(), ch.stream, &tn_dev, ms ? ms->kappa.data() : nullptr) != 0) return -1;
+    io.ddim_tab = ch.ddim_tab(); io.ddim_tnext = tn_dev; io.ms_hist = ms ? ms->hist : nullptr;
     return 0;
 }
 
@@ -707,9 +718,10 @@ extern "C" int cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_un
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    MultistepScope ms(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
-    if (dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0) return -1;
+    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0) return -1;
     if (rec_begin(rs, x, nsteps, ch.n_state()) != 0 || known1_begin(k1, ch, x, 0) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     const StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
@@ -726,11 +738,12 @@ extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cin
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    MultistepScope ms(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
     if (dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, &dd) != 0) return -1;
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    if (rec_begin(rs, x, n_steps, ch.n_state()) != 0 || known1_begin(k1, ch, x, 0) != 0) return -1;
+    if (rec_begin(rs, x, n_steps, ch.n_state()) != 0 || known1_begin(k1, ch, x, 0) != 0 || ms_begin(ms, n_steps, coefs, ch.n_state(), x) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     if (ddim_tables1(ch, dd, io) != 0) return -1;
@@ -753,9 +766,10 @@ extern "C" int cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pa
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    MultistepScope ms(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
-    if (dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || known2_refuse(ks) != 0) return -1;
+    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || known2_refuse(ks) != 0) return -1;
     if (known1_refuse(k1, "the autoregressive rollout draws a fresh state per segment and hands rows over between segments: a region of "
                           "one [B, rows, F] state does not name a place in it") != 0) return -1;
     REQUIRE(!rs.on(), "recorder: the autoregressive rollout is not recorded (its step index is (segment, step)); the recorder was dropped");
@@ -811,8 +825,9 @@ extern "C" int cindm_ddpm1d_sample_ula(cindm_ddpm1d* h, cindm_unet1d* pair, cind
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    MultistepScope ms(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
-    if (dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || known2_refuse(ks) != 0) return -1;
+    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || known2_refuse(ks) != 0) return -1;
     if (known1_refuse(k1, "the Langevin chain moves the whole state, conditioning rows included, at one noise level per timestep without a "
                           "reverse update: the region's forward-diffusion trajectory is not defined for it") != 0) return -1;
     REQUIRE(!rs.on(), "recorder: the Langevin chain is not recorded (its step index is (timestep, inner iteration)); the recorder was dropped");
@@ -853,9 +868,10 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    MultistepScope ms(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
-    if (known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0 || guided_refuse(ch, ts, qs, dz, x, 0, initial_state_overwrite, overwrite_steps) != 0) return -1;
+    if (ms_refuse(ms) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0 || guided_refuse(ch, ts, qs, dz, x, 0, initial_state_overwrite, overwrite_steps) != 0) return -1;
     if (rec_begin(rs, x, nsteps, ch.n_state()) != 0 || known1_begin(k1, ch, x, std::max(dz->recurrence, 1)) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
@@ -883,12 +899,14 @@ extern "C" int cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pa
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    MultistepScope ms(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
     if (known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, &dd) != 0 || guided_refuse(ch, ts, qs, dz, x, 1, initial_state_overwrite, overwrite_steps) != 0) return -1;
     REQUIRE(!inpaint_cond || (inpaint_steps >= 1 && inpaint_steps <= ch.Ltot()), "bad inpaint_steps");
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    if (rec_begin(rs, x, n_steps, ch.n_state()) != 0 || known1_begin(k1, ch, x, dz->recurrence) != 0) return -1;
+    if (rec_begin(rs, x, n_steps, ch.n_state()) != 0 || known1_begin(k1, ch, x, dz->recurrence) != 0 ||
+        ms_begin(ms, n_steps, coefs, ch.n_state(), x, ch.stage()) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     if (ddim_tables1(ch, dd, io) != 0) return -1;

@@ -11,7 +11,9 @@
 //   known2_begin, known2_node  the known region of a chain (cindm_ddpm1d_set_known2d): its check against the state, and its launch
 //   ddpm_step2, ddim_step2     the captured step: [gradient,] step, [shift,] [known node,] [record node]
 //   run_chain2                 the tail: counter, rec_arm, [known node: rule 1,] replay -- under force_chain_with_recovery when guided -- and rec_done
-// An entry is: RecScope, Known2DScope, refusals, rec_begin2, known2_begin, chain_stream, (DDIM: upload_ddim_tables,) build the step, run_chain2.
+//   ms_begin2, ms_tables2      the multistep solver of a DDIM chain (cindm_ddpm1d_set_multistep): its checks, and kappa behind the caller's tables
+// An entry is: RecScope, Known2DScope, Known1DScope, QuadTablesScope, MultistepScope, refusals, (DDIM: ms_begin2,) rec_begin2, known2_begin, chain_stream,
+// (DDIM: upload_ddim_tables, ms_tables2,) build the step, run_chain2.
 
 // Returns the bytes of a diffusion workspace for `images` images; the offsets of its second and third slice go to *o_unet / *o_xT.
 // The x_T snapshot serves the guided chains' recovery (force_chain_with_recovery): no allocation after *_create.
@@ -217,12 +219,36 @@ static Ddim2dArgs ddim_args2(const Chain2D& ch, float* x, const Ddim2dCall& dd, 
     return a;
 }
 
+// The multistep solver of a 2-D DDIM chain: the fourth word of a table row carries the guidance weight here, so kappa is a table of
+// its own behind the rows and the next-times (a sixth word per step of the caller's buffer).  *kappa_dev stays null without it.
+static int ms_tables2(const Chain2D& ch, const Ddim2dCall& dd, const float** kappa_dev) {
+    *kappa_dev = nullptr;
+    const Multistep* m = ch.s->ms;
+    if (!m) return 0;
+    float* dst = (float*)dd.tab + (size_t)dd.n_steps * 5;
+    HIPCHK(hipMemcpyAsync(dst, m->kappa.data(), m->kappa.size() * sizeof(float), hipMemcpyHostToDevice, ch.stream));
+    HIPCHK(hipStreamSynchronize(ch.stream));
+    *kappa_dev = dst;
+    return 0;
+}
+
+// what a 2-D DDIM entry checks of an armed multistep solver, after chain2_refuse
+static int ms_begin2(MultistepScope& ms, const Chain2D& ch, const Ddim2dCall& dd, const float* x) {
+    if (!ms.on()) return 0;
+    REQUIRE(dd.tab_bytes >= (size_t)dd.n_steps * 6 * sizeof(float), "multistep solver: the DDIM table buffer needs 6 words per step (24 bytes)");
+    REQUIRE(((uintptr_t)x & 15) == 0, "multistep solver: the state x must be 16-byte aligned");
+    return ms_begin(ms, dd.n_steps, dd.coefs, ch.state_floats(), x);
+}
+
 // One DDIM step of the 2-D path (ddim_sample; DESIGN 4.5g): the U-Net + ddim2d_update_kernel + step_counter_kernel (t and the step
 // index advance on the device from the time_next table).  With grad, the update is ddim2d_guided_update_kernel, which carries the
 // guidance shift (DESIGN 4.5k).
-static int run_ddim_step2(const Chain2D& ch, const Ddim2dArgs& a, const float* grad = nullptr) {
+// kappa (device, [n_steps]) and hist: the multistep solver's operands (DESIGN 4.5r), or null: its forms of the two update kernels.
+static int run_ddim_step2(const Chain2D& ch, const Ddim2dArgs& a, const float* grad = nullptr, const float* kappa = nullptr, float* hist = nullptr) {
     if (cindm_unet2d_forward(ch.u, a.x, 0, ch.s->t_dev, ch.eps(), ch.NI(), ch.unet_ws(), ch.unet_ws_bytes(), ch.stream) != 0) return -1;
-    if (grad) hipLaunchKernelGGL(ddim2d_guided_update_kernel, dim3(ch.update_blocks()), dim3(256), 0, ch.stream, a, grad);
+    if (kappa && grad) hipLaunchKernelGGL(ddim2d_ms_update_kernel<true>, dim3(ch.update_blocks()), dim3(256), 0, ch.stream, a, grad, kappa, hist);
+    else if (kappa) hipLaunchKernelGGL(ddim2d_ms_update_kernel<false>, dim3(ch.update_blocks()), dim3(256), 0, ch.stream, a, (const float*)nullptr, kappa, hist);
+    else if (grad) hipLaunchKernelGGL(ddim2d_guided_update_kernel, dim3(ch.update_blocks()), dim3(256), 0, ch.stream, a, grad);
     else hipLaunchKernelGGL(ddim2d_update_kernel, dim3(ch.update_blocks()), dim3(256), 0, ch.stream, a);
     hipLaunchKernelGGL(step_counter_kernel, dim3(1), dim3(64), 0, ch.stream, ch.s->t_dev, a.tnext, (int*)nullptr, (int*)nullptr);
     HIPCHK(hipGetLastError());
@@ -256,10 +282,11 @@ static auto ddpm_step2(const Chain2D& ch, const Step2IO& io, float* x, const For
 //     x' = the DDIM update of x_t           (Unet forward + the unguided chain's update, the same draws)
 //     x_next = x' - weights[i] * g          (in the same launch: ddim2d_guided_update_kernel)
 // weights ride in the 4th word of the caller's per-step table rows.
-static auto ddim_step2(const Chain2D& ch, const Ddim2dArgs& a, float* x, const ForceGuide* g = nullptr) {
+static auto ddim_step2(const Chain2D& ch, const Ddim2dArgs& a, float* x, const ForceGuide* g = nullptr, const float* kappa = nullptr,
+                       float* hist = nullptr) {
     return [=](int) -> int {
         if (g && g->gradient(ch, x) != 0) return -1;
-        if (run_ddim_step2(ch, a, g ? g->grad : nullptr) != 0) return -1;
+        if (run_ddim_step2(ch, a, g ? g->grad : nullptr, kappa, hist) != 0) return -1;
         if (ch.s->kn && known2_node(ch, x, 0) != 0) return -1;
         return ch.s->rec ? rec_node(ch.s, x, 0, ch.stream) : 0;
     };
@@ -283,6 +310,9 @@ static int force_chain_with_recovery(const Chain2D& ch, cindm_forceunet* f, floa
     if (st == 0) return 0;
     if (!f->O("recover")) return fail("an in-kernel exchange of the surrogate's GroupNorm derivative timed out (foreign load on the device); "
                                       "option recover = 0: not re-run");
+    if (ch.s->ms && ch.s->ms->kappa[0] != 0.f)
+        return fail("an in-kernel exchange of the surrogate's GroupNorm derivative timed out, and the chain's first step reads a multistep "
+                    "history that the run has overwritten: restore the history and call again");
     HIPCHK(hipMemcpyAsync(x, ch.xT(), bytes, hipMemcpyDeviceToDevice, ch.stream));
     f->nx_force = 1; ++f->recovered;
     const int rc2 = chain();
@@ -313,12 +343,13 @@ extern "C" int cindm_ddpm2d_sample(cindm_ddpm1d* s, cindm_unet2d* u, float* x, i
     Known2DScope ks(s);
     Known1DScope k1(s);
     QuadTablesScope qs(s);
+    MultistepScope ms(s);
     if (qdt_refuse(qs) != 0) return -1;
     if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
                           "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
-    if (chain2_refuse(ch, x, nullptr, t_start, t_end) != 0) return -1;
+    if (ms_refuse(ms) != 0 || chain2_refuse(ch, x, nullptr, t_start, t_end) != 0) return -1;
     const Draws2 z{noise_state_steps, noise_boundary_steps, seed, sample_offset};
     if (rec_begin2(rs, ch, x, nsteps) != 0 || known2_begin(ks, ch, x, z) != 0) return -1;
     if (chain_stream(s, stream_, use_graph, &ch.stream) != 0) return -1;
@@ -334,21 +365,24 @@ extern "C" int cindm_ddpm2d_sample_ddim(cindm_ddpm1d* s, cindm_unet2d* u, float*
     Known2DScope ks(s);
     Known1DScope k1(s);
     QuadTablesScope qs(s);
+    MultistepScope ms(s);
     if (qdt_refuse(qs) != 0) return -1;
     if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
                           "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const Ddim2dCall dd{n_steps, times, coefs, nullptr, tab, tab_bytes};
-    if (chain2_refuse(ch, x, &dd) != 0) return -1;
+    if (chain2_refuse(ch, x, &dd) != 0 || ms_begin2(ms, ch, dd, x) != 0) return -1;
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     const Draws2 z{noise_state_steps, noise_boundary_steps, seed, sample_offset};
     if (rec_begin2(rs, ch, x, n_steps, kNoX0Ddim2d) != 0 || known2_begin(ks, ch, x, z) != 0) return -1;
     if (chain_stream(s, stream_, use_graph, &ch.stream) != 0) return -1;
     int* tn_dev = nullptr;      // the per-step tables go to the caller's device buffer
     if (upload_ddim_tables(s->T, n_steps, times, coefs, (float*)tab, ch.stream, &tn_dev) != 0) return -1;
+    const float* kappa_dev = nullptr;
+    if (ms_tables2(ch, dd, &kappa_dev) != 0) return -1;
     ks.k.tnext = tn_dev;
     const Ddim2dArgs a = ddim_args2(ch, x, dd, tn_dev, z);
-    return run_chain2(rs, ch, nullptr, x, times[0], true, n_steps, ddim_step2(ch, a, x));
+    return run_chain2(rs, ch, nullptr, x, times[0], true, n_steps, ddim_step2(ch, a, x, nullptr, kappa_dev, kappa_dev ? ms.m.hist : nullptr));
 }
 
 // Design-guided 2-D sampling with the airfoil objective INSIDE the captured step (ddpm_step2)
@@ -363,13 +397,14 @@ extern "C" int cindm_ddpm2d_sample_force(cindm_ddpm1d* s, cindm_unet2d* u, cindm
     Known2DScope ks(s);
     Known1DScope k1(s);
     QuadTablesScope qs(s);
+    MultistepScope ms(s);
     if (qdt_refuse(qs) != 0) return -1;
     if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
                           "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const ForceGuide g{f, frames, p_min, p_max, lambda_force, lambda_overlap, down_factor, sum_boundary, grad, ws_force, ws_force_bytes};
     const int nsteps = t_start - t_end + 1;
-    if (chain2_refuse(ch, x, nullptr, t_start, t_end) != 0 || force_refuse(ch, g, x, eta) != 0) return -1;
+    if (ms_refuse(ms) != 0 || chain2_refuse(ch, x, nullptr, t_start, t_end) != 0 || force_refuse(ch, g, x, eta) != 0) return -1;
     const Draws2 z{noise_state_steps, noise_boundary_steps, seed, sample_offset};
     if (rec_begin2(rs, ch, x, nsteps) != 0 || known2_begin(ks, ch, x, z) != 0) return -1;
     if (chain_stream(s, stream_, use_graph, &ch.stream) != 0) return -1;
@@ -389,20 +424,23 @@ extern "C" int cindm_ddpm2d_sample_ddim_force(cindm_ddpm1d* s, cindm_unet2d* u, 
     Known2DScope ks(s);
     Known1DScope k1(s);
     QuadTablesScope qs(s);
+    MultistepScope ms(s);
     if (qdt_refuse(qs) != 0) return -1;
     if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
                           "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const Ddim2dCall dd{n_steps, times, coefs, weights, tab, tab_bytes};
     const ForceGuide g{f, frames, p_min, p_max, lambda_force, lambda_overlap, down_factor, sum_boundary, grad, ws_force, ws_force_bytes};
-    if (chain2_refuse(ch, x, &dd) != 0 || force_refuse(ch, g, x, weights) != 0) return -1;
+    if (chain2_refuse(ch, x, &dd) != 0 || force_refuse(ch, g, x, weights) != 0 || ms_begin2(ms, ch, dd, x) != 0) return -1;
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     const Draws2 z{noise_state_steps, noise_boundary_steps, seed, sample_offset};
     if (rec_begin2(rs, ch, x, n_steps, kNoX0Ddim2d) != 0 || known2_begin(ks, ch, x, z) != 0) return -1;
     if (chain_stream(s, stream_, use_graph, &ch.stream) != 0) return -1;
     int* tn_dev = nullptr;
     if (upload_ddim_tables(s->T, n_steps, times, coefs, (float*)tab, ch.stream, &tn_dev, weights) != 0) return -1;
+    const float* kappa_dev = nullptr;
+    if (ms_tables2(ch, dd, &kappa_dev) != 0) return -1;
     ks.k.tnext = tn_dev;
     const Ddim2dArgs a = ddim_args2(ch, x, dd, tn_dev, z);
-    return run_chain2(rs, ch, &g, x, times[0], true, n_steps, ddim_step2(ch, a, x, &g));
+    return run_chain2(rs, ch, &g, x, times[0], true, n_steps, ddim_step2(ch, a, x, &g, kappa_dev, kappa_dev ? ms.m.hist : nullptr));
 }

@@ -3561,8 +3561,11 @@ __global__ void compose_gather_kernel(const ComposeArgs a) {
 
 // One thread per state element (b, l, f) of the FULL sequence (cond rows skipped on output).
 // kQuad: the guided branch evaluates the quadratic objective (dz_mode 5) on all four components of a body; false: every other mode.
-template <bool kQuad>
-__device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_t i) {
+// kMulti: the DDIM update carries the second-order multistep term: v = v + kappa (x0 - hist[i]) with kappa = the 4th word
+// of the step's table row, each operation rounded once, ahead of the inpainting overwrite; kappa == 0 does not read the history; the
+// update -- never a relaxation iteration -- writes x0 to hist[i].  One thread reads and writes one element: in place is safe.
+template <bool kQuad, bool kMulti = false>
+__device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_t i, float* hist = nullptr) {
     const int Lfull = a.Ltot + a.cond_steps;
     const int t = step_scalar(a.t_ptr, a.t_imm);
     const int sidx = a.ddim_tab ? *a.step_idx : 0;
@@ -3742,6 +3745,10 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
                 const float z = a.noise ? a.noise[(size_t)sidx * a.noise_t_stride + i]
                                 : (sg != 0.f ? counter_normal(dseed, (uint64_t)(dsoff + b), (uint32_t)t, el) : 0.f);
                 v = __fadd_rn(__fadd_rn(__fmul_rn(x0, san), __fmul_rn(cc, epsd)), __fmul_rn(sg, z));
+                if constexpr (kMulti) {
+                    const float kap = a.ddim_tab[4 * sidx + 3];
+                    if (kap != 0.f) v = __fadd_rn(v, __fmul_rn(kap, __fsub_rn(x0, hist[i])));
+                }
                 if (a.inp_cond && lx < a.inp_steps) {      // inpainting overwrite with q_sample(cond, time) (:1790-1793)
                     const size_t ci = ((size_t)b * a.inp_steps + lx) * a.F + f;
                     const float z2 = a.inp_noise ? a.inp_noise[(size_t)sidx * a.inp_noise_t_stride + ci]
@@ -3749,6 +3756,7 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
                     v = a.sqrt_ac[t] * a.inp_cond[ci] + a.sqrt_1mac[t] * z2;
                 }
             }
+            if constexpr (kMulti) hist[i] = x0;
         } else {
             v = pred;
             if (a.add_noise && t > 0) {
@@ -3774,6 +3782,10 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
             const float z = a.noise ? a.noise[(size_t)sidx * a.noise_t_stride + i]
                             : (sg != 0.f ? counter_normal(dseed, (uint64_t)(dsoff + b), (uint32_t)t, el) : 0.f);
             v = __fadd_rn(__fadd_rn(__fmul_rn(x0, san), __fmul_rn(cc, eps)), __fmul_rn(sg, z));
+            if constexpr (kMulti) {
+                const float kap = a.ddim_tab[4 * sidx + 3];
+                if (kap != 0.f) v = __fadd_rn(v, __fmul_rn(kap, __fsub_rn(x0, hist[i])));
+            }
             if (a.inp_cond && lx < a.inp_steps) {      // inpainting overwrite with q_sample(cond, time) (:1790-1793)
                 const size_t ci = ((size_t)b * a.inp_steps + lx) * a.F + f;
                 const float z2 = a.inp_noise ? a.inp_noise[(size_t)sidx * a.inp_noise_t_stride + ci]
@@ -3781,6 +3793,7 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
                 v = a.sqrt_ac[t] * a.inp_cond[ci] + a.sqrt_1mac[t] * z2;
             }
         }
+        if constexpr (kMulti) hist[i] = x0;
         a.x_out[i] = v;
     } else if (a.x_out) {
         float v = mean;
@@ -3811,6 +3824,16 @@ __global__ void compose_update_kernel(const ComposeArgs a) {
 // it was (DESIGN 4.5q has both kernels' resource usage)
 __global__ void compose_update_quad_kernel(const ComposeArgs a) {
     compose_update_body<true>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// the DDIM updates of a chain that runs the second-order multistep solver: instantiations of their own, so that the two
+// kernels above are the code they were.  Launched for a step's update only -- a guided step's relaxation iterations keep the kernels
+// above and leave the history alone -- and never fused into ups_last_kernel.
+__global__ void compose_update_ms_kernel(const ComposeArgs a, float* hist) {
+    compose_update_body<false, true>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, hist);
+}
+__global__ void compose_update_ms_quad_kernel(const ComposeArgs a, float* hist) {
+    compose_update_body<true, true>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, hist);
 }
 
 // ---------------------------------------------------------------------------------------------

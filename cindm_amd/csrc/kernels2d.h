@@ -3017,6 +3017,97 @@ __global__ __launch_bounds__(256) void ddim2d_guided_update_kernel(const Ddim2dA
     }
 }
 
+// The multistep forms of ddim2d_update_kernel (kGuided false) and ddim2d_guided_update_kernel (true): the same update,
+// and the second-order term v = v + kappa (x0 - hist) on the DDIM value -- each operation rounded once, ahead of the guidance shift --
+// with kappa = kappa_tab[step index]; kappa == 0 does not read the history, the last pair (time_next < 0) returns x0 and reads
+// none either.  Every step writes its x0 to hist, a buffer in the layout of x (padded channels: 0).  One more 16-byte load and one
+// more 16-byte store per element group, no second pass; a thread reads and writes only its own element groups of hist, as of x.
+// Kernels of their own, so that the two above are the code they were.
+template <bool kGuided>
+__global__ __launch_bounds__(256) void ddim2d_ms_update_kernel(const Ddim2dArgs a, const float* __restrict__ grad,
+                                                               const float* __restrict__ kappa_tab, float* __restrict__ hist) {
+    const int G = a.CP >> 2;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int t = uniform_word(a.t_dev);
+    const int sidx = uniform_word(a.t_dev + 2);
+    const int total = a.B * a.HW * G;
+    if (i >= total) return;
+    const int g = i % G;
+    const int bp = i / G;
+    const int pix = bp % a.HW;
+    const int b = bp / a.HW;
+    const int c0 = 4 * g, Cs = a.C - 3;
+    const int tn = uniform_word(a.tnext + sidx);
+    const float san = uniform_float(a.tab + 4 * sidx), cc = uniform_float(a.tab + 4 * sidx + 1), sg = uniform_float(a.tab + 4 * sidx + 2);
+    const float wg = kGuided ? uniform_float(a.tab + 4 * sidx + 3) : 0.f;
+    const float kap = tn >= 0 ? uniform_float(kappa_tab + sidx) : 0.f;
+    const float ra = a.sqrt_recip[t], rb = a.sqrt_recipm1[t];
+    const int obj = (a.use_avg >> 4) & 3;
+    const float sa = obj == 2 ? a.sqrt_ac[t] : 0.f, sm = obj == 2 ? a.sqrt_1mac[t] : 0.f;
+    const bool avg = (a.use_avg & 1) != 0;
+    const bool draws = tn >= 0 && (a.noise_state != nullptr || sg != 0.f);
+    float es[4] = {0.f, 0.f, 0.f, 0.f};
+    if (obj == 0 && c0 < Cs) {
+        for (int k = 0; k < a.nb; ++k) {
+            const float4 e = *reinterpret_cast<const float4*>(a.eps + (((size_t)(b * a.nb + k) * a.HW) + pix) * a.CP + c0);
+            es[0] += e.x; es[1] += e.y; es[2] += e.z; es[3] += e.w;
+        }
+        if (avg) { const float inv = (float)a.nb; es[0] /= inv; es[1] /= inv; es[2] /= inv; es[3] /= inv; }
+    }
+    float zs[4] = {0.f, 0.f, 0.f, 0.f};
+    if (draws && c0 < Cs) {
+        if (a.noise_state) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (c0 + j < Cs) zs[j] = a.noise_state[(size_t)sidx * a.ns_t_stride + ((size_t)b * a.HW + pix) * Cs + c0 + j];
+        } else {
+            noise2d_state4(a.seed, a.sample_off + b, (uint32_t)t, (uint32_t)pix, G, g, zs);
+        }
+    }
+    for (int k = 0; k < a.nb; ++k) {
+        const int im = b * a.nb + k;
+        const size_t o = (((size_t)im * a.HW) + pix) * a.CP + c0;
+        const float4 e4 = *reinterpret_cast<const float4*>(a.eps + o);
+        const float4 x4 = *reinterpret_cast<const float4*>(a.x + o);
+        float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f), h4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (kGuided) g4 = *reinterpret_cast<const float4*>(grad + o);
+        if (kap != 0.f) h4 = *reinterpret_cast<const float4*>(hist + o);
+        const float ev[4] = {e4.x, e4.y, e4.z, e4.w}, xv[4] = {x4.x, x4.y, x4.z, x4.w}, gv[4] = {g4.x, g4.y, g4.z, g4.w};
+        const float hv[4] = {h4.x, h4.y, h4.z, h4.w};
+        float zb[4] = {0.f, 0.f, 0.f, 0.f};
+        if (draws && c0 + 3 >= Cs && c0 < a.C) {
+            if (a.noise_bound) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (c0 + j >= Cs && c0 + j < a.C)
+                        zb[j] = a.noise_bound[(size_t)sidx * a.nb_t_stride + ((size_t)im * a.HW + pix) * 3 + (c0 + j - Cs)];
+            } else {
+                noise2d_bound4(a.seed, (a.sample_off + b) * a.nb + k, (uint32_t)t, (uint32_t)pix, G, g, zb);
+            }
+        }
+        float r[4], xs[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = c0 + j;
+            const float e = (obj == 0 && c < Cs) ? es[j] : ev[j];
+            const float x0 = clamp_pm1(obj == 0 ? __fsub_rn(__fmul_rn(ra, xv[j]), __fmul_rn(rb, e)) : obj == 1 ? e
+                                                : __fsub_rn(__fmul_rn(sa, xv[j]), __fmul_rn(sm, e)));
+            const float er = __fsub_rn(__fmul_rn(ra, xv[j]), x0) / rb;
+            float v = x0;
+            if (tn >= 0) {
+                v = __fadd_rn(__fmul_rn(x0, san), __fmul_rn(cc, er));
+                if (draws) v = __fadd_rn(v, __fmul_rn(sg, c < Cs ? zs[j] : zb[j]));
+                if (kap != 0.f) v = __fadd_rn(v, __fmul_rn(kap, __fsub_rn(x0, hv[j])));
+            }
+            if constexpr (kGuided) v = __fsub_rn(v, __fmul_rn(wg, gv[j]));
+            r[j] = c < a.C ? v : 0.f;
+            xs[j] = c < a.C ? x0 : 0.f;
+        }
+        *reinterpret_cast<float4*>(hist + o) = make_float4(xs[0], xs[1], xs[2], xs[3]);
+        *reinterpret_cast<float4*>(a.x_out + o) = make_float4(r[0], r[1], r[2], r[3]);
+    }
+}
+
 // x_T for the 2-D path from the counter-based generator (state channels shared over the boundaries of a design)
 __global__ void fill_noise2d_kernel(float* x, int B, int nb, int HW, int C, int CP, uint64_t seed, int64_t off, uint32_t tag) {
     const int G = CP >> 2;

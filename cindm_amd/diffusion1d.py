@@ -35,7 +35,7 @@ from . import _ffi
 from .diffusion_base import DiffusionHandle
 from .objectives import PointObjective, QuadraticObjective, WaypointObjective
 from .record import DeviceRecorder, LoopRecorder, record_schedule, stream_mask
-from .schedule import make_schedule, ula_schedule
+from .schedule import check_solver, make_schedule, ula_schedule
 
 ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"])
 
@@ -671,7 +671,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
 
     @torch.no_grad()
     def _run_guided_ddim(self, img, cond, desc, dz, times, coefs, *, noise, seed, sample_offset, inpaint_cond,
-                         initial_state_overwrite, use_graph=True, rec=None, tables=None, karm=None):
+                         initial_state_overwrite, use_graph=True, rec=None, tables=None, karm=None, ms=None):
         """DDIM steps ``times[0] .. times[-2]`` guided by the built-in objective as one library call
         (cindm_ddpm1d_sample_ddim_guided); ``noise`` rows (step / recur / cond) are indexed by the position in ``times``.
         ``tables``: as _run_guided_loop."""
@@ -687,6 +687,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
             self._arm(rec, h)
             self._arm_tables(tables, h, img)
             self._arm_known(karm, h)
+            self._arm_multistep(ms, h)
             with torch.cuda.device(device):
                 _ffi.check(_ffi.lib().cindm_ddpm1d_sample_ddim_guided(
                     h, self.model._h, un, C.byref(desc), C.byref(dz), _ffi.ptr(img), _ffi.ptr(cond_d), S, tarr, _ffi.ptr(carr),
@@ -713,7 +714,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
     def p_sample_loop(self, shape, cond, n_composed=0, compose_start_step=4, compose_n_bodies=2, compose_mode="mean",
                       design_fn=None, design_guidance="standard", initial_state_overwrite=None, initialization_mode=0,
                       initialization_img=None, *, noise=None, seed=None, sample_offset=0, use_graph=True, t_stop=0,
-                      return_trajectory_every=None, trajectory=("x",), known=None, known_mask=None):
+                      return_trajectory_every=None, trajectory=("x",), known=None, known_mask=None, solver="ddim"):
         """:1656-1720.  Build-only keywords: ``noise`` (NoiseTape, explicit draws), ``seed`` /
         ``sample_offset`` (counter-based generator keyed by global sample index), ``t_stop`` (truncate),
         ``return_trajectory_every=k`` with ``trajectory=("x",)`` / ``("x", "x0")``: returns (designs, ChainRecord) with the state after
@@ -725,7 +726,11 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         itself after t = 0), so it comes back exactly; z per element from the tape's ``known_init`` / ``known_step[t]`` /
         ``known_recur[t][r]``, else counter-based under a seed word of its own.  The region overwrites last and may not touch rows
         that ``cond`` inpainting or ``initial_state_overwrite`` claim (ValueError).  Inside the captured step on the library routes
-        (known1d_kernel), ``known_replace`` on the route that loops in Python; a recorder's x stream is taken after the overwrite."""
+        (known1d_kernel), ``known_replace`` on the route that loops in Python; a recorder's x stream is taken after the overwrite.
+        ``solver``: "ddim" (nothing changes); "dpmpp-2m" is a ValueError here -- this is the DDPM chain (see ddim_sample)."""
+        if check_solver(self, solver):
+            raise ValueError("solver='dpmpp-2m' runs on the DDIM chains: p_sample_loop is the DDPM chain (sample() with "
+                             "sampling_timesteps < timesteps, or ddim_sample)")
         full = (shape[0], shape[1] + n_composed * compose_start_step, compose_n_bodies * 4)
         fast = design_fn is None and "recurrence" not in design_guidance and initial_state_overwrite is None
         iters = max(int(design_guidance.split("-")[-1]) if "recurrence" in design_guidance else 0, 1)
@@ -809,7 +814,9 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
                compose_n_bodies=2, compose_mode="mean", design_fn=None, design_guidance="standard",
                initial_state_overwrite=None, initialization_mode=0, initialization_img=None, **build_kw):
         """:2330-2376.  ``build_kw``: noise=, seed=, sample_offset=, use_graph=, t_stop=, return_trajectory_every=, trajectory=,
-        known=, known_mask= (see p_sample_loop; the known region is held by the DDPM and the DDIM route alike)."""
+        known=, known_mask= (see p_sample_loop; the known region is held by the DDPM and the DDIM route alike), solver= ("ddim" |
+        "dpmpp-2m", see ddim_sample)."""
+        check_solver(self, build_kw.get("solver", "ddim"))
         self.is_ddim_sampling = self.sampling_timesteps < self.num_timesteps
         if self.is_ddim_sampling:               # :2348-2363
             build_kw.pop("t_stop", None)
@@ -904,7 +911,8 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
 
     @torch.no_grad()
     def sample_compose_multibodies(self, cond, N, L, n_bodies, *, noise=None, seed=None, sample_offset=0,
-                                   use_graph=True, t_stop=0, full_state=False, return_trajectory_every=None, trajectory=("x",)):
+                                   use_graph=True, t_stop=0, full_state=False, return_trajectory_every=None, trajectory=("x",),
+                                   solver="ddim"):
         """:1986-2042: x = cat(cond, noise); for i = N-1 .. 401: L Langevin iterations on the whole x (``sample_step_ULA``, the
         conditioning rows drift too); for i = 400 .. 0: x[:, cs:] = p_sample(x[:, cs:], x[:, :cs], i).  Returns
         [B, rollout_steps, 4*n_bodies].  N <= 401 has no Langevin phase (L and n_bodies are not looked at, as before).
@@ -912,6 +920,9 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         ``t_stop`` (truncate; > 400 stops inside the Langevin phase, after timestep t_stop), ``full_state`` (return the whole
         [B, conditioned_steps + rollout_steps, F] state, drifted conditioning rows first), ``return_trajectory_every`` /
         ``trajectory`` (N <= 401 only; the records hold the [B, rollout_steps, F] state; see p_sample_loop)."""
+        if check_solver(self, solver):
+            raise NotImplementedError("solver='dpmpp-2m': sample_compose_multibodies is a Langevin phase followed by DDPM steps; the "
+                                      "multistep solver runs on the DDIM chains")
         ula = N > 401
         if ula and return_trajectory_every is not None:
             raise NotImplementedError("return_trajectory_every with N > 401: the Langevin chain's step index is (timestep, inner iteration) "
@@ -960,7 +971,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
                     compose_mode="mean", design_fn=None, design_guidance="standard", initial_state_overwrite=None,
                     initialization_mode=0, initialization_img=None, *, noise=None, seed=None, sample_offset=0,
                     use_graph=True, init_img=None, step_range=None, return_trajectory_every=None, trajectory=("x",),
-                    known=None, known_mask=None):
+                    known=None, known_mask=None, solver="ddim", history=None):
         """:1724-1804.  Build-only keywords: ``init_img`` + ``step_range=(i0, i1)`` run DDIM steps i0 .. i1-1 from a given
         state (teacher-forced segments for parity tests: the deterministic sampler amplifies a 1e-6 perturbation of the
         U-Net to 1e-3 .. 1e-2 over 50 .. 250 steps with random-init weights -- measured on the CPU reference itself).
@@ -976,7 +987,14 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         ``known`` / ``known_mask``: replacement conditioning as p_sample_loop -- q(k, times[0], z_init) before the first step (skipped
         with ``init_img``, whose caller hands over a state that is already at its level, so that teacher-forced segments chain
         exactly), q(k, t, z) after every relaxation iteration, q(k, times[i + 1], z) after step i, k itself after the last pair; the
-        tape's ``known_step`` / ``known_recur`` rows are indexed by the DDIM step."""
+        tape's ``known_step`` / ``known_recur`` rows are indexed by the DDIM step.
+        ``solver="dpmpp-2m"`` (build-only): the second-order multistep solver on the same grid at no extra U-Net
+        evaluation -- step i adds ``multistep_kappa()[i] * (x_start_i - x_start_{i-1})`` to its DDIM value (each operation rounded
+        once) ahead of the inpainting overwrite, the known region and the recorder; the first step and the last pair are plain DDIM
+        steps.  Inside the captured step on the library routes, in torch on the route that loops in Python.  Needs
+        ``ddim_sampling_eta == 0`` and ``sampling_timesteps < timesteps`` (ValueError).  With ``step_range=(i0, i1)`` the call
+        takes ``history=`` (the x_start of step i0 - 1: required when i0 > 0) and returns (result, history of step i1 - 1)."""
+        ms_on = self._check_solver(solver, step_range, history)
         n_pairs = len(self.ddim_schedule()[0]) - 1
         iters = max(int(design_guidance.split("-")[-1]) if "recurrence" in design_guidance else 0, 1)
         kn = self._known_region(tuple(shape), known, known_mask, cond, initial_state_overwrite, noise,
@@ -1005,6 +1023,9 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
                               known_step=sl(noise.known_step), known_recur=sl(noise.known_recur))
         S = len(times) - 1
         full = tuple(img.shape)
+        ms = self._multistep(ms_on, i0, i1, history, img)
+        # (a segment call of the multistep solver hands the history of its last step back beside its result)
+        handed = (lambda out: (out, ms[1])) if (ms is not None and step_range is not None) else (lambda out: out)
         karm = self._known_armer(kn, full, noise, device, init=init_img is None)
         kz = lambda row, word: self._known_z(full, row, word, seed, sample_offset, device)
         inpaint = cond if (self.conditioned_steps == 0 and cond is not None) else None
@@ -1020,13 +1041,14 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
             def call(h, un, ws):
                 self._arm(rec, h)
                 self._arm_known(karm, h)
+                self._arm_multistep(ms, h)
                 with torch.cuda.device(device):
                     _ffi.check(_ffi.lib().cindm_ddpm1d_sample_ddim(
                         h, self.model._h, un, C.byref(desc), _ffi.ptr(img), _ffi.ptr(cond_d), S, tarr, _ffi.ptr(carr),
                         _ffi.ptr(None if noise is None else noise.step), C.c_uint64(seed), sample_offset, _ffi.ptr(inp),
                         0 if inp is None else inp.shape[1], _ffi.ptr(None if noise is None else noise.cond), B,
                         _ffi.ptr(ws), ws.numel(), _ffi.current_stream(device), int(use_graph)))
-            return self._recorded(self._chain(img, desc, call), rec)
+            return handed(self._recorded(self._chain(img, desc, call), rec))
         if "recurrence" not in design_guidance:
             raise NotImplementedError("DDIM with design_fn needs a '-recurrence-N' guidance (the reference's other branch "
                                       "returns x_{t-1}, not a noise prediction, :1283)")
@@ -1036,17 +1058,19 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         if dz is not None and dz.recurrence >= 1:
             # built-in objective: relaxations, gradient, overwrite and the DDIM update stay inside the captured step
             rec = self._recorder(return_trajectory_every, trajectory, S, tuple(img.shape), device, times=times)
-            return self._recorded(self._run_guided_ddim(img, cond, desc, dz, times, coefs, noise=noise, seed=seed,
-                                                        sample_offset=sample_offset, inpaint_cond=inpaint,
-                                                        initial_state_overwrite=initial_state_overwrite, use_graph=use_graph,
-                                                        rec=rec, tables=tables, karm=karm), rec)
+            return handed(self._recorded(self._run_guided_ddim(img, cond, desc, dz, times, coefs, noise=noise, seed=seed,
+                                                               sample_offset=sample_offset, inpaint_cond=inpaint,
+                                                               initial_state_overwrite=initial_state_overwrite, use_graph=use_graph,
+                                                               rec=rec, tables=tables, karm=karm, ms=ms), rec))
         coefs = coefs.to(device)
+        kap = None if ms is None else ms[0].to(device)
         img_T = img
         # this route loops in Python: the same record, cloned per step
         rec = None if return_trajectory_every is None else LoopRecorder(S, return_trajectory_every, trajectory, times=times)
 
         def chain():
             img = img_T
+            x_prev = None if ms is None else ms[2]
             if rec is not None:
                 rec.reset()
             if kn is not None and init_img is None:      # rule 1
@@ -1062,6 +1086,8 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
                 else:
                     z = noise.step[i] if noise is not None else torch.randn_like(img)
                     img = x_start * coefs[i, 0] + coefs[i, 1] * eps + coefs[i, 2] * z
+                    if ms is not None and float(ms[0][i]) != 0.0:      # the multistep term (kappa == 0 reads no history)
+                        img = img + kap[i] * (x_start - x_prev)
                     if inpaint is not None:
                         zc = noise.cond[i] if (noise is not None and noise.cond is not None) else torch.randn_like(inpaint)
                         img[:, :inpaint.shape[1], :] = self.q_sample(self._f32(inpaint, device), t, zc)
@@ -1069,18 +1095,21 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
                     img = self.known_replace(img, kn[0], kn[1], tn, None if tn < 0 else kz(None if noise is None else noise.known_step[i], tn))
                 if rec is not None:
                     rec.after(i, img, x_start)
+                x_prev = x_start
+            if ms is not None:
+                ms[1].copy_(x_prev)
             return img
 
         img = chain()
         if self._timed_out(desc, device):
             img = self._rerun_exchange_free(chain, desc, device)
-        return self._recorded(img, rec)
+        return handed(self._recorded(img, rec))
 
     # ------------------------------------------------------------------ autoregressive time composition
     @torch.no_grad()
     def autoregress_time_compose_sample(self, batch_size, cond, n_composed, is_single_step_prediction=False, prediction_steps=40,
                                         *, noise=None, seed=None, sample_offset=0, use_graph=True, return_trajectory_every=None,
-                                        trajectory=("x",)):
+                                        trajectory=("x",), solver="ddim"):
         """:2240-2327 (the default ``--time_compose_method autoregress`` of inference/inference_1d_composing_time_steps.py, :179-213).
         K segments -- n_composed + 1, or ceil(prediction_steps / conditioned_steps) with ``is_single_step_prediction`` --
         each an unguided DDIM chain on a fresh x_T [B, rollout_steps, F] conditioned on ``cond`` (segment 0) or on the last
@@ -1090,6 +1119,8 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         Build-only keywords as ``ddim_sample``: ``seed`` (segment k uses ``autoregress_segment_seeds(seed, K)[k]``, so segment k
         equals ``ddim_sample(seed=seed_k)`` on its condition), ``sample_offset``, ``use_graph``, ``noise`` = NoiseTape(init
         [K,B,R,F], step [K,S,B,R,F]).  The whole rollout is one library call (``cindm_ddpm1d_sample_autoregress``)."""
+        if check_solver(self, solver):
+            raise NotImplementedError("solver='dpmpp-2m': the autoregressive rollout runs the first-order DDIM update only")
         if return_trajectory_every is not None:
             raise NotImplementedError("return_trajectory_every: the autoregressive rollout's step index is (segment, step) and the "
                                       "library does not record it; record a segment with ddim_sample(seed=autoregress_segment_seeds(...)[k])")
@@ -1136,7 +1167,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
     # ------------------------------------------------------------------ parallel time composition
     @torch.no_grad()
     def composing_time_sample(self, shape, cond, clip_denoised=True, n_composed=2, *, noise=None, seed=None, sample_offset=0,
-                              use_graph=True, return_trajectory_every=None, trajectory=("x",)):
+                              use_graph=True, return_trajectory_every=None, trajectory=("x",), solver="ddim"):
         """:1807-1854 (the ``EBMs_compose`` method of inference/inference_1d_composing_time_steps.py, :171-178).  All
         K = n_composed + 1 segments are denoised side by side by ONE unguided DDIM chain on K * B rows: at the top of every
         step segment k + 1 takes the last conditioned_steps rows of segment k's current, still noisy state as its condition
@@ -1151,6 +1182,8 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         [S,K,B,R,F], indexed by the DDIM step).  ``return_trajectory_every`` / ``trajectory``: as ``ddim_sample``; the call then
         returns ((img, img_infered), ChainRecord) with ``.x`` / ``.x0`` [n_records, K, B, R, F].  One library call
         (``cindm_ddpm1d_sample_timecompose``): the update of every step also performs the hand-over."""
+        if check_solver(self, solver):
+            raise NotImplementedError("solver='dpmpp-2m': the parallel time composition runs the first-order DDIM update only")
         Lc, R = self.conditioned_steps, self.image_size
         K = time_compose_segments(Lc, R, n_composed)
         if cond is None or cond.dim() != 3 or cond.shape[1] != Lc:

@@ -29,7 +29,7 @@ from torch import nn
 from . import _ffi
 from .diffusion_base import DiffusionHandle
 from .record import DeviceRecorder, LoopRecorder, stream_mask
-from .schedule import make_schedule
+from .schedule import check_solver, make_schedule
 from .unet2d import from_device_layout, to_device_layout
 
 
@@ -421,7 +421,7 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
             return from_device_layout(rows.reshape(n * B * nb, H * W, cp), Cc, H, W).reshape(n, B, nb, Cc, H, W)
         return out, rec.collect(self._handle(), unpack)
 
-    def _chain2(self, shape, x, rec, call, known=None):
+    def _chain2(self, shape, x, rec, call, known=None, ms=None):
         """One library chain on the state ``x`` (device layout, updated in place): the workspace, the recorder and the known
         region (``known`` = (region, tape, its rows)) armed, the entry ``call(L, h, ws)`` and what the sampling call returns."""
         B, nb, Cc, H, W = shape
@@ -429,6 +429,7 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
         if rec is not None:
             rec.arm(h)
         keep = None if known is None else self._known_arm(h, known[0], shape, known[1], known[2], x.device)      # (alive over the call)
+        self._arm_multistep(ms, h)      # (``ms``: the multistep solver of a DDIM call, DiffusionHandle._multistep)
         with torch.cuda.device(x.device):
             _ffi.check(call(_ffi.lib(), h, ws))
         return self._recorded(from_device_layout(x, Cc, H, W).reshape(B, nb, Cc, H, W), rec, shape)
@@ -450,7 +451,7 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
     @torch.no_grad()
     def p_sample_loop(self, shape, design_fn=None, design_guidance="standard", return_all_timesteps=None, *,
                       noise=None, seed=0, sample_offset=0, use_graph=True, t_stop=0, device=None, fused=True,
-                      return_trajectory_every=None, trajectory=("x",), known=None, known_mask=None, cond=None):
+                      return_trajectory_every=None, trajectory=("x",), known=None, known_mask=None, cond=None, solver="ddim"):
         """:893-907.  Returns [B, nb, C, H, W].  ``noise``: a NoiseTape2D (parity runs); otherwise x_T and the
         per-step draws come from the library's counter-based generator keyed by (seed, sample_offset + design).
         ``return_trajectory_every=k`` with ``trajectory=("x",)`` / ``("x", "x0")``: returns (designs, ChainRecord) with the state
@@ -467,7 +468,11 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
         This differs on purpose from the 1-D inpainting, which copies the reference: level t after the step at t, and nothing on
         the last DDIM pair.  The state channels of known and mask must be identical over the boundary copies (ValueError).  Inside
         the captured step on the library routes (known2d_kernel), ``known_replace`` on the routes that loop in Python; a recorder
-        records after the overwrite."""
+        records after the overwrite.
+        ``solver``: "ddim" (nothing changes); "dpmpp-2m" is a ValueError here -- this is the DDPM chain (see ddim_sample)."""
+        if check_solver(self, solver):
+            raise ValueError("solver='dpmpp-2m' runs on the DDIM chains: p_sample_loop is the DDPM chain (sample() with "
+                             "sampling_timesteps < timesteps, or ddim_sample)")
         B, nb, Cc, H, W = shape
         T = self.num_timesteps
         kn = self._known_region(shape, known, known_mask, cond, noise, T)
@@ -523,7 +528,8 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
     @torch.no_grad()
     def ddim_sample(self, shape, design_fn=None, design_guidance="standard", return_all_timesteps=False, *, noise=None, seed=0,
                     sample_offset=0, use_graph=True, init_img=None, step_range=None, device=None, fused=True,
-                    return_trajectory_every=None, trajectory=("x",), known=None, known_mask=None, cond=None):
+                    return_trajectory_every=None, trajectory=("x",), known=None, known_mask=None, cond=None, solver="ddim",
+                    history=None):
         """DDIM sampling of the 2-D path (:910-949; the reference's own body cannot run, so this build defines it from its
         working pieces).  Returns [B, nb, C, H, W].  With (times, coefs) = ddim_schedule(), for each pair (t, t_next):
         (pred_noise, x_start) = model_predictions(x, t, clip_x_start=True, rederive_pred_noise=True, share_noise=True);
@@ -546,9 +552,16 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
         like sample_noise at every step, whatever sigma is (tape rows ``known_init`` / ``known_state[i]`` / ``known_boundary[i]`` by
         DDIM step index).  This differs on purpose from the 1-D inpainting, which copies the reference: level t after the step at
         t, and nothing on the last DDIM pair.  A recorder records after the overwrite.
+        ``solver="dpmpp-2m"``: the second-order multistep solver on the same grid at no extra U-Net evaluation --
+        step i adds ``multistep_kappa()[i] * (x_start_i - x_start_{i-1})`` to its DDIM value (each operation rounded once) ahead of
+        the guidance shift, the known region and the recorder; the first step and the last pair are plain DDIM steps.  Inside the
+        update kernel on the library routes; ``fused=False`` applies it in torch on ``model_predictions``' x_start.  Needs
+        ``ddim_sampling_eta == 0`` and ``sampling_timesteps < timesteps`` (ValueError).  With ``step_range=(i0, i1)`` the call takes
+        ``history=`` [B, nb, C, H, W] (the x_start of step i0 - 1: required when i0 > 0) and returns (result, history of step i1 - 1).
         Refused (NotImplementedError): any other ``design_fn`` or guidance (the reference has no working guided 2-D DDIM),
         share_noise False and ``return_all_timesteps``."""
         from .forceunet import ForceObjective
+        ms_on = self._check_solver(solver, step_range, history)
         if design_fn is not None and not (isinstance(design_fn, ForceObjective) and design_guidance == "standard-alpha"):
             raise NotImplementedError("DDIM with design_fn: only a ForceObjective under design_guidance='standard-alpha' has a DDIM form "
                                       "(the reference has no working guided 2-D DDIM; its ddim_sample takes no design_fn); sample with "
@@ -582,6 +595,11 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
             x = to_device_layout(init_img.reshape(B * nb, Cc, H, W).to(device, torch.float32), cp)
         else:
             x = self._x_T(shape, noise, seed, sample_offset, device)
+        ms = self._multistep(ms_on, i0, i1, history, x,
+                             pack=lambda v: to_device_layout(v.reshape(B * nb, Cc, H, W).to(device, torch.float32), cp))
+        # (a segment call of the multistep solver hands the history of its last step back beside its result)
+        handed = (lambda out: (out, from_device_layout(ms[1], Cc, H, W).reshape(B, nb, Cc, H, W))) \
+            if (ms is not None and step_range is not None) else (lambda out: out)
         if fo is not None and not fused:
             # the same definition from existing calls: the objective, one unguided DDIM step, the shift in torch
             w = self.ddim_guidance_weights()
@@ -591,10 +609,17 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
             if kn is not None:
                 img = self.known_replace(shape, img, kn[0], kn[1], times[i0], self._known_z(shape, noise, None, self.num_timesteps, seed,
                                                                                            sample_offset, device))
+            x_prev = None if (ms is None or ms[2] is None) else from_device_layout(ms[2], Cc, H, W)
             for i in range(i0, i1):
                 g = fo(img)
+                if ms is not None:      # the x_start the step's update forms (clamped; the same U-Net evaluation, made once more)
+                    x_start = self.model_predictions(shape, img, times[i], clip_x_start=True, rederive_pred_noise=True).pred_x_start
                 img = self.ddim_sample(shape, noise=noise, seed=seed, sample_offset=sample_offset, use_graph=use_graph, init_img=img,
                                        step_range=(i, i + 1), device=device).reshape(B * nb, Cc, H, W)
+                if ms is not None:      # the multistep term (kappa == 0 reads no history; the last pair returns x_start)
+                    if times[i + 1] >= 0 and float(ms[0][i - i0]) != 0.0:
+                        img = img + ms[0][i - i0].to(device) * (x_start - x_prev)
+                    x_prev = x_start
                 img = img - w[i] * g
                 if kn is not None:
                     tn = times[i + 1]
@@ -602,15 +627,18 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
                                              None if tn < 0 else self._known_z(shape, noise, i, tn, seed, sample_offset, device))
                 if lrec is not None:
                     lrec.after(i - i0, img)
-            return self._recorded(img.reshape(B, nb, Cc, H, W), lrec, shape)
+            if ms is not None:
+                ms[1].copy_(to_device_layout(x_prev, cp))
+            return handed(self._recorded(img.reshape(B, nb, Cc, H, W), lrec, shape))
         times, coefs = times[i0:i1 + 1], coefs[i0:i1].contiguous()
         S = len(times) - 1
         rec = self._recorder(return_trajectory_every, trajectory, S, shape, device, times=times)
         ns, nbnd = self._tape_cl(noise, device, slice(i0, i1))
         karm = None if kn is None else (kn, noise, slice(i0, i1))
         # the per-step device tables live in a caller tensor (the library allocates nothing): [S][4] coefficients + [S] time_next
-        if self._ddim_tab is None or self._ddim_tab.numel() < 5 * S or self._ddim_tab.device != device:
-            self._ddim_tab = torch.empty(5 * max(S, self.sampling_timesteps), dtype=torch.float32, device=device)
+        # (the multistep solver's kappa sits behind them: a sixth word per step)
+        if self._ddim_tab is None or self._ddim_tab.numel() < 6 * S or self._ddim_tab.device != device:
+            self._ddim_tab = torch.empty(6 * max(S, self.sampling_timesteps), dtype=torch.float32, device=device)
         tab = self._ddim_tab
         tarr = (C.c_int32 * (S + 1))(*times)
         stream, share = _ffi.current_stream(device), self._share_mode()
@@ -619,20 +647,21 @@ class GaussianDiffusion(DiffusionHandle, nn.Module):
             # per DDIM step (cindm_ddpm2d_sample_ddim_force); the weights ride in the 4th word of the table rows
             fh, fargs, g, wsf = force
             w = self.ddim_guidance_weights()[i0:i1].contiguous()
-            return self._chain2(shape, x, rec, lambda L, h, ws: L.cindm_ddpm2d_sample_ddim_force(
+            return handed(self._chain2(shape, x, rec, lambda L, h, ws: L.cindm_ddpm2d_sample_ddim_force(
                 h, self.model._h, fh, _ffi.ptr(x), B, nb, share, S, tarr, _ffi.ptr(coefs), _ffi.ptr(w), _ffi.ptr(tab), tab.numel() * 4,
                 _ffi.ptr(ns), _ffi.ptr(nbnd), seed, sample_offset, *fargs, _ffi.ptr(g), _ffi.ptr(ws), ws.numel(), _ffi.ptr(wsf),
-                wsf.numel(), stream, int(use_graph)), karm)
-        return self._chain2(shape, x, rec, lambda L, h, ws: L.cindm_ddpm2d_sample_ddim(
+                wsf.numel(), stream, int(use_graph)), karm, ms))
+        return handed(self._chain2(shape, x, rec, lambda L, h, ws: L.cindm_ddpm2d_sample_ddim(
             h, self.model._h, _ffi.ptr(x), B, nb, share, S, tarr, _ffi.ptr(coefs), _ffi.ptr(tab), tab.numel() * 4, _ffi.ptr(ns),
-            _ffi.ptr(nbnd), seed, sample_offset, _ffi.ptr(ws), ws.numel(), stream, int(use_graph)), karm)
+            _ffi.ptr(nbnd), seed, sample_offset, _ffi.ptr(ws), ws.numel(), stream, int(use_graph)), karm, ms))
 
     @torch.no_grad()
     def sample(self, batch_size=16, design_fn=None, design_guidance="standard", num_boundaries=1,
                return_all_timesteps=False, **kw):
         """:960-963 (``sampling_timesteps < timesteps``: ddim_sample).  ``kw``: the build-only keywords of p_sample_loop /
         ddim_sample, ``return_trajectory_every=`` / ``trajectory=`` and the replacement conditioning ``known=`` / ``known_mask=`` /
-        ``cond=`` among them."""
+        ``cond=`` among them, and ``solver=`` ("ddim" | "dpmpp-2m", see ddim_sample)."""
+        check_solver(self, kw.get("solver", "ddim"))
         S = self.image_size
         shape = (batch_size, num_boundaries, self.channels, S, S)
         if self.is_ddim_sampling:

@@ -155,7 +155,8 @@ def shard_known1d(sample_kw, batch_size, lo, hi):
 def sample_sharded(diffusion, batch_size, *, seed, group=None, gather=True, cond=None, **sample_kw):
     """``diffusion.sample(batch_size=...)`` with the batch partitioned over the process group.
     ``cond`` (if given) is the GLOBAL [batch_size, ...] tensor; each rank takes its slice, and per-design ``known=`` /
-    ``known_mask=`` tables theirs (shard_known1d)."""
+    ``known_mask=`` tables theirs (shard_known1d).  ``solver="dpmpp-2m"`` is forwarded like every other sampling keyword: each
+    rank's chain owns its own history tensor, and the solver is element-wise, so the partition does not change a design."""
     _no_trajectory(sample_kw)
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)
@@ -207,7 +208,7 @@ def sample2d_sharded(diffusion, batch_size, *, seed, num_boundaries=1, group=Non
     """2-D ``GaussianDiffusion.sample(batch_size=..., num_boundaries=...)`` with the DESIGNS partitioned over the
     process group (the boundary copies of a design stay on one rank: they share noise and predicted states).
     Returns [batch_size, num_boundaries, C, H, W] on every rank.  The replacement conditioning ``known=`` / ``known_mask=`` /
-    ``cond=`` is sliced to the rank's designs (shard_known2d)."""
+    ``cond=`` is sliced to the rank's designs (shard_known2d).  ``solver="dpmpp-2m"`` is forwarded; each rank owns its history."""
     _no_trajectory(sample_kw)
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(group), dist.get_world_size(group)

@@ -72,7 +72,55 @@ def ddim_schedule(diffusion):
     return times, coefs
 
 
-ULA_STEP_SCALE = 0.035          # sample_step_ULA's step size: betas_inference * 0.035 (model/diffusion_1d.py:2050)
+SOLVERS = ("ddim", "dpmpp-2m")
+
+
+def multistep_kappa(diffusion):
+    """fp32 [S]: the per-step factor of the second-order multistep solver (DPM-Solver++ 2M in data-prediction form)
+    on the ``ddim_schedule()`` grid.  For the pair (t, t') of step i, with alpha = sqrt(abar_t), sigma = sqrt(1 - abar_t),
+    lambda = ln(alpha / sigma) (primes for t') and h_i = lambda' - lambda,
+        kappa_i = (alpha' - sigma' alpha / sigma) h_i / (2 h_{i-1}),   kappa_0 = 0,   kappa_i = 0 for the last pair (t' < 0),
+    so that "DDIM update + kappa_i (X_i - X_{i-1})" is the solver's step.  Computed in float64 from ``alphas_cumprod`` and rounded
+    once; cached like ``ddim_schedule``.  ValueError when lambda is not strictly increasing along the grid (h <= 0)."""
+    d = diffusion
+    T, S = d.num_timesteps, d.sampling_timesteps
+    key = (T, S, d.alphas_cumprod.data_ptr(), d.alphas_cumprod._version)
+    cached = getattr(d, "_kappa_cache", None)
+    if cached is not None and cached[0] == key:
+        return cached[1].clone()
+    times, _ = ddim_schedule(d)
+    ac = d.alphas_cumprod.detach().to("cpu", torch.float64)
+    grid = [t for t in times if t >= 0]
+    a = torch.stack([ac[t] for t in grid]).sqrt()
+    s = torch.stack([1.0 - ac[t] for t in grid]).sqrt()
+    lam = torch.log(a / s)
+    h = lam[1:] - lam[:-1]                       # h[i]: step i, for every pair whose t' >= 0
+    if not bool(torch.isfinite(lam).all()) or not bool((h > 0).all()):
+        raise ValueError("multistep_kappa: lambda = ln(alpha / sigma) is not strictly increasing along the DDIM time grid")
+    kappa = torch.zeros(len(times) - 1, dtype=torch.float64)
+    for i in range(1, len(h)):
+        kappa[i] = (a[i + 1] - s[i + 1] * a[i] / s[i]) * h[i] / (2.0 * h[i - 1])
+    kappa = kappa.to(torch.float32)
+    d._kappa_cache = (key, kappa.clone())
+    return kappa
+
+
+def check_solver(diffusion, solver):
+    """What the ``solver=`` keyword of the sampling methods refuses, before any device work: an unknown name, and for "dpmpp-2m" a
+    stochastic chain (``ddim_sampling_eta != 0``) or one that is not a DDIM chain (``sampling_timesteps == timesteps``).  Returns
+    True for the multistep solver."""
+    if solver not in SOLVERS:
+        raise ValueError(f"unknown solver {solver!r}: one of {SOLVERS}")
+    if solver == "ddim":
+        return False
+    if float(diffusion.ddim_sampling_eta) != 0.0:
+        raise ValueError("solver='dpmpp-2m' is deterministic: ddim_sampling_eta must be 0")
+    if not diffusion.sampling_timesteps < diffusion.num_timesteps:
+        raise ValueError("solver='dpmpp-2m' runs on the DDIM chains: construct the diffusion with sampling_timesteps < timesteps")
+    return True
+
+
+ULA_STEP_SCALE = 0.035         # sample_step_ULA's step size: betas_inference * 0.035 (model/diffusion_1d.py:2050)
 
 
 def ula_schedule(betas_inference):

@@ -584,6 +584,28 @@ int  cindm_ddpm1d_set_known1d(cindm_ddpm1d* h, const float* known, int32_t known
                               const float* noise_recur, int64_t recur_stride, int32_t apply_init,
                               int64_t batch, int32_t rows, int32_t feats);
 
+/* Second-order multistep solver on the DDIM chains (DPM-Solver++ 2M in data-prediction form).  For the pair (X, E) a
+ * chain hands to its DDIM update -- x' = sqrt(alpha_next) X + c E (+ sigma z, which the solver requires to be 0) -- step i computes
+ *     x' = [that DDIM value] + kappa[i] * (X_i - X_{i-1}),
+ * the difference, the product and the sum rounded once each, ahead of whatever follows the DDIM value today (the 2-D guidance shift,
+ * the inpainting overwrite, the known-region node, the recorder), and writes X_i to hist.  A step with kappa[i] == 0 does not read
+ * hist -- the first step of a chain needs no initialised history -- and the last pair (time_next < 0) returns X as before.  In a
+ * guided 1-D step only the iteration that performs the DDIM update reads and writes hist; relaxation iterations leave it alone.
+ * kappa_host: HOST floats [n_steps], copied by this call (schedule.multistep_kappa of the Python face computes them in float64:
+ *        kappa_i = (alpha' - sigma' alpha / sigma) h_i / (2 h_{i-1}) with lambda = ln(alpha / sigma), h_i = lambda' - lambda, kappa_0 = 0;
+ *        a caller that continues a chain passes kappa_0 != 0 and the history X_{-1} in hist).
+ * hist:  DEVICE floats shaped like the chain's state (1-D: [B, L_tot, F]; 2-D: the channel-last padded layout of x), 16-byte
+ *        aligned, the caller's, distinct from the state; hist_floats: its length, which must equal the state's.  On return it holds
+ *        the X of the last step.
+ * Arms the NEXT chain call on this handle; that call consumes the solver whether it succeeds or fails, and kappa_host == NULL
+ * disarms.  Run by cindm_ddpm1d_sample_ddim / _sample_ddim_guided and cindm_ddpm2d_sample_ddim / _sample_ddim_force, which check
+ * n_steps against the call, hist_floats against the state and that every step's sigma is 0; every other chain entry refuses an armed
+ * solver.  The 2-D entries keep kappa behind their tables: tab_bytes must then be >= n_steps * 24.  cindm_ddpm1d_workspace_bytes is
+ * unchanged.  The multistep 1-D step never runs its update inside the last U-Net kernel (one launch more than the fused DDIM step).
+ * A chain whose first step reads the history (kappa[0] != 0) cannot be re-run after an exchange time-out: the call fails and says so.
+ * With nothing armed a chain launches exactly what it launched before this entry existed, under the same graph key. */
+int  cindm_ddpm1d_set_multistep(cindm_ddpm1d* h, const float* kappa_host, int32_t n_steps, float* hist, int64_t hist_floats);
+
 /* ===================================================================== 2-D airfoil path
  * Replaces Unet.forward (model/diffusion_2d.py:369-408) and GaussianDiffusion.p_sample /
  * p_sample_loop (model/diffusion_2d.py:788-907) of the reference for the sampling path
