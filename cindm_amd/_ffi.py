@@ -72,6 +72,7 @@ SIGNATURES = {
     "cindm_ddpm1d_recorder_info": (C.c_int, [_vp, C.POINTER(_i32)]),
     "cindm_ddpm1d_set_design_tables": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i64]),
     "cindm_ddpm1d_set_design_quadratic": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i64]),
+    "cindm_ddpm1d_set_design_pairdist": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i64]),
     "cindm_ddpm1d_set_known2d": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32]),
     "cindm_ddpm1d_set_known1d": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i64, _i32, _i32]),
     "cindm_ddpm1d_set_multistep": (C.c_int, [_vp, _vp, _i32, _vp, _i64]),

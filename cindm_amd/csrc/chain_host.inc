@@ -1,7 +1,7 @@
 // The chain driver: what every sampling entry (cindm_ddpm1d_sample*, cindm_ddpm2d_sample*) does around its own step.
 // Textually included by cindm_hip.hip after the 1-D U-Net's host code and before ddpm1d_host.inc and the 2-D host files; each piece
 // exists once.
-//   RecSpec, DesignTables, QuadTables, cindm_ddpm1d, KeyBuilder   the schedule handle both sides run on, with what a chain call arms on it
+//   RecSpec, DesignTables, QuadTables, PairTables, cindm_ddpm1d, KeyBuilder   the schedule handle both sides run on, with what a chain call arms on it
 //   chain_stream        which stream a chain runs on
 //   stream_steps        the eager loop
 //   graph_capture/_run  capture a step functor into an instantiated graph; launch it n times and synchronise
@@ -10,6 +10,7 @@
 //   RecScope            the chain recorder: taken by every chain entry
 //   DesignTablesScope   the waypoint objective's tables: taken by every 1-D chain entry, run by the two guided ones
 //   QuadTablesScope     the quadratic objective's tables: taken by every chain entry, run by the two guided 1-D ones
+//   PairTablesScope     the pair-distance objective's tables: taken by every chain entry, run by the two guided 1-D ones
 //   Known2DScope        the 2-D chains' known region: taken by every chain entry, run by the four 2-D ones
 //   Known1DScope        the 1-D chains' known region: taken by every chain entry, run by cindm_ddpm1d_sample / _sample_guided /
 //                       _sample_ddim / _sample_ddim_guided
@@ -37,6 +38,12 @@ struct DesignTables {
 struct QuadTables {
     const float* S = nullptr; const float* h = nullptr; int S_per_design = 0, h_per_design = 0;
     int rows = 0, features = 0; int64_t batch = 0;
+};
+
+// The pair-distance objective's device tables as armed by the caller (cindm_ddpm1d_set_design_pairdist, below)
+struct PairTables {
+    const float* band = nullptr; const float* weight = nullptr; int band_per_design = 0, weight_per_design = 0;
+    int rows = 0, n_bodies = 0; int64_t batch = 0;
 };
 
 // The known region of a 2-D chain as armed by the caller (cindm_ddpm1d_set_known2d, below: known .. cp) and as one chain runs it
@@ -80,6 +87,8 @@ struct cindm_ddpm1d {
     DesignTables dzt_armed; const DesignTables* dzt = nullptr;
     // the quadratic objective's tables, likewise
     QuadTables qdt_armed; const QuadTables* qdt = nullptr;
+    // the pair-distance objective's tables, likewise
+    PairTables pdt_armed; const PairTables* pdt = nullptr;
     // the known region of the 2-D chains: what the next chain call will take, and the one a running 2-D chain holds (null: none)
     Known2D kn_armed; const Known2D* kn = nullptr;
     // the known region of the 1-D chains, likewise
@@ -307,6 +316,11 @@ static int dzt_begin(DesignTablesScope& ts, const cindm_design_desc* dz, int Lto
                           "cindm_ddpm1d_set_design_quadratic; the tables were dropped");
         return 0;
     }
+    if (dz->mode == 6) {
+        REQUIRE(!ts.on(), "design tables (target, scale) are armed but the descriptor's mode is 6, which reads the pair-distance tables of "
+                          "cindm_ddpm1d_set_design_pairdist; the tables were dropped");
+        return 0;
+    }
     if (dz->mode != 3 && dz->mode != 4) {
         REQUIRE(!ts.on(), "design tables are armed but the descriptor's mode is 1 / 2 (the point objective, which reads none); the tables were dropped");
         return 0;
@@ -363,6 +377,11 @@ static int qdt_refuse(const QuadTablesScope& qs) {
 // x, x2: the state buffers the guided update reads a row of as float4 (x2: the guided DDIM chain's second buffer, or null)
 static int qdt_begin(QuadTablesScope& qs, const cindm_design_desc* dz, int Ltot, int n_bodies, int64_t B, const float* x, const float* x2) {
     const QuadTables& t = qs.t;
+    if (dz->mode == 6) {
+        REQUIRE(!qs.on(), "quadratic design tables are armed but the descriptor's mode is 6, which reads the pair-distance tables of "
+                          "cindm_ddpm1d_set_design_pairdist; the tables were dropped");
+        return 0;
+    }
     if (dz->mode != 5) {
         REQUIRE(!qs.on(), "quadratic design tables are armed but the descriptor's mode is 1 .. 4 (the point and waypoint objectives, which do "
                           "not read them); the tables were dropped");
@@ -396,6 +415,62 @@ extern "C" int cindm_ddpm1d_set_design_quadratic(cindm_ddpm1d* h, const float* S
     QuadTables& t = h->qdt_armed;
     t.S = S; t.h = hvec; t.S_per_design = S_per_design ? 1 : 0; t.h_per_design = h_per_design ? 1 : 0;
     t.rows = rows; t.features = features; t.batch = batch;
+    return 0;
+}
+
+// ---- the pair-distance objective's tables (DESIGN 4.5s) ---------------------------------------------------------------------------------
+// cindm_ddpm1d_set_design_pairdist arms the handle; the next chain entry -- 1-D or 2-D -- takes the tables with PairTablesScope, so the
+// call consumes them however it ends, and either refuses them (pdt_refuse: every chain that is not guided) or checks them against its
+// descriptor and state (pdt_begin) and runs with them: run_step reads h->pdt for the whole call, the re-run included.
+struct PairTablesScope {
+    cindm_ddpm1d* h; PairTables t;
+    explicit PairTablesScope(cindm_ddpm1d* h_) : h(h_) {
+        if (!h) return;
+        t = h->pdt_armed; h->pdt_armed = PairTables();
+    }
+    ~PairTablesScope() { if (h) h->pdt = nullptr; }
+    bool on() const { return t.band != nullptr; }
+};
+
+static int pdt_refuse(const PairTablesScope& ps) {
+    REQUIRE(!ps.on(), "pair-distance design tables: only the guided 1-D chains (cindm_ddpm1d_sample_guided / _sample_ddim_guided) read them; the tables were dropped");
+    return 0;
+}
+
+static int pdt_begin(PairTablesScope& ps, const cindm_design_desc* dz, int Ltot, int n_bodies, int64_t B) {
+    const PairTables& t = ps.t;
+    if (dz->mode != 6) {
+        REQUIRE(!ps.on(), "pair-distance design tables are armed but the descriptor's mode is 1 .. 5 (the point, waypoint and quadratic "
+                          "objectives, which do not read them); the tables were dropped");
+        return 0;
+    }
+    REQUIRE(ps.on(), "design objective mode 6 reads band and weight from tables: arm them with cindm_ddpm1d_set_design_pairdist before the chain call");
+    if (t.rows != Ltot)
+        return fail("pair-distance design tables: " + std::to_string(t.rows) + " rows, the state has " + std::to_string(Ltot));
+    if (t.n_bodies != n_bodies)
+        return fail("pair-distance design tables: " + std::to_string(t.n_bodies) + " bodies, the composition has " + std::to_string(n_bodies));
+    if (t.batch != B)
+        return fail("pair-distance design tables: made for a batch of " + std::to_string(t.batch) + ", the chain runs " + std::to_string(B));
+    REQUIRE((((uintptr_t)t.band | (uintptr_t)t.weight) & 3) == 0, "pair-distance design tables: band and weight must be 4-byte aligned");
+    ps.h->pdt = &ps.t;
+    return 0;
+}
+
+static void pdt_key(KeyBuilder& K, const cindm_ddpm1d* h) {
+    if (h->pdt) K(h->pdt->band)(h->pdt->weight)(h->pdt->band_per_design)(h->pdt->weight_per_design);
+}
+
+extern "C" int cindm_ddpm1d_set_design_pairdist(cindm_ddpm1d* h, const float* band, int32_t band_per_design, const float* weight,
+                                                int32_t weight_per_design, int32_t rows, int32_t n_bodies, int64_t batch) {
+    if (h) h->pdt_armed = PairTables();      // (a refused call leaves the handle disarmed)
+    REQUIRE(h, "null handle");
+    if (!band && !weight) return 0;
+    REQUIRE(band && weight, "pair-distance design tables: band and weight come together (NULL, NULL disarms)");
+    REQUIRE(rows >= 1 && batch >= 1, "pair-distance design tables: rows and batch must be >= 1");
+    REQUIRE(n_bodies >= 2 && n_bodies <= 8, "pair-distance design tables: n_bodies must be in 2 .. 8");
+    PairTables& t = h->pdt_armed;
+    t.band = band; t.weight = weight; t.band_per_design = band_per_design ? 1 : 0; t.weight_per_design = weight_per_design ? 1 : 0;
+    t.rows = rows; t.n_bodies = n_bodies; t.batch = batch;
     return 0;
 }
 

@@ -158,3 +158,6 @@ extern "C" void cindm_comm_destroy(cindm_comm* c) {
     if (c->comm && rccl().CommDestroy) (void)rccl().CommDestroy(c->comm);
     delete c;
 }
+
+// ============================================================================ kernels defined behind all others
+#include "kernels_tail.h"

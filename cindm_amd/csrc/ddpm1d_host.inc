@@ -14,7 +14,7 @@
 //   ddim_tables1               the DDIM preamble: per-step tables into the workspace's slice
 //   loop_steps, loop_chain     the unguided loop and the chain that is one such loop
 //   guided_step, guided_chain  the recurrence iterations of a guided step and the guided chains' tail
-// An entry is: RecScope, DesignTablesScope, Known2DScope, Known1DScope, QuadTablesScope, MultistepScope, Chain1D, refusals, rec_begin, known1_begin,
+// An entry is: RecScope, DesignTablesScope, Known2DScope, Known1DScope, QuadTablesScope, PairTablesScope, MultistepScope, Chain1D, refusals, rec_begin, known1_begin,
 // (DDIM: ms_begin,) chain_stream, (DDIM: ddim_tables1,) chain_io plus what it adds, and one call of loop_chain, guided_chain or its own body (the rollout).
 
 extern "C" int cindm_ddpm1d_create(const cindm_sched_desc* d, cindm_ddpm1d** out) {
@@ -292,7 +292,11 @@ static int run_step(const Chain1D& ch, const StepIO& io, int32_t t, const int32_
     const bool guided = io.dz && io.x_out;
     if (guided) {
         a.dz_mode = io.dz->mode; a.dz_alpha = io.dz->alpha; a.dz_tc = io.dz->time_consistency_coef;
-        if (io.dz->mode == 5) {     // quadratic objective: its tables' addresses and flags are operands of the captured update as well
+        if (io.dz->mode == 6) {     // pair-distance objective: likewise
+            REQUIRE(h->pdt, "design objective mode 6 outside a chain that took pair-distance design tables (internal error)");
+            a.dz_band = h->pdt->band; a.dz_weight = h->pdt->weight;
+            a.dz_mode |= (h->pdt->band_per_design ? kDzTargetPerDesign : 0) | (h->pdt->weight_per_design ? kDzScalePerDesign : 0);
+        } else if (io.dz->mode == 5) {     // quadratic objective: its tables' addresses and flags are operands of the captured update as well
             REQUIRE(h->qdt, "design objective mode 5 outside a chain that took quadratic design tables (internal error)");
             a.dz_S = h->qdt->S; a.dz_h = h->qdt->h;
             a.dz_mode |= (h->qdt->S_per_design ? kDzTargetPerDesign : 0) | (h->qdt->h_per_design ? kDzScalePerDesign : 0);
@@ -357,8 +361,11 @@ static int run_step(const Chain1D& ch, const StepIO& io, int32_t t, const int32_
         hipLaunchKernelGGL(timecompose_update_kernel, dim3((unsigned)((ne / 4 + 255) / 256)), dim3(256), 0, stream, u);
     } else if (io.ms_hist && io.ddim_tab && !(guided && io.relax)) {
         // the multistep solver's update (never fused; a relaxation iteration is not an update and keeps the kernels below)
-        if ((a.dz_mode & kDzModeMask) == 5) hipLaunchKernelGGL(compose_update_ms_quad_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a, io.ms_hist);
+        if ((a.dz_mode & kDzModeMask) == 6) launch_compose_update_pair(a, io.ms_hist, ne, stream);
+        else if ((a.dz_mode & kDzModeMask) == 5) hipLaunchKernelGGL(compose_update_ms_quad_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a, io.ms_hist);
         else hipLaunchKernelGGL(compose_update_ms_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a, io.ms_hist);
+    } else if ((a.dz_mode & kDzModeMask) == 6) {      // (guided: never fused)
+        launch_compose_update_pair(a, nullptr, ne, stream);
     } else if ((a.dz_mode & kDzModeMask) == 5) {      // (guided: never fused)
         hipLaunchKernelGGL(compose_update_quad_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a);
     } else if (!pair->fused_done) hipLaunchKernelGGL(compose_update_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a);
@@ -429,17 +436,19 @@ static int chain1_refuse(const Chain1D& ch, const float* x, const float* cond, c
 }
 
 // What a guided entry refuses on top of chain1_refuse (after it): the objective, its tables (dzt_begin takes them for the call) and
-// the rows it overwrites; likewise the quadratic objective's tables (qdt_begin; x: the state its update reads 16 bytes at a time).
+// the rows it overwrites; likewise the quadratic objective's tables (qdt_begin; x: the state its update reads 16 bytes at a time)
+// and the pair-distance objective's (pdt_begin).
 // min_recurrence: 0 for the DDPM chain (no recurrence: one plain guided iteration), 1 for the DDIM chain.
-static int guided_refuse(const Chain1D& ch, DesignTablesScope& ts, QuadTablesScope& qs, const cindm_design_desc* dz, const float* x, int min_recurrence,
+static int guided_refuse(const Chain1D& ch, DesignTablesScope& ts, QuadTablesScope& qs, PairTablesScope& ps, const cindm_design_desc* dz, const float* x, int min_recurrence,
                          const float* initial_state_overwrite, int overwrite_steps) {
     REQUIRE(dz, "null argument");
-    REQUIRE(dz->mode >= 1 && dz->mode <= 5, "design objective mode must be 1 (L2), 2 (L2square), 3 (table L2), 4 (table L2square) or 5 (quadratic tables)");
+    REQUIRE(dz->mode >= 1 && dz->mode <= 6, "design objective mode must be 1 (L2), 2 (L2square), 3 (table L2), 4 (table L2square), 5 (quadratic tables) or 6 (pair-distance tables)");
     if (min_recurrence == 0) REQUIRE(dz->recurrence >= 0 && dz->recurrence <= 64, "recurrence count out of range");
     else REQUIRE(dz->recurrence >= 1 && dz->recurrence <= 64,
                  "guided DDIM needs a recurrence count in 1 .. 64 (without recurrence the reference returns no noise prediction)");
     if (dzt_begin(ts, dz, ch.Ltot(), ch.c->n_bodies, ch.B) != 0) return -1;
     if (qdt_begin(qs, dz, ch.Ltot(), ch.c->n_bodies, ch.B, x, ch.stage()) != 0) return -1;
+    if (pdt_begin(ps, dz, ch.Ltot(), ch.c->n_bodies, ch.B) != 0) return -1;
     REQUIRE(dz->mode >= 3 || (dz->last_n_step >= 1 && dz->last_n_step <= ch.Ltot()), "last_n_step out of range");
     REQUIRE(!initial_state_overwrite || (overwrite_steps >= 1 && overwrite_steps <= ch.Ltot()), "bad overwrite_steps");
     return 0;
@@ -698,6 +707,7 @@ static int guided_chain(RecScope& rs, const Chain1D& ch, StepIO io, int kind, co
         K(*io.dz)(recur_noise_steps)(R);
         dzt_key(K, ch.h);
         qdt_key(K, ch.h);
+        pdt_key(K, ch.h);
         const int rc = replay_steps(ch, K.k, nsteps, step, pp);
         return rc == 0 ? after() : rc;
     }));
@@ -718,10 +728,11 @@ extern "C" int cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_un
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    PairTablesScope ps(h);
     MultistepScope ms(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
-    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0) return -1;
+    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0) return -1;
     if (rec_begin(rs, x, nsteps, ch.n_state()) != 0 || known1_begin(k1, ch, x, 0) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     const StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
@@ -738,10 +749,11 @@ extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cin
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    PairTablesScope ps(h);
     MultistepScope ms(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
-    if (dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, &dd) != 0) return -1;
+    if (dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, &dd) != 0) return -1;
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     if (rec_begin(rs, x, n_steps, ch.n_state()) != 0 || known1_begin(k1, ch, x, 0) != 0 || ms_begin(ms, n_steps, coefs, ch.n_state(), x) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
@@ -766,10 +778,11 @@ extern "C" int cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pa
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    PairTablesScope ps(h);
     MultistepScope ms(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
-    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || known2_refuse(ks) != 0) return -1;
+    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0 || known2_refuse(ks) != 0) return -1;
     if (known1_refuse(k1, "the autoregressive rollout draws a fresh state per segment and hands rows over between segments: a region of "
                           "one [B, rows, F] state does not name a place in it") != 0) return -1;
     REQUIRE(!rs.on(), "recorder: the autoregressive rollout is not recorded (its step index is (segment, step)); the recorder was dropped");
@@ -825,9 +838,10 @@ extern "C" int cindm_ddpm1d_sample_ula(cindm_ddpm1d* h, cindm_unet1d* pair, cind
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    PairTablesScope ps(h);
     MultistepScope ms(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
-    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || known2_refuse(ks) != 0) return -1;
+    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0 || known2_refuse(ks) != 0) return -1;
     if (known1_refuse(k1, "the Langevin chain moves the whole state, conditioning rows included, at one noise level per timestep without a "
                           "reverse update: the region's forward-diffusion trajectory is not defined for it") != 0) return -1;
     REQUIRE(!rs.on(), "recorder: the Langevin chain is not recorded (its step index is (timestep, inner iteration)); the recorder was dropped");
@@ -868,10 +882,11 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    PairTablesScope ps(h);
     MultistepScope ms(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
-    if (ms_refuse(ms) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0 || guided_refuse(ch, ts, qs, dz, x, 0, initial_state_overwrite, overwrite_steps) != 0) return -1;
+    if (ms_refuse(ms) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0 || guided_refuse(ch, ts, qs, ps, dz, x, 0, initial_state_overwrite, overwrite_steps) != 0) return -1;
     if (rec_begin(rs, x, nsteps, ch.n_state()) != 0 || known1_begin(k1, ch, x, std::max(dz->recurrence, 1)) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
@@ -899,10 +914,11 @@ extern "C" int cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pa
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    PairTablesScope ps(h);
     MultistepScope ms(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
-    if (known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, &dd) != 0 || guided_refuse(ch, ts, qs, dz, x, 1, initial_state_overwrite, overwrite_steps) != 0) return -1;
+    if (known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, &dd) != 0 || guided_refuse(ch, ts, qs, ps, dz, x, 1, initial_state_overwrite, overwrite_steps) != 0) return -1;
     REQUIRE(!inpaint_cond || (inpaint_steps >= 1 && inpaint_steps <= ch.Ltot()), "bad inpaint_steps");
     if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     if (rec_begin(rs, x, n_steps, ch.n_state()) != 0 || known1_begin(k1, ch, x, dz->recurrence) != 0 ||

@@ -12,7 +12,7 @@
 //   ddpm_step2, ddim_step2     the captured step: [gradient,] step, [shift,] [known node,] [record node]
 //   run_chain2                 the tail: counter, rec_arm, [known node: rule 1,] replay -- under force_chain_with_recovery when guided -- and rec_done
 //   ms_begin2, ms_tables2      the multistep solver of a DDIM chain (cindm_ddpm1d_set_multistep): its checks, and kappa behind the caller's tables
-// An entry is: RecScope, Known2DScope, Known1DScope, QuadTablesScope, MultistepScope, refusals, (DDIM: ms_begin2,) rec_begin2, known2_begin, chain_stream,
+// An entry is: RecScope, Known2DScope, Known1DScope, QuadTablesScope, PairTablesScope, MultistepScope, refusals, (DDIM: ms_begin2,) rec_begin2, known2_begin, chain_stream,
 // (DDIM: upload_ddim_tables, ms_tables2,) build the step, run_chain2.
 
 // Returns the bytes of a diffusion workspace for `images` images; the offsets of its second and third slice go to *o_unet / *o_xT.
@@ -343,8 +343,9 @@ extern "C" int cindm_ddpm2d_sample(cindm_ddpm1d* s, cindm_unet2d* u, float* x, i
     Known2DScope ks(s);
     Known1DScope k1(s);
     QuadTablesScope qs(s);
+    PairTablesScope ps(s);
     MultistepScope ms(s);
-    if (qdt_refuse(qs) != 0) return -1;
+    if (qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0) return -1;
     if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
                           "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
@@ -365,8 +366,9 @@ extern "C" int cindm_ddpm2d_sample_ddim(cindm_ddpm1d* s, cindm_unet2d* u, float*
     Known2DScope ks(s);
     Known1DScope k1(s);
     QuadTablesScope qs(s);
+    PairTablesScope ps(s);
     MultistepScope ms(s);
-    if (qdt_refuse(qs) != 0) return -1;
+    if (qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0) return -1;
     if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
                           "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
@@ -397,8 +399,9 @@ extern "C" int cindm_ddpm2d_sample_force(cindm_ddpm1d* s, cindm_unet2d* u, cindm
     Known2DScope ks(s);
     Known1DScope k1(s);
     QuadTablesScope qs(s);
+    PairTablesScope ps(s);
     MultistepScope ms(s);
-    if (qdt_refuse(qs) != 0) return -1;
+    if (qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0) return -1;
     if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
                           "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
@@ -424,8 +427,9 @@ extern "C" int cindm_ddpm2d_sample_ddim_force(cindm_ddpm1d* s, cindm_unet2d* u, 
     Known2DScope ks(s);
     Known1DScope k1(s);
     QuadTablesScope qs(s);
+    PairTablesScope ps(s);
     MultistepScope ms(s);
-    if (qdt_refuse(qs) != 0) return -1;
+    if (qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0) return -1;
     if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
                           "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);

@@ -2572,12 +2572,15 @@ struct ComposeArgs {
     // scalars, so the struct -- which sits by value in the kernarg of ups_last_kernel and its fused forms -- keeps its size.
     // The quadratic objective (mode 5) reads S [B | 1, Ltot, F, F] and h [B | 1, Ltot, F] from device tables through the same two words
     // and the same two per-design bits; its gradient is compiled into compose_update_quad_kernel only.
-    int dz_mode;                 // 0 off; bits 0-2: 1 "L2", 2 "L2square" (point), 3 "L2", 4 "L2square" (tables), 5 quadratic (tables); kDzTargetPerDesign, kDzScalePerDesign
+    // The pair-distance objective (mode 6) reads band [B | 1, Ltot, P, 2] = (lo, hi) and weight [B | 1, Ltot, P], P = nb (nb - 1) / 2 in
+    // pair_index order, likewise; its gradient is compiled into compose_update_pair_kernel only.
+    int dz_mode;                 // 0 off; bits 0-2: 1 "L2", 2 "L2square" (point), 3 "L2", 4 "L2square" (tables), 5 quadratic (tables), 6 pair distance (tables); kDzTargetPerDesign, kDzScalePerDesign
     int dz_alpha;                // 1: scale the gradient by eta_t = beta_t / sqrt(alphas_cumprod_prev_t) (standard-alpha)
     union {
         struct { int dz_last_n; float dz_coef, dz_tx, dz_ty; };              // modes 1, 2
         struct { const float* dz_target; const float* dz_scale; };           // modes 3, 4: [B | 1, Ltot, nb, 2] and [B | 1, Ltot, nb]
         struct { const float* dz_S; const float* dz_h; };                    // mode 5: [B | 1, Ltot, F, F] (kDzTargetPerDesign) and [B | 1, Ltot, F] (kDzScalePerDesign)
+        struct { const float* dz_band; const float* dz_weight; };            // mode 6: [B | 1, Ltot, P, 2] (kDzTargetPerDesign) and [B | 1, Ltot, P] (kDzScalePerDesign)
     };
     float dz_tc;
     int relax;                   // this launch is a relaxation iteration (:1365-1367): x <- a_t pred + b_t z' (guided DDIM: and the step state stays)
@@ -2601,8 +2604,9 @@ __device__ __forceinline__ void compose_advance(const ComposeArgs& a, int t) {
     if (a.ep_next0) a.ep_next0[0] = a.ep_cur0[0] + 1;
     if (a.ep_next1) a.ep_next1[0] = a.ep_cur1[0] + 1;
 }
-// the update of state element i = (b * Ltot + row) * F + f (compose_update_kernel's body; compose_update_body<true> is
-// compose_update_quad_kernel's: the same update with the quadratic objective's gradient in place of the position objectives')
+// the update of state element i = (b * Ltot + row) * F + f (compose_update_kernel's body; compose_update_body<kObjQuad> is
+// compose_update_quad_kernel's and compose_update_body<kObjPair> compose_update_pair_kernel's: the same update with the quadratic /
+// the pair-distance objective's gradient in place of the position objectives')
 __device__ void compose_update_element(const ComposeArgs& a, int64_t i);
 __device__ __forceinline__ void counter_normal4(uint64_t seed, uint64_t sample, uint32_t step, uint32_t elem4, float (&z)[4]);
 // x_{t-1} of one element of a PLAIN single-model step from the model output o (compose_update_element's mode 0 followed
@@ -3560,11 +3564,13 @@ __global__ void compose_gather_kernel(const ComposeArgs a) {
 }
 
 // One thread per state element (b, l, f) of the FULL sequence (cond rows skipped on output).
-// kQuad: the guided branch evaluates the quadratic objective (dz_mode 5) on all four components of a body; false: every other mode.
+// kObj: what the guided branch evaluates.  kObjPosition: the position objectives of dz_mode 1 - 4; kObjQuad: the quadratic objective
+// (dz_mode 5) on all four components of a body; kObjPair: the pair-distance objective (dz_mode 6) on the position components.
 // kMulti: the DDIM update carries the second-order multistep term: v = v + kappa (x0 - hist[i]) with kappa = the 4th word
 // of the step's table row, each operation rounded once, ahead of the inpainting overwrite; kappa == 0 does not read the history; the
 // update -- never a relaxation iteration -- writes x0 to hist[i].  One thread reads and writes one element: in place is safe.
-template <bool kQuad, bool kMulti = false>
+constexpr int kObjPosition = 0, kObjQuad = 1, kObjPair = 2;
+template <int kObj, bool kMulti = false>
 __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_t i, float* hist = nullptr) {
     const int Lfull = a.Ltot + a.cond_steps;
     const int t = step_scalar(a.t_ptr, a.t_imm);
@@ -3674,7 +3680,7 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
         // too this is the guided DDIM loop: relaxation iterations as below, the last iteration is the DDIM update on (eps + g, x0).
         float g = 0.f;
         const int dzm = a.dz_mode & kDzModeMask;
-        if constexpr (kQuad) {
+        if constexpr (kObj == kObjQuad) {
             // quadratic objective: g = (sum_f' S[l, f, f'] x[b, l, f']) - h[l, f], from 0.f in ascending f', every product and sum rounded
             // once, h subtracted last.  F % 4 == 0 and 16-byte aligned tables and states (qdt_begin): both rows are read as float4.
             const int64_t bS = (a.dz_mode & kDzTargetPerDesign) ? b : 0, bh = (a.dz_mode & kDzScalePerDesign) ? b : 0;
@@ -3690,8 +3696,33 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
             g = __fsub_rn(acc, a.dz_h[(bh * a.Ltot + lx) * a.F + f]);
         }
         if (comp < 2) {
-            if constexpr (kQuad) {
+            if constexpr (kObj == kObjQuad) {
                 // (the position objectives of modes 1 - 4 are not part of this instantiation; the time-consistency term below is)
+            } else if constexpr (kObj == kObjPair) {
+                // pair-distance objective: g = sum over the other bodies o, ascending, from 0.f, of the pair {body, o}'s term
+                //   w * 2 * (r - lo) * d / r  where r < lo,   w * 2 * (r - hi) * d / r  where r > hi,   0.f otherwise and where w == 0 or r == 0,
+                // d = x[body, comp] - x[o, comp], r = sqrt(dx dx + dy dy): every product, sum, square root and quotient rounded once, in
+                // the order ((((w * 2) * (r - bound)) * d) / r).  Every state load is in the thread's own row of x (F floats at i - f);
+                // the tables' indices are bounded by pdt_begin's rows == Ltot, n_bodies == nb, batch == B.
+                const int64_t bb = (a.dz_mode & kDzTargetPerDesign) ? b : 0, bw = (a.dz_mode & kDzScalePerDesign) ? b : 0;
+                const float* xr = a.x + (i - f);
+                const float* wp = a.dz_weight + (bw * a.Ltot + lx) * P;
+                const float* bp = a.dz_band + (bb * a.Ltot + lx) * P * 2;
+                const float xw = a.x[i ^ 1];
+                for (int o = 0; o < a.nb; ++o) {
+                    if (o == body) continue;
+                    const int p = pair_index(min(body, o), max(body, o), a.nb);
+                    const float w = wp[p];
+                    float term = 0.f;
+                    if (w != 0.f) {
+                        const float lo = bp[2 * p], hi = bp[2 * p + 1];
+                        const float d = __fsub_rn(xv, xr[4 * o + comp]), dw = __fsub_rn(xw, xr[4 * o + (comp ^ 1)]);
+                        const float r = sqrtf(__fadd_rn(__fmul_rn(d, d), __fmul_rn(dw, dw)));
+                        if (r != 0.f && (r < lo || r > hi))
+                            term = __fmul_rn(__fmul_rn(__fmul_rn(w, 2.0f), __fsub_rn(r, r < lo ? lo : hi)), d) / r;
+                    }
+                    g = __fadd_rn(g, term);
+                }
             } else if (dzm >= 3) {
                 // table objective: the point branch's expressions with the scale and the target read per (design | all, row, body)
                 const int64_t bs = (a.dz_mode & kDzScalePerDesign) ? b : 0, bt = (a.dz_mode & kDzTargetPerDesign) ? b : 0;
@@ -3814,7 +3845,7 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
     }
 }
 
-__device__ void compose_update_element(const ComposeArgs& a, int64_t i) { compose_update_body<false>(a, i); }
+__device__ void compose_update_element(const ComposeArgs& a, int64_t i) { compose_update_body<kObjPosition>(a, i); }
 
 __global__ void compose_update_kernel(const ComposeArgs a) {
     compose_update_element(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
@@ -3823,17 +3854,23 @@ __global__ void compose_update_kernel(const ComposeArgs a) {
 // the guided update with the quadratic objective (dz_mode 5): an instantiation of its own, so that compose_update_kernel is the code
 // it was (DESIGN 4.5q has both kernels' resource usage)
 __global__ void compose_update_quad_kernel(const ComposeArgs a) {
-    compose_update_body<true>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    compose_update_body<kObjQuad>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
+
+// the guided update with the pair-distance objective (dz_mode 6) and its DDIM update under the multistep solver: likewise
+// instantiations of their own, compose_update_pair_kernel<kMulti> in kernels_tail.h, launched through this function.  The translation
+// unit includes that file last and the kernel is a template first used there, so the code object holds the two behind every kernel
+// that exists and those keep their places in it (4.5r has what moving them may cost).  hist: null for the guided update.
+void launch_compose_update_pair(const ComposeArgs& a, float* hist, int64_t n_elements, hipStream_t stream);
 
 // the DDIM updates of a chain that runs the second-order multistep solver: instantiations of their own, so that the two
 // kernels above are the code they were.  Launched for a step's update only -- a guided step's relaxation iterations keep the kernels
 // above and leave the history alone -- and never fused into ups_last_kernel.
 __global__ void compose_update_ms_kernel(const ComposeArgs a, float* hist) {
-    compose_update_body<false, true>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, hist);
+    compose_update_body<kObjPosition, true>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, hist);
 }
 __global__ void compose_update_ms_quad_kernel(const ComposeArgs a, float* hist) {
-    compose_update_body<true, true>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, hist);
+    compose_update_body<kObjQuad, true>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, hist);
 }
 
 // ---------------------------------------------------------------------------------------------

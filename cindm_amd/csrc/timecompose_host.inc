@@ -19,11 +19,12 @@ extern "C" int cindm_ddpm1d_sample_timecompose(cindm_ddpm1d* h, cindm_unet1d* pa
     Known2DScope ks(h);
     Known1DScope k1(h);
     QuadTablesScope qs(h);
+    PairTablesScope ps(h);
     MultistepScope ms(h);
     REQUIRE(n_seg >= 2 && B >= 1 && (int64_t)n_seg * B <= 65535, "n_seg must be >= 2 and n_seg * B <= 65535 (the update derives a row's segment by a 32-bit multiply)");
     Chain1D ch(h, pair, uncond, c, (int64_t)n_seg * B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
-    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || known2_refuse(ks) != 0) return -1;
+    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0 || known2_refuse(ks) != 0) return -1;
     if (known1_refuse(k1, "the parallel time composition hands rows of one segment's state over to the next one's condition at every "
                           "step: a region of one [B, rows, F] state does not name a place in its n_seg * B rows") != 0) return -1;
     REQUIRE(h && pair && c && x && cond && cond_buf && times && coefs && seeds, "null argument");

@@ -10,7 +10,7 @@ What runs where
     between two library calls per step, exactly where the reference takes it.
   * DDIM (``sampling_timesteps < timesteps``, ``ddim_sample`` :1724-1804): unguided = ONE library call
     (``cindm_ddpm1d_sample_ddim``, same captured-step replay with per-step coefficient tables); guided by a ``PointObjective``,
-    a ``WaypointObjective`` or a ``QuadraticObjective`` ("standard" / "standard-alpha" with ``-recurrence-N``) = ONE library call too (``cindm_ddpm1d_sample_ddim_guided``: relaxation
+    a ``WaypointObjective``, a ``QuadraticObjective`` or a ``PairDistanceObjective`` ("standard" / "standard-alpha" with ``-recurrence-N``) = ONE library call too (``cindm_ddpm1d_sample_ddim_guided``: relaxation
     iterations and the DDIM update of (eps + grad, x_start) inside the captured step, state and step state ping-ponged); guided by
     any other callable or guidance (recurrence guidance) = library predictions + the user's gradient per step.
   * autoregressive time composition (``autoregress_time_compose_sample`` :2240-2327): the whole rollout -- every segment's
@@ -33,7 +33,7 @@ from torch import nn
 
 from . import _ffi
 from .diffusion_base import DiffusionHandle
-from .objectives import PointObjective, QuadraticObjective, WaypointObjective
+from .objectives import PairDistanceObjective, PointObjective, QuadraticObjective, WaypointObjective
 from .record import DeviceRecorder, LoopRecorder, record_schedule, stream_mask
 from .schedule import check_solver, make_schedule, ula_schedule
 
@@ -274,7 +274,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
 
     @staticmethod
     def _arm_tables(obj, h, img):
-        """A WaypointObjective's or QuadraticObjective's tables, armed like the recorder: the guided chain call consumes them, so every
+        """A WaypointObjective's, QuadraticObjective's or PairDistanceObjective's tables, armed like the recorder: the guided chain call consumes them, so every
         issue arms again."""
         if obj is not None:
             obj.arm(h, img.shape[0], img.device)
@@ -282,9 +282,9 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
     @staticmethod
     def _builtin(design_fn, design_guidance, B, L, n_bodies):
         """(descriptor, tables) when ``design_fn`` under ``design_guidance`` runs inside the captured step -- a PointObjective whose
-        last_n_step fits the state, a WaypointObjective or a QuadraticObjective -- else (None, None).  A table objective whose tables
+        last_n_step fits the state, a WaypointObjective, a QuadraticObjective or a PairDistanceObjective -- else (None, None).  A table objective whose tables
         do not fit the state [B, L, 4 * n_bodies] is a ValueError on every route, before any device work."""
-        if isinstance(design_fn, (WaypointObjective, QuadraticObjective)):
+        if isinstance(design_fn, (WaypointObjective, QuadraticObjective, PairDistanceObjective)):
             design_fn.check_state(B, L, n_bodies)
             dz = design_fn.descriptor(design_guidance)
             return dz, (design_fn if dz is not None else None)
@@ -649,8 +649,8 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
     def _run_guided_loop(self, img, cond, desc, dz, t_start, t_end, *, noise, seed, sample_offset, inpaint_cond,
                          initial_state_overwrite, use_graph=True, rec=None, tables=None, karm=None):
         """Reverse steps t_start .. t_end guided by the built-in objective as one library call
-        (cindm_ddpm1d_sample_guided); ``noise`` rows (step / recur / cond) are indexed by t.  ``tables``: the WaypointObjective
-        or QuadraticObjective whose descriptor ``dz`` is (modes 3 / 4, 5): every issue of the call arms its tables."""
+        (cindm_ddpm1d_sample_guided); ``noise`` rows (step / recur / cond) are indexed by t.  ``tables``: the WaypointObjective,
+        QuadraticObjective or PairDistanceObjective whose descriptor ``dz`` is (modes 3 / 4, 5, 6): every issue of the call arms its tables."""
         device, B = img.device, img.shape[0]
         cond_d = self._f32(cond, device) if (cond is not None and self.conditioned_steps != 0) else None
         inp = self._f32(inpaint_cond, device)
@@ -979,7 +979,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         Without ``design_fn`` the whole loop is one library call (``cindm_ddpm1d_sample_ddim``); as in the reference the
         prediction then ignores the compose keywords (:1755).  With ``design_fn`` (recurrence guidance only -- the
         reference's non-recurrence branch does not return a noise prediction, :1283) the prediction honours them.  A
-        ``PointObjective`` (last_n_step <= L), ``WaypointObjective`` or ``QuadraticObjective`` under "standard" / "standard-alpha" ``-recurrence-N`` (N >= 1) runs as one library
+        ``PointObjective`` (last_n_step <= L), ``WaypointObjective``, ``QuadraticObjective`` or ``PairDistanceObjective`` under "standard" / "standard-alpha" ``-recurrence-N`` (N >= 1) runs as one library
         chain (``cindm_ddpm1d_sample_ddim_guided``; counter-based draws keyed by (seed, sample_offset + b, t, element) when there
         is no tape); any other callable or guidance: each step is ``recurrence`` library predictions + the user's autograd
         gradient, and the DDIM update of the tiny state runs in torch.

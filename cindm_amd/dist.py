@@ -166,7 +166,7 @@ def sample_sharded(diffusion, batch_size, *, seed, group=None, gather=True, cond
     sample_kw = shard_known1d(sample_kw, batch_size, lo, hi)
     local_cond = None if cond is None else cond[lo:hi]
     design_fn = sample_kw.get("design_fn")
-    if hasattr(design_fn, "shard"):        # an objective with per-design tables (WaypointObjective, QuadraticObjective): each rank takes its slice
+    if hasattr(design_fn, "shard"):        # an objective with per-design tables (WaypointObjective, QuadraticObjective, PairDistanceObjective): each rank takes its slice
         sample_kw = dict(sample_kw, design_fn=design_fn.shard(lo, hi))
     local = diffusion.sample(batch_size=hi - lo, cond=local_cond, seed=seed, sample_offset=lo, **sample_kw)
     return all_gather_designs(local, batch_size, group) if gather else local

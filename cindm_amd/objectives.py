@@ -20,7 +20,12 @@ vector ``h`` per (design | all designs, row), value ``1/2 x^T S x - h^T x`` summ
 ("arrive and stop"), a relation between bodies ("0 and 1 meet", "keep 2 and 3 apart" with a negative weight), the centre of mass or the
 total momentum at a row and any weighted least-squares mix of these are such tables (``from_residuals`` builds them from residuals
 ``a^T x - r``).  Its gradient acts on all four components of a body -- the first built-in objective whose does -- and takes the same
-two library chains (``cindm_ddpm1d_set_design_quadratic``, descriptor mode 5: the guided update compiled with this gradient)."""
+two library chains (``cindm_ddpm1d_set_design_quadratic``, descriptor mode 5: the guided update compiled with this gradient).
+
+``PairDistanceObjective`` states a relation between the positions of two bodies that is not quadratic: a band ``[lo, hi]`` for the
+distance of every (design | all designs, row, pair) with a weight, penalised quadratically outside the band.  "Stay at least d apart"
+(``apart``), "come within d" (``within``) and "meet at distance d" (``at``) are such bands and mix freely in one table; the first and
+the last are non-convex.  It takes the same two library chains (``cindm_ddpm1d_set_design_pairdist``, descriptor mode 6)."""
 import copy
 
 import torch
@@ -415,3 +420,219 @@ class QuadraticObjective:
         batch = B if self.per_design is None else self.per_design
         _ffi.check(_ffi.lib().cindm_ddpm1d_set_design_quadratic(handle, _ffi.ptr(S), int(S.dim() == 4), _ffi.ptr(h), int(h.dim() == 3),
                                                                self.rows, self.features, batch))
+
+
+_PAIR_COUNTS = {nb * (nb - 1) // 2: nb for nb in range(2, 9)}        # P -> n_bodies, 2 .. 8 bodies
+
+
+def pair_index(i, j, n_bodies):
+    """The library's pair order (0,1), (0,2), .., (1,2), ..: the index of pair (i, j), i < j (``pair_index`` in kernels.h)."""
+    return i * n_bodies - (i * (i + 1)) // 2 + (j - i - 1)
+
+
+class PairDistanceObjective:
+    """``lo``, ``hi``, ``weight``: each [L, P] or [B, L, P], P = nb (nb - 1) / 2 pairs (i, j), i < j, in the order of ``pair_index``.
+    0 <= lo <= hi, lo finite, hi finite or +inf; weight finite, >= 0 (0 = no relation at that (row, pair)).  With r the distance
+    between the positions (features 4i, 4i+1 and 4j, 4j+1) of the pair's bodies, the value for pos [B, L, 4 * nb] is
+
+        sum_b sum_l sum_p weight[b | 0, l, p] * ( max(lo[b | 0, l, p] - r, 0)^2 + max(r - hi[b | 0, l, p], 0)^2 )
+        + the time-consistency term of PointObjective
+
+    The penalty is C1 at r = lo and r = hi; its direction is undefined at r = 0, where the gradient is defined as 0: ``__call__`` masks
+    coincident pairs ahead of the square root, so autograd gives 0 there and not NaN, and the kernel and ``closed_form_grad`` skip them.
+
+    What the kernel evaluates (``closed_form_grad`` restates it) at position component c of body i, over the other bodies o in
+    ascending o from 0.f: d = pos_i,c - pos_o,c; r = sqrt(d * d + d' * d') with d' the other component's difference;
+    term = ((((w * 2) * (r - lo)) * d) / r where r < lo, ((((w * 2) * (r - hi)) * d) / r where r > hi, else 0.f, and 0.f where w == 0 or
+    r == 0; g = g + term.  Every difference, product, sum, square root and quotient is rounded once, in the order written."""
+
+    def __init__(self, lo, hi, weight, *, time_consistency_coef=0.0):
+        lo, hi, weight = (torch.as_tensor(v).detach().to("cpu", torch.float32).contiguous() for v in (lo, hi, weight))
+        for name, v in (("lo", lo), ("hi", hi), ("weight", weight)):
+            if v.dim() not in (2, 3) or 0 in v.shape:
+                raise ValueError(f"{name} must be [L, P] or [B, L, P], not {tuple(v.shape)}")
+        if not (tuple(lo.shape[-2:]) == tuple(hi.shape[-2:]) == tuple(weight.shape[-2:])):
+            raise ValueError(f"lo {tuple(lo.shape)}, hi {tuple(hi.shape)} and weight {tuple(weight.shape)} disagree on (L, P)")
+        nB = {v.shape[0] for v in (lo, hi, weight) if v.dim() == 3}
+        if len(nB) > 1:
+            raise ValueError(f"lo, hi and weight disagree on the number of designs: {sorted(nB)}")
+        P = weight.shape[-1]
+        if P not in _PAIR_COUNTS:
+            raise ValueError(f"P = {P}: the pairs of 2 .. 8 bodies are {sorted(_PAIR_COUNTS)}")
+        if not bool(torch.isfinite(lo).all()) or bool((lo < 0).any()):
+            raise ValueError("lo must be finite and >= 0")
+        if not bool((hi >= lo).all()):          # (NaN fails the comparison; +inf passes)
+            raise ValueError("hi must be >= lo (+inf allowed, NaN not)")
+        if not bool(torch.isfinite(weight).all()) or bool((weight < 0).any()):
+            raise ValueError("weight must be finite and >= 0")
+        self.lo, self.hi, self.weight = lo, hi, weight
+        self.time_consistency_coef = float(time_consistency_coef)
+        self._dev = {}
+
+    @staticmethod
+    def _table(d, weight):
+        """``d`` (a number, or a table that broadcasts against weight's [L, P]) as an fp32 table [L, P] or [B, L, P]."""
+        weight = torch.as_tensor(weight)
+        d = torch.as_tensor(d).detach().to("cpu", torch.float32)
+        return d.expand(weight.shape[-2:]).contiguous() if d.dim() < 2 else d
+
+    @classmethod
+    def apart(cls, d, weight, *, time_consistency_coef=0.0):
+        """The pair stays at least ``d`` apart: the band [d, +inf)."""
+        lo = cls._table(d, weight)
+        return cls(lo, torch.full_like(lo, float("inf")), weight, time_consistency_coef=time_consistency_coef)
+
+    @classmethod
+    def within(cls, d, weight, *, time_consistency_coef=0.0):
+        """The pair comes within ``d``: the band [0, d]."""
+        hi = cls._table(d, weight)
+        return cls(torch.zeros_like(hi), hi, weight, time_consistency_coef=time_consistency_coef)
+
+    @classmethod
+    def at(cls, d, weight, *, time_consistency_coef=0.0):
+        """The pair meets at distance exactly ``d``: the band [d, d]."""
+        lo = cls._table(d, weight)
+        return cls(lo, lo.clone(), weight, time_consistency_coef=time_consistency_coef)
+
+    # ------------------------------------------------------------------ shapes
+    @property
+    def rows(self):
+        return self.weight.shape[-2]
+
+    @property
+    def n_bodies(self):
+        return _PAIR_COUNTS[self.weight.shape[-1]]
+
+    @property
+    def per_design(self):
+        """Designs the per-design tables are for, or None when all tables are shared by every design."""
+        for v in (self.lo, self.hi, self.weight):
+            if v.dim() == 3:
+                return v.shape[0]
+        return None
+
+    def check_state(self, B, L, n_bodies):
+        """ValueError unless the tables fit a state [B, L, 4 * n_bodies]."""
+        if self.rows != L:
+            raise ValueError(f"PairDistanceObjective: tables of {self.rows} rows, the state has {L}")
+        if self.n_bodies != n_bodies:
+            raise ValueError(f"PairDistanceObjective: tables of {self.n_bodies} bodies, the state has {n_bodies}")
+        if self.per_design is not None and self.per_design != B:
+            raise ValueError(f"PairDistanceObjective: per-design tables for {self.per_design} designs, the batch has {B} "
+                             "(shard(lo, hi) slices them for a part of the batch)")
+
+    def shard(self, lo, hi):
+        """The objective of designs lo .. hi-1: per-design tables sliced, tables shared by every design passed through."""
+        o = copy.copy(self)
+        o.lo, o.hi, o.weight = (v[lo:hi].contiguous() if v.dim() == 3 else v for v in (self.lo, self.hi, self.weight))
+        o._dev = {}
+        return o
+
+    def tables(self, device):
+        """(band, weight): the two contiguous fp32 tensors on ``device`` (cached per device) the kernel reads.  band [B | -, L, P, 2]
+        holds (lo, hi) interleaved; lo and hi share one per-design flag: where either is per design both are materialised."""
+        device = torch.device(device)
+        if device not in self._dev:
+            lo, hi = self.lo, self.hi
+            if lo.dim() != hi.dim():
+                shape = lo.shape if lo.dim() == 3 else hi.shape
+                lo, hi = lo.expand(shape), hi.expand(shape)
+            self._dev[device] = (torch.stack((lo, hi), dim=-1).contiguous().to(device), self.weight.to(device).contiguous())
+        return self._dev[device]
+
+    # ------------------------------------------------------------------ value and gradient
+    def _pairs(self):
+        nb = self.n_bodies
+        ij = [(i, j) for i in range(nb) for j in range(i + 1, nb)]
+        return torch.tensor([i for i, _ in ij]), torch.tensor([j for _, j in ij])
+
+    def _time_consistency(self, pos, n_bodies):
+        idx = torch.cat([torch.arange(ii * 4, ii * 4 + 2) for ii in range(n_bodies)]).to(pos.device)
+        return (pos[:, 1:, idx] - pos[:, :-1, idx]).square().sum(-1).mean(-1).sum() * self.time_consistency_coef
+
+    def __call__(self, pos):
+        """pos: [B, L, n_bodies*4] -> scalar loss (summed over the batch)."""
+        B, L, F = pos.shape
+        self.check_state(B, L, F // 4)
+        lo, hi, w = self.lo.to(pos), self.hi.to(pos), self.weight.to(pos)
+        I, J = (v.to(pos.device) for v in self._pairs())
+        x = pos.reshape(B, L, F // 4, 4)[..., :2]
+        sq = (x[:, :, I] - x[:, :, J]).square().sum(-1)                  # [B, L, P]
+        # (the square root only sees pairs that are apart: its derivative at 0 is inf, and 0 * inf would reach the gradient; a
+        #  coincident pair has r = 0 as a constant -- the right value, and the zero gradient the kernel defines there)
+        apart = sq > 0
+        r = torch.where(apart, torch.sqrt(torch.where(apart, sq, torch.ones_like(sq))), torch.zeros_like(sq))
+        pen = (lo - r).clamp(min=0).square() + (r - hi).clamp(min=0).square()
+        total = torch.where(w > 0, w * pen, torch.zeros_like(pen)).sum()
+        if self.time_consistency_coef > 0 and L > 1:
+            total = total + self._time_consistency(pos, F // 4)
+        return total
+
+    def closed_form_grad(self, pos):
+        """The gradient of ``__call__`` as compose_update_pair_kernel evaluates it, operation for operation: per position component c
+        of body i, acc = 0; for o = 0 .. nb-1, o != i, with (w, lo, hi) the entry of the pair {i, o}:
+            d = pos_i,c - pos_o,c;  r = sqrt(d_x * d_x + d_y * d_y);
+            term = ((((w * 2) * (r - lo)) * d) / r  where r < lo,  ((((w * 2) * (r - hi)) * d) / r  where r > hi,  else 0;
+            term = 0 where w == 0 or r == 0;  acc = acc + term
+        (each operation rounded once in the dtype of ``pos``), then on position features
+            g = acc + ((tc * 2) * lap) / (L - 1),  lap = (x_l - x_{l-1}) [l >= 1] - (x_{l+1} - x_l) [l + 1 < L]."""
+        B, L, F = pos.shape
+        nb = F // 4
+        self.check_state(B, L, nb)
+        lo, hi, w = (v.to(pos).unsqueeze(-1) for v in (self.lo, self.hi, self.weight))      # [B | -, L, P, 1]
+        x = pos.reshape(B, L, nb, 4)[..., :2]
+        g = torch.zeros_like(x)
+        for i in range(nb):
+            acc = torch.zeros_like(x[:, :, i])
+            for o in range(nb):
+                if o == i:
+                    continue
+                p = pair_index(min(i, o), max(i, o), nb)
+                wp, lop, hip = w[..., p, :], lo[..., p, :], hi[..., p, :]
+                d = x[:, :, i] - x[:, :, o]                                               # [B, L, 2]
+                dd = d * d
+                r = torch.sqrt(dd[..., 0:1] + dd[..., 1:2])
+                below = r < lop
+                active = (wp != 0) & (r != 0) & (below | (r > hip))
+                # (the unselected side may hold inf or NaN -- r - inf, a quotient by 0 -- and is never read)
+                bound = torch.where(below, lop, torch.where(active, hip, r))
+                term = (((wp * 2.0) * (r - bound)) * d) / torch.where(active, r, torch.ones_like(r))
+                acc = acc + torch.where(active, term, torch.zeros_like(term))
+            g[:, :, i] = acc
+        if self.time_consistency_coef > 0 and L > 1:
+            lap = torch.zeros_like(x)
+            lap[:, 1:] += x[:, 1:] - x[:, :-1]
+            lap[:, :-1] -= x[:, 1:] - x[:, :-1]
+            g = g + self.time_consistency_coef * 2.0 * lap / float(L - 1)
+        out = torch.zeros_like(pos).reshape(B, L, nb, 4)
+        out[..., :2] = g
+        return out.reshape(B, L, F)
+
+    def descriptor(self, design_guidance):
+        """cindm_design_desc (mode 6: the tables are armed per call) for this objective under ``design_guidance``, or None when that
+        guidance needs the generic (autograd) path."""
+        g = design_guidance
+        rec = 0
+        if "recurrence" in g:
+            try:
+                rec = int(g.split("-")[-1])
+            except ValueError:
+                return None
+            g = g[:g.index("-recurrence")]
+            if rec < 1:
+                return None
+        if g not in ("standard", "standard-alpha"):
+            return None
+        d = _ffi.DesignDesc()
+        d.mode = 6
+        d.alpha = int(g == "standard-alpha")
+        d.recurrence, d.time_consistency_coef = rec, self.time_consistency_coef
+        return d
+
+    def arm(self, handle, B, device):
+        """Arms the next guided chain call on ``handle`` (a cindm_ddpm1d) with this objective's tables, for a batch of ``B`` designs
+        (per-design tables declare their own extent: the chain call refuses another batch)."""
+        band, weight = self.tables(device)
+        batch = B if self.per_design is None else self.per_design
+        _ffi.check(_ffi.lib().cindm_ddpm1d_set_design_pairdist(handle, _ffi.ptr(band), int(band.dim() == 4), _ffi.ptr(weight),
+                                                              int(weight.dim() == 3), self.rows, self.n_bodies, batch))

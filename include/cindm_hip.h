@@ -271,9 +271,13 @@ int  cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* unco
  *   (+ the time-consistency term); in these modes last_n_step, coef and pos_target are not read.
  * Mode 5 is the quadratic objective, read from device tables as well (cindm_ddpm1d_set_design_quadratic below):
  *   sum_b sum_l ( 1/2 x[b, l]^T S[b | 0, l] x[b, l] - h[b | 0, l]^T x[b, l] )     over all F = 4 * n_bodies features of a row
- *   (+ the time-consistency term, on the position channels); last_n_step, coef and pos_target are not read either. */
+ *   (+ the time-consistency term, on the position channels); last_n_step, coef and pos_target are not read either.
+ * Mode 6 is the pair-distance objective, read from device tables as well (cindm_ddpm1d_set_design_pairdist below):
+ *   sum_b sum_l sum_p weight[b | 0, l, p] * ( max(lo[b | 0, l, p] - r, 0)^2 + max(r - hi[b | 0, l, p], 0)^2 )
+ *   with r the distance between the positions of the bodies of pair p at row l (+ the time-consistency term); last_n_step, coef and
+ *   pos_target are not read either. */
 typedef struct {
-    int32_t mode;               /* 1 = "L2", 2 = "L2square"; 3 = table "L2", 4 = table "L2square"; 5 = quadratic tables */
+    int32_t mode;               /* 1 = "L2", 2 = "L2square"; 3 = table "L2", 4 = table "L2square"; 5 = quadratic tables; 6 = pair-distance tables */
     int32_t alpha;              /* 0: "standard" (gradient as is), 1: "standard-alpha" (x eta_t)   :1243-1248 */
     int32_t recurrence;         /* 0: non-recurrence branch; N >= 1: "-recurrence-N"                :1284-1370 */
     int32_t last_n_step;
@@ -515,6 +519,34 @@ int  cindm_ddpm1d_set_design_tables(cindm_ddpm1d* h, const float* target, int32_
 int  cindm_ddpm1d_set_design_quadratic(cindm_ddpm1d* h, const float* S, int32_t S_per_design,
                                        const float* hvec, int32_t h_per_design,
                                        int32_t rows, int32_t features, int64_t batch);
+
+/* The pair-distance objective's tables (cindm_design_desc mode 6).  No reference counterpart.  A relation between the positions of two
+ * bodies that is not quadratic -- "stay at least d apart" (lo = d, hi = +inf), "come within d" (lo = 0, hi = d), "meet at distance d"
+ * (lo = hi = d) -- is one (lo, hi, weight) entry per (design | all designs, row, pair); relations mix freely in one table.
+ * Pairs p = (i, j), i < j, are ordered (0,1), (0,2), .., (1,2), ..: p = i * n_bodies - i (i + 1) / 2 + (j - i - 1); P = n_bodies (n_bodies - 1) / 2.
+ * band:   DEVICE floats [batch, rows, P, 2] when band_per_design, else [rows, P, 2] shared by every design: (lo, hi) interleaved,
+ *         0 <= lo <= hi, lo finite, hi finite or +inf.
+ * weight: DEVICE floats [batch, rows, P] when weight_per_design, else [rows, P]; finite, >= 0.
+ * The update kernel (compose_update_pair_kernel, the guided update compiled with this gradient) evaluates at the position component
+ * c (0: x, 1: y) of body i at (b, l), from g = 0.f over the other bodies o in ascending o, g = g + term(i, o):
+ *   d  = x[b, l, 4 i + c] - x[b, l, 4 o + c],   d' = the same difference of the other position component,
+ *   r  = sqrt(d * d + d' * d'),
+ *   term = ((((w * 2) * (r - lo)) * d) / r  where r < lo,   ((((w * 2) * (r - hi)) * d) / r  where r > hi,   0.f otherwise,
+ * and 0.f where w == 0 or r == 0 (w, lo, hi: the entry of the pair {i, o}); every difference, product, sum, square root and quotient
+ * is rounded once to fp32 (no contraction), in the order written.  Velocity components get no term.  Then the time-consistency term,
+ * the standard-alpha factor and the rest of the guided update as for modes 1 - 5.  The gradient reads the element's own row of x only.
+ * cindm_ddpm1d_set_design_pairdist arms the NEXT chain call on this handle (n_bodies in 2 .. 8); that call consumes the tables whether
+ * it succeeds or fails, and (NULL, NULL) disarms.  cindm_ddpm1d_sample_guided / _sample_ddim_guided check rows == L_tot, n_bodies ==
+ * c->n_bodies and batch == B before they launch or copy anything, under every compose mode they serve, and _sample_ddim_guided also
+ * with the multistep solver armed (compose_update_pair_kernel<true>).  They refuse mode 6 with nothing armed, armed pair-distance tables
+ * with modes 1 - 5, and the tables of cindm_ddpm1d_set_design_tables or cindm_ddpm1d_set_design_quadratic with mode 6; every other
+ * chain entry -- the unguided 1-D chains, the rollout, the time composition, the Langevin chain and all 2-D chains -- refuses armed
+ * pair-distance tables and says why.  A refusal leaves the handle usable.  Lifetime and capture as for the quadratic tables: caller-owned,
+ * alive and unchanged until the chain's work has finished; the two addresses and the two flags are operands of the captured update, so
+ * a call with other tables captures its step again.  The workspace size does not change. */
+int  cindm_ddpm1d_set_design_pairdist(cindm_ddpm1d* h, const float* band, int32_t band_per_design,
+                                      const float* weight, int32_t weight_per_design,
+                                      int32_t rows, int32_t n_bodies, int64_t batch);
 
 /* Replacement conditioning of the 2-D chains: a known region of the state [B * nb, H * W, CP] is held on the forward-diffusion
  * trajectory of its clean values and returned exactly (known2d_kernel: one more node of the captured step, after the step's
