@@ -359,6 +359,10 @@ static int run_step(const Chain1D& ch, const StepIO& io, int32_t t, const int32_
         TimeComposeArgs u = *io.tc;
         u.c = a;
         hipLaunchKernelGGL(timecompose_update_kernel, dim3((unsigned)((ne / 4 + 255) / 256)), dim3(256), 0, stream, u);
+    } else if (io.ddim_tab && !guided && a.objective != 0 && a.clip) {
+        // the unguided DDIM update under pred_x0 / pred_v with the clamp on: pred_noise re-derived from the clamped x_start, as
+        // model_predictions(clip_x_start = True) does (never fused: the fused update serves pred_noise only)
+        launch_compose_update_clamped(a, io.ms_hist, ne, stream);
     } else if (io.ms_hist && io.ddim_tab && !(guided && io.relax)) {
         // the multistep solver's update (never fused; a relaxation iteration is not an update and keeps the kernels below)
         if ((a.dz_mode & kDzModeMask) == 6) launch_compose_update_pair(a, io.ms_hist, ne, stream);

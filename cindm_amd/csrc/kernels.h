@@ -3569,8 +3569,12 @@ __global__ void compose_gather_kernel(const ComposeArgs a) {
 // kMulti: the DDIM update carries the second-order multistep term: v = v + kappa (x0 - hist[i]) with kappa = the 4th word
 // of the step's table row, each operation rounded once, ahead of the inpainting overwrite; kappa == 0 does not read the history; the
 // update -- never a relaxation iteration -- writes x0 to hist[i].  One thread reads and writes one element: in place is safe.
+// kClampedEps: the unguided DDIM update under pred_x0 / pred_v with the clamp on.  ddim_sample hands clip_x_start = clip_denoised to
+// model_predictions (:1755), which re-derives pred_noise from the CLAMPED x_start (:1018-1027); eps of the branches below is
+// p_mean_variance's, from the unclamped one (the guided chain's DDIM return and every predict caller keep it).  An instantiation of
+// its own (compose_update_clamped_kernel in kernels_tail.h), so that the other kernels are the code they were.
 constexpr int kObjPosition = 0, kObjQuad = 1, kObjPair = 2;
-template <int kObj, bool kMulti = false>
+template <int kObj, bool kMulti = false, bool kClampedEps = false>
 __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_t i, float* hist = nullptr) {
     const int Lfull = a.Ltot + a.cond_steps;
     const int t = step_scalar(a.t_ptr, a.t_imm);
@@ -3812,6 +3816,7 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
             const float san = a.ddim_tab[4 * sidx], cc = a.ddim_tab[4 * sidx + 1], sg = a.ddim_tab[4 * sidx + 2];
             const float z = a.noise ? a.noise[(size_t)sidx * a.noise_t_stride + i]
                             : (sg != 0.f ? counter_normal(dseed, (uint64_t)(dsoff + b), (uint32_t)t, el) : 0.f);
+            if constexpr (kClampedEps) { if (a.objective != 0 && a.clip) eps = (ra * xv - x0) / rb; }
             v = __fadd_rn(__fadd_rn(__fmul_rn(x0, san), __fmul_rn(cc, eps)), __fmul_rn(sg, z));
             if constexpr (kMulti) {
                 const float kap = a.ddim_tab[4 * sidx + 3];
@@ -3862,6 +3867,8 @@ __global__ void compose_update_quad_kernel(const ComposeArgs a) {
 // unit includes that file last and the kernel is a template first used there, so the code object holds the two behind every kernel
 // that exists and those keep their places in it (4.5r has what moving them may cost).  hist: null for the guided update.
 void launch_compose_update_pair(const ComposeArgs& a, float* hist, int64_t n_elements, hipStream_t stream);
+// the unguided DDIM update with pred_noise re-derived from the clamped x_start (kClampedEps), with or without the multistep term: likewise
+void launch_compose_update_clamped(const ComposeArgs& a, float* hist, int64_t n_elements, hipStream_t stream);
 
 // the DDIM updates of a chain that runs the second-order multistep solver: instantiations of their own, so that the two
 // kernels above are the code they were.  Launched for a step's update only -- a guided step's relaxation iterations keep the kernels

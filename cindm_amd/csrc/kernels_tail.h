@@ -20,4 +20,17 @@ void launch_compose_update_pair(const ComposeArgs& a, float* hist, int64_t n_ele
     else hipLaunchKernelGGL(compose_update_pair_kernel<false>, grid, dim3(256), 0, stream, a, (float*)nullptr);
 }
 
+// the unguided DDIM update under pred_x0 / pred_v with the clamp on (compose_update_body's kClampedEps; kMulti: under the multistep
+// solver): the host launches it for that combination only, and never fused
+template <bool kMulti>
+__global__ void compose_update_clamped_kernel(const ComposeArgs a, float* hist) {
+    compose_update_body<kObjPosition, kMulti, true>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, hist);
+}
+
+void launch_compose_update_clamped(const ComposeArgs& a, float* hist, int64_t n_elements, hipStream_t stream) {
+    const dim3 grid((unsigned)((n_elements + 255) / 256));
+    if (hist) hipLaunchKernelGGL(compose_update_clamped_kernel<true>, grid, dim3(256), 0, stream, a, hist);
+    else hipLaunchKernelGGL(compose_update_clamped_kernel<false>, grid, dim3(256), 0, stream, a, (float*)nullptr);
+}
+
 }  // namespace cindm
