@@ -1,22 +1,23 @@
 // The chain driver: what every sampling entry (cindm_ddpm1d_sample*, cindm_ddpm2d_sample*) does around its own step.
 // Textually included by cindm_hip.hip after the 1-D U-Net's host code and before ddpm1d_host.inc and the 2-D host files; each piece
 // exists once.
-//   RecSpec, DesignTables, QuadTables, PairTables, cindm_ddpm1d, KeyBuilder   the schedule handle both sides run on, with what a chain call arms on it
+//   RecSpec, DesignTables, Known2D, Known1D, Multistep, Armed, cindm_ddpm1d, KeyBuilder   the schedule handle both sides run on, with what a
+//                       chain call arms on it
 //   chain_stream        which stream a chain runs on
 //   stream_steps        the eager loop
 //   graph_capture/_run  capture a step functor into an instantiated graph; launch it n times and synchronise
 //   replay_once         the 2-D chains' replay: stream_steps, or capture + run + destroy (no cache)
 //   upload_ddim_tables  schedule check + the DDIM loops' per-step device tables
-//   RecScope            the chain recorder: taken by every chain entry
-//   DesignTablesScope   the waypoint objective's tables: taken by every 1-D chain entry, run by the two guided ones
-//   QuadTablesScope     the quadratic objective's tables: taken by every chain entry, run by the two guided 1-D ones
-//   PairTablesScope     the pair-distance objective's tables: taken by every chain entry, run by the two guided 1-D ones
-//   Known2DScope        the 2-D chains' known region: taken by every chain entry, run by the four 2-D ones
-//   Known1DScope        the 1-D chains' known region: taken by every chain entry, run by cindm_ddpm1d_sample / _sample_guided /
-//                       _sample_ddim / _sample_ddim_guided
-//   MultistepScope      the second-order multistep solver: taken by every chain entry, run by cindm_ddpm1d_sample_ddim /
-//                       _sample_ddim_guided and cindm_ddpm2d_sample_ddim / _sample_ddim_force (bottom of this file)
-// On top of these, the six 1-D entries (ddpm1d_host.inc) state their own facts once in Chain1D (the workspace layout), step1_refuse /
+//   ChainArmed          everything armed on the handle -- the recorder, the three table objectives' tables, the 2-D and the 1-D known
+//                       region, the multistep solver -- taken by every chain entry, 1-D or 2-D, as its first statement; the entry
+//                       states what of it it serves (refuse_all_but) and refuses the rest
+//   rec_*               the chain recorder: run by every entry but the rollout and the Langevin chain
+//   design_*            the table objectives (waypoint, quadratic, pair-distance): run by the two guided 1-D entries
+//   Known2D / Known1D   the known regions: run by the four 2-D entries / by cindm_ddpm1d_sample / _sample_guided / _sample_ddim /
+//                       _sample_ddim_guided
+//   ms_*                the second-order multistep solver: run by cindm_ddpm1d_sample_ddim / _sample_ddim_guided and
+//                       cindm_ddpm2d_sample_ddim / _sample_ddim_force (bottom of this file)
+// On top of these, the 1-D entries (ddpm1d_host.inc, timecompose_host.inc) state their own facts once in Chain1D (the workspace layout), step1_refuse /
 // chain1_refuse / guided_refuse, chain_io, ddim_tables1, loop_chain and guided_chain, and the four 2-D entries (ddpm2d_host.inc)
 // theirs in Chain2D (the workspace layout), chain2_refuse / force_refuse, ForceGuide, ddim_args2, ddpm_step2 / ddim_step2 and run_chain2.
 // The 1-D replay (replay_steps in ddpm1d_host.inc: graph cached in the handle by key, ping-pong pair + odd tail, flag polls) is built
@@ -26,24 +27,16 @@
 struct RecSpec {
     float* buf = nullptr; int64_t buf_floats = 0; int every = 0, streams = 0;
     int n = 0; int64_t fpr = 0; float* x0_stage = nullptr;
+    bool on() const { return buf != nullptr; }
 };
 
-// The waypoint objective's device tables as armed by the caller (cindm_ddpm1d_set_design_tables, below)
+// The device tables of a table objective as armed by the caller (cindm_ddpm1d_set_design_tables / _quadratic / _pairdist, below).
+// kind: an index into kDesignKinds; (a, b) are (target, scale), (S, h) or (band, weight); width counts what that kind's facts say.
+enum { kWaypoint = 0, kQuadratic = 1, kPairDist = 2, kNumDesignKinds = 3 };
 struct DesignTables {
-    const float* target = nullptr; const float* scale = nullptr; int target_per_design = 0, scale_per_design = 0;
-    int rows = 0, n_bodies = 0; int64_t batch = 0;
-};
-
-// The quadratic objective's device tables as armed by the caller (cindm_ddpm1d_set_design_quadratic, below)
-struct QuadTables {
-    const float* S = nullptr; const float* h = nullptr; int S_per_design = 0, h_per_design = 0;
-    int rows = 0, features = 0; int64_t batch = 0;
-};
-
-// The pair-distance objective's device tables as armed by the caller (cindm_ddpm1d_set_design_pairdist, below)
-struct PairTables {
-    const float* band = nullptr; const float* weight = nullptr; int band_per_design = 0, weight_per_design = 0;
-    int rows = 0, n_bodies = 0; int64_t batch = 0;
+    int kind = 0; const float* a = nullptr; const float* b = nullptr; int a_per_design = 0, b_per_design = 0;
+    int rows = 0, width = 0; int64_t batch = 0;
+    bool on() const { return a != nullptr; }
 };
 
 // The known region of a 2-D chain as armed by the caller (cindm_ddpm1d_set_known2d, below: known .. cp) and as one chain runs it
@@ -53,6 +46,7 @@ struct Known2D {
     const float* zi_state = nullptr; const float* zi_bound = nullptr; const float* z_state = nullptr; const float* z_bound = nullptr;
     int64_t zs_stride = 0, zb_stride = 0, images = 0; int hw = 0, cp = 0;
     const int* tnext = nullptr; uint64_t seed = 0; int64_t sample_off = 0;
+    bool on() const { return known != nullptr; }
 };
 
 // The known region of a 1-D chain as armed by the caller (cindm_ddpm1d_set_known1d, below) and checked against the chain's state by
@@ -61,12 +55,20 @@ struct Known1D {
     const float* known = nullptr; const unsigned char* mask = nullptr; int known_per_design = 0, mask_per_design = 0;
     const float* z_init = nullptr; const float* z_step = nullptr; const float* z_recur = nullptr;
     int64_t step_stride = 0, recur_stride = 0, batch = 0; int rows = 0, feats = 0, apply_init = 1;
+    bool on() const { return known != nullptr; }
 };
 
 // The second-order multistep solver as armed by the caller (cindm_ddpm1d_set_multistep, bottom of this file): the per-step kappa
 // (a host copy: the entry puts it beside its DDIM tables) and the caller's history buffer, shaped like the chain's state
 struct Multistep {
     std::vector<float> kappa; float* hist = nullptr; int64_t hist_floats = 0;
+    bool on() const { return hist != nullptr; }
+};
+
+// Everything a caller can arm on the handle for the next chain call (one slot per kind of table objective: two kinds can be armed
+// at once, and a guided entry says which one does not fit).  ChainArmed, below, is how a chain entry takes it.
+struct Armed {
+    RecSpec rec; DesignTables tables[kNumDesignKinds]; Known2D kn; Known1D kn1; Multistep ms;
 };
 
 struct cindm_ddpm1d {
@@ -80,21 +82,12 @@ struct cindm_ddpm1d {
     int last_step_launches = 0, last_step_fused = 0;     // what the last emitted reverse step consisted of (cindm_ddpm1d_last_step_info)
     int last_chain_recovered = 0, last_chain_crowded = 0, last_chain_in_flight = 0, last_chain_range = 0;     // cindm_ddpm1d_last_chain_info
     hipGraph_t graph1 = nullptr; hipGraphExec_t gexec1 = nullptr;      // ping-pong loops: the one-step graph that ends an odd count
-    // the chain recorder (cindm_ddpm1d_set_recorder): what the next chain call will take, the one a running chain
-    // records with (null: none) and what the last chain wrote (cindm_ddpm1d_recorder_info)
-    RecSpec rec_armed; const RecSpec* rec = nullptr; int rec_info[4] = {0, 0, 0, 0};
-    // the design tables: what the next chain call will take, and the ones a running guided chain reads (null: none)
-    DesignTables dzt_armed; const DesignTables* dzt = nullptr;
-    // the quadratic objective's tables, likewise
-    QuadTables qdt_armed; const QuadTables* qdt = nullptr;
-    // the pair-distance objective's tables, likewise
-    PairTables pdt_armed; const PairTables* pdt = nullptr;
-    // the known region of the 2-D chains: what the next chain call will take, and the one a running 2-D chain holds (null: none)
-    Known2D kn_armed; const Known2D* kn = nullptr;
-    // the known region of the 1-D chains, likewise
-    Known1D kn1_armed; const Known1D* kn1 = nullptr;
-    // the multistep solver: what the next chain call will take, and the one a running DDIM chain applies (null: none)
-    Multistep ms_armed; const Multistep* ms = nullptr;
+    Armed armed;                        // what the next chain call will take (the cindm_ddpm1d_set_* entries write it)
+    int rec_info[4] = {0, 0, 0, 0};     // what the last chain recorded (cindm_ddpm1d_recorder_info)
+    // what the running chain holds of what it took (null: none): its recorder, the tables of its objective, its known region (2-D,
+    // 1-D), its multistep solver.  They point into the entry's ChainArmed, which clears them when the entry returns.
+    const RecSpec* rec = nullptr; const DesignTables* dzt = nullptr; const Known2D* kn = nullptr; const Known1D* kn1 = nullptr;
+    const Multistep* ms = nullptr;
     void drop_graph() {
         if (gexec) (void)hipGraphExecDestroy(gexec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -192,29 +185,41 @@ static int upload_ddim_tables(int T, int32_t n_steps, const int32_t* times, cons
     return 0;
 }
 
+// ---- what a chain call takes (the rule of everything armed) ---------------------------------------------------------------------------
+// The cindm_ddpm1d_set_* entries arm the handle.  The next chain entry, 1-D or 2-D, takes ALL of it with a ChainArmed as its first
+// statement -- so the call consumes what was armed however it ends -- and then either runs with a thing or refuses it with the
+// reason: refuse_all_but names what the entry serves, and the served things are checked against the chain by their *_begin
+// (rec_begin, design_begin, known1_begin, known2_begin, ms_begin), which hand them to the handle's running-chain pointers for the
+// whole call, the recovery re-run included.  The destructor clears those pointers.  (The recorder is taken by every entry; the two
+// that do not record refuse it themselves, with their own reason.)
+enum : unsigned { kServesTables = 1, kServesKnown2 = 2, kServesKnown1 = 4, kServesMultistep = 8 };
+
+struct ChainArmed : Armed {
+    cindm_ddpm1d* h;
+    explicit ChainArmed(cindm_ddpm1d* h_) : h(h_) {
+        if (!h) return;
+        static_cast<Armed&>(*this) = std::move(h->armed); h->armed = Armed();
+        for (int& v : h->rec_info) v = 0;
+    }
+    ~ChainArmed() { if (h) { h->rec = nullptr; h->dzt = nullptr; h->kn = nullptr; h->kn1 = nullptr; h->ms = nullptr; } }
+    ChainArmed(const ChainArmed&) = delete;
+    ChainArmed& operator=(const ChainArmed&) = delete;
+    // the refusal of the first armed thing that `serves` does not name, in one order for every entry: waypoint, quadratic and
+    // pair-distance tables, 2-D known region, 1-D known region (why_known1: the entry's reason), multistep solver
+    int refuse_all_but(unsigned serves, const char* why_known1 = nullptr) const;
+};
+
 // ---- the chain recorder (DESIGN 4.5l) --------------------------------------------------------------------------------------------------
-// cindm_ddpm1d_set_recorder arms the handle; the next chain entry takes the recorder with RecScope as its first statement -- so the
-// call consumes it however it ends -- and either refuses it or runs with it:
+// cindm_ddpm1d_set_recorder arms the handle; a chain entry either refuses the recorder it took or runs with it:
 //   rec_begin   checks it against the chain (steps, floats per record) before the entry's first launch or copy
 //   rec_arm     writes the device descriptor; part of what a chain body does after it has set the step state, so a re-run re-arms
 //   rec_node    the step's chain_record_kernel launch (captured with the step)
 //   rec_done    what cindm_ddpm1d_recorder_info reports
-struct RecScope {
-    cindm_ddpm1d* h; RecSpec r;
-    explicit RecScope(cindm_ddpm1d* h_) : h(h_) {
-        if (!h) return;
-        r = h->rec_armed; h->rec_armed = RecSpec();
-        for (int& v : h->rec_info) v = 0;
-    }
-    ~RecScope() { if (h) h->rec = nullptr; }
-    bool on() const { return r.buf != nullptr; }
-};
-
 static int64_t rec_records(int64_t n, int every) { return (n + every - 1) / every; }
 
-static int rec_begin(RecScope& rs, const float* x, int n_steps, int64_t fpr, const char* x0_refusal = nullptr) {
-    if (!rs.on()) return 0;
-    RecSpec& r = rs.r;
+static int rec_begin(ChainArmed& took, const float* x, int n_steps, int64_t fpr, const char* x0_refusal = nullptr) {
+    if (!took.rec.on()) return 0;
+    RecSpec& r = took.rec;
     REQUIRE(n_steps >= 1 && fpr > 0, "recorder: empty chain");
     REQUIRE(((uintptr_t)x & 15) == 0, "recorder: the state x must be 16-byte aligned (the record node reads it 16 bytes per lane)");
     r.every = std::min(r.every, n_steps);      // the same records (every >= n: the result alone), and the kernel's step arithmetic stays small
@@ -227,7 +232,7 @@ static int rec_begin(RecScope& rs, const float* x, int n_steps, int64_t fpr, con
                     " (ceil(steps / every) records x streams x floats per record, plus one staging record for x0)");
     r.n = n_steps; r.fpr = fpr;
     r.x0_stage = (r.streams & 2) ? r.buf + rec_records(n_steps, r.every) * ns * fpr : nullptr;
-    rs.h->rec = &rs.r;
+    took.h->rec = &took.rec;
     return 0;
 }
 
@@ -263,16 +268,16 @@ static int rec_node(cindm_ddpm1d* h, const float* state, int slot, hipStream_t s
     return 0;
 }
 
-static int rec_done(RecScope& rs, int rc) {
-    if (rs.on() && rc == 0) {
-        const RecSpec& r = rs.r;
-        rs.h->rec_info[0] = (int)rec_records(r.n, r.every); rs.h->rec_info[1] = (int)r.fpr; rs.h->rec_info[2] = r.n; rs.h->rec_info[3] = r.streams;
+static int rec_done(ChainArmed& took, int rc) {
+    if (took.rec.on() && rc == 0) {
+        const RecSpec& r = took.rec; int* info = took.h->rec_info;
+        info[0] = (int)rec_records(r.n, r.every); info[1] = (int)r.fpr; info[2] = r.n; info[3] = r.streams;
     }
     return rc;
 }
 
 extern "C" int cindm_ddpm1d_set_recorder(cindm_ddpm1d* h, float* buf, int64_t buf_floats, int32_t every, int32_t streams) {
-    if (h) h->rec_armed = RecSpec();      // (a refused call leaves the handle disarmed)
+    if (h) h->armed.rec = RecSpec();      // (a refused call leaves the handle disarmed)
     if (buf) {
         REQUIRE(every >= 1, "recorder: every must be >= 1");
         REQUIRE(streams >= 1 && (streams & ~3) == 0, "recorder: unknown stream bit (1 = x, 2 = x0)");
@@ -280,7 +285,8 @@ extern "C" int cindm_ddpm1d_set_recorder(cindm_ddpm1d* h, float* buf, int64_t bu
     }
     REQUIRE(h, "null handle");
     if (!buf) return 0;
-    h->rec_armed.buf = buf; h->rec_armed.buf_floats = buf_floats; h->rec_armed.every = every; h->rec_armed.streams = streams;
+    RecSpec& r = h->armed.rec;
+    r.buf = buf; r.buf_floats = buf_floats; r.every = every; r.streams = streams;
     return 0;
 }
 
@@ -290,215 +296,131 @@ extern "C" int cindm_ddpm1d_recorder_info(const cindm_ddpm1d* h, int32_t info[4]
     return 0;
 }
 
-// ---- the waypoint objective's tables (DESIGN 4.5m) -------------------------------------------------------------------------------------
-// cindm_ddpm1d_set_design_tables arms the handle; like the recorder, the next chain entry takes the tables with DesignTablesScope --
-// so the call consumes them however it ends -- and either refuses them (dzt_refuse: every chain that is not guided) or checks them
-// against its descriptor and state (dzt_begin) and runs with them: run_step reads h->dzt for the whole call, the re-run included.
-struct DesignTablesScope {
-    cindm_ddpm1d* h; DesignTables t;
-    explicit DesignTablesScope(cindm_ddpm1d* h_) : h(h_) {
-        if (!h) return;
-        t = h->dzt_armed; h->dzt_armed = DesignTables();
-    }
-    ~DesignTablesScope() { if (h) h->dzt = nullptr; }
-    bool on() const { return t.target != nullptr; }
+// ---- the table objectives: waypoint (DESIGN 4.5m), quadratic (4.5q), pair-distance (4.5s) ----------------------------------------------
+// cindm_ddpm1d_set_design_tables / _quadratic / _pairdist arm the handle, one slot per kind.  An entry either refuses the tables it
+// took (design_refuse, through refuse_all_but: every chain that is not guided) or checks them against its descriptor and state
+// (design_begin) and runs with the kind its descriptor's mode reads: run_step reads h->dzt for the whole call, the re-run included.
+// What differs between the kinds is data: the modes that read them, how messages name the kind and its two tables, what `width`
+// counts, the alignment the update kernel needs and the ComposeArgs operands the tables become.
+struct DesignKind {
+    int mode_lo, mode_hi; const char* modes;               // the descriptor modes that read these tables, and as messages write them
+    const char* label;                                     // the kind in messages
+    const char* a_name; const char* b_name;                // its two tables
+    const char* reads;                                     // the two as "mode N reads .. from tables" names them
+    const char* setter;
+    const char* noun; int per_body; const char* fits;      // width: what it counts, how many a body has, what it is held against
+    const char* rows_rule; const char* width_rule;         // the setter's range refusals (the setter states the width's range itself)
+    int align;                                             // bytes, of both tables
+    const char* readers;                                   // who reads them, as the refusal of every other entry says it
+    const char* lower_modes;                               // armed under a mode below its own: what those modes are
+    const char* armed_as; const char* tables_of;           // armed under a mode above its own: its name there / as such a refusal names that mode's reader
+    const float* ComposeArgs::*arg_a; const float* ComposeArgs::*arg_b;
+};
+static const DesignKind kDesignKinds[kNumDesignKinds] = {
+    {3, 4, "3 / 4", "design tables", "target", "scale", "its target and scale", "cindm_ddpm1d_set_design_tables",
+     "bodies", 1, "the composition has ", "rows, n_bodies and batch must be >= 1", "rows, n_bodies and batch must be >= 1", 16,
+     "guided chains", "1 / 2 (the point objective, which reads none)", "design tables (target, scale)", nullptr,
+     &ComposeArgs::dz_target, &ComposeArgs::dz_scale},
+    {5, 5, "5", "quadratic design tables", "S", "h", "S and h", "cindm_ddpm1d_set_design_quadratic",
+     "features", 4, "the composition's state has ", "rows and batch must be >= 1", "features must be a multiple of 4 in 4 .. 32", 16,
+     "guided 1-D chains", "1 .. 4 (the point and waypoint objectives, which do not read them)", "quadratic design tables",
+     "quadratic tables of cindm_ddpm1d_set_design_quadratic", &ComposeArgs::dz_S, &ComposeArgs::dz_h},
+    {6, 6, "6", "pair-distance design tables", "band", "weight", "band and weight", "cindm_ddpm1d_set_design_pairdist",
+     "bodies", 1, "the composition has ", "rows and batch must be >= 1", "n_bodies must be in 2 .. 8", 4,
+     "guided 1-D chains", "1 .. 5 (the point, waypoint and quadratic objectives, which do not read them)", nullptr,
+     "pair-distance tables of cindm_ddpm1d_set_design_pairdist", &ComposeArgs::dz_band, &ComposeArgs::dz_weight},
 };
 
-static int dzt_refuse(const DesignTablesScope& ts) {
-    REQUIRE(!ts.on(), "design tables: only the guided chains (cindm_ddpm1d_sample_guided / _sample_ddim_guided) read them; the tables were dropped");
+// the kind whose tables a descriptor mode reads, or -1 (the point objective's modes read none)
+static int design_kind_of(int mode) {
+    for (int kind = 0; kind < kNumDesignKinds; ++kind)
+        if (mode >= kDesignKinds[kind].mode_lo && mode <= kDesignKinds[kind].mode_hi) return kind;
+    return -1;
+}
+
+static int design_refuse(const ChainArmed& took) {
+    for (int kind = 0; kind < kNumDesignKinds; ++kind) {
+        const DesignKind& k = kDesignKinds[kind];
+        if (took.tables[kind].on())
+            return fail(std::string(k.label) + ": only the " + k.readers + " (cindm_ddpm1d_sample_guided / _sample_ddim_guided) read them; the tables were dropped");
+    }
     return 0;
 }
 
-static int dzt_begin(DesignTablesScope& ts, const cindm_design_desc* dz, int Ltot, int n_bodies, int64_t B) {
-    const DesignTables& t = ts.t;
-    if (dz->mode == 5) {
-        REQUIRE(!ts.on(), "design tables (target, scale) are armed but the descriptor's mode is 5, which reads the quadratic tables of "
-                          "cindm_ddpm1d_set_design_quadratic; the tables were dropped");
-        return 0;
+// For each kind: when it serves dz->mode it must be armed and fit the state, otherwise it must not be armed.
+// x, x2: the state buffers the guided update reads a row of as float4 (x2: the guided DDIM chain's second buffer, or null)
+static int design_begin(ChainArmed& took, const cindm_design_desc* dz, int Ltot, int n_bodies, int64_t B, const float* x, const float* x2) {
+    for (int kind = 0; kind < kNumDesignKinds; ++kind) {
+        const DesignKind& k = kDesignKinds[kind]; const DesignTables& t = took.tables[kind];
+        const std::string label = k.label;
+        if (design_kind_of(dz->mode) != kind) {
+            if (!t.on()) continue;
+            if (dz->mode > k.mode_hi)
+                return fail(std::string(k.armed_as) + " are armed but the descriptor's mode is " + std::to_string(dz->mode) + ", which reads the " +
+                            kDesignKinds[design_kind_of(dz->mode)].tables_of + "; the tables were dropped");
+            return fail(label + " are armed but the descriptor's mode is " + k.lower_modes + "; the tables were dropped");
+        }
+        if (!t.on())
+            return fail(std::string("design objective mode ") + k.modes + " reads " + k.reads + " from tables: arm them with " + k.setter + " before the chain call");
+        if (t.rows != Ltot)
+            return fail(label + ": " + std::to_string(t.rows) + " rows, the state has " + std::to_string(Ltot));
+        if (t.width != k.per_body * n_bodies)
+            return fail(label + ": " + std::to_string(t.width) + " " + k.noun + ", " + k.fits + std::to_string(k.per_body * n_bodies));
+        if (t.batch != B)
+            return fail(label + ": made for a batch of " + std::to_string(t.batch) + ", the chain runs " + std::to_string(B));
+        if ((((uintptr_t)t.a | (uintptr_t)t.b) & (uintptr_t)(k.align - 1)) != 0)
+            return fail(label + ": " + k.a_name + " and " + k.b_name + " must be " + std::to_string(k.align) + "-byte aligned");
+        if (kind == kQuadratic)
+            REQUIRE((((uintptr_t)x | (uintptr_t)x2) & 15) == 0, "quadratic design tables: the state x must be 16-byte aligned (the update reads its rows 16 bytes at a time)");
+        took.h->dzt = &t;
     }
-    if (dz->mode == 6) {
-        REQUIRE(!ts.on(), "design tables (target, scale) are armed but the descriptor's mode is 6, which reads the pair-distance tables of "
-                          "cindm_ddpm1d_set_design_pairdist; the tables were dropped");
-        return 0;
-    }
-    if (dz->mode != 3 && dz->mode != 4) {
-        REQUIRE(!ts.on(), "design tables are armed but the descriptor's mode is 1 / 2 (the point objective, which reads none); the tables were dropped");
-        return 0;
-    }
-    REQUIRE(ts.on(), "design objective mode 3 / 4 reads its target and scale from tables: arm them with cindm_ddpm1d_set_design_tables "
-                     "before the chain call");
-    if (t.rows != Ltot)
-        return fail("design tables: " + std::to_string(t.rows) + " rows, the state has " + std::to_string(Ltot));
-    if (t.n_bodies != n_bodies)
-        return fail("design tables: " + std::to_string(t.n_bodies) + " bodies, the composition has " + std::to_string(n_bodies));
-    if (t.batch != B)
-        return fail("design tables: made for a batch of " + std::to_string(t.batch) + ", the chain runs " + std::to_string(B));
-    REQUIRE((((uintptr_t)t.target | (uintptr_t)t.scale) & 15) == 0, "design tables: target and scale must be 16-byte aligned");
-    ts.h->dzt = &ts.t;
     return 0;
 }
 
-static void dzt_key(KeyBuilder& K, const cindm_ddpm1d* h) {
-    if (h->dzt) K(h->dzt->target)(h->dzt->scale)(h->dzt->target_per_design)(h->dzt->scale_per_design);
+static void design_key(KeyBuilder& K, const cindm_ddpm1d* h) {
+    if (h->dzt) K(h->dzt->a)(h->dzt->b)(h->dzt->a_per_design)(h->dzt->b_per_design);
+}
+
+// what the three setters share; width_ok: the setter's own rule for the width
+static int design_arm(cindm_ddpm1d* h, int kind, const float* a, int32_t a_per_design, const float* b, int32_t b_per_design, int32_t rows,
+                      int32_t width, bool width_ok, int64_t batch) {
+    const DesignKind& k = kDesignKinds[kind];
+    if (h) h->armed.tables[kind] = DesignTables();      // (a refused call leaves the handle disarmed)
+    REQUIRE(h, "null handle");
+    if (!a && !b) return 0;
+    if (!a || !b) return fail(std::string(k.label) + ": " + k.a_name + " and " + k.b_name + " come together (NULL, NULL disarms)");
+    if (rows < 1 || batch < 1) return fail(std::string(k.label) + ": " + k.rows_rule);
+    if (!width_ok) return fail(std::string(k.label) + ": " + k.width_rule);
+    DesignTables& t = h->armed.tables[kind];
+    t.kind = kind; t.a = a; t.b = b; t.a_per_design = a_per_design ? 1 : 0; t.b_per_design = b_per_design ? 1 : 0;
+    t.rows = rows; t.width = width; t.batch = batch;
+    return 0;
 }
 
 extern "C" int cindm_ddpm1d_set_design_tables(cindm_ddpm1d* h, const float* target, int32_t target_per_design, const float* scale,
                                               int32_t scale_per_design, int32_t rows, int32_t n_bodies, int64_t batch) {
-    if (h) h->dzt_armed = DesignTables();      // (a refused call leaves the handle disarmed)
-    REQUIRE(h, "null handle");
-    if (!target && !scale) return 0;
-    REQUIRE(target && scale, "design tables: target and scale come together (NULL, NULL disarms)");
-    REQUIRE(rows >= 1 && n_bodies >= 1 && batch >= 1, "design tables: rows, n_bodies and batch must be >= 1");
-    DesignTables& t = h->dzt_armed;
-    t.target = target; t.scale = scale; t.target_per_design = target_per_design ? 1 : 0; t.scale_per_design = scale_per_design ? 1 : 0;
-    t.rows = rows; t.n_bodies = n_bodies; t.batch = batch;
-    return 0;
-}
-
-// ---- the quadratic objective's tables (DESIGN 4.5q) ------------------------------------------------------------------------------------
-// cindm_ddpm1d_set_design_quadratic arms the handle; the next chain entry -- 1-D or 2-D -- takes the tables with QuadTablesScope, so the
-// call consumes them however it ends, and either refuses them (qdt_refuse: every chain that is not guided) or checks them against its
-// descriptor and state (qdt_begin) and runs with them: run_step reads h->qdt for the whole call, the re-run included.
-struct QuadTablesScope {
-    cindm_ddpm1d* h; QuadTables t;
-    explicit QuadTablesScope(cindm_ddpm1d* h_) : h(h_) {
-        if (!h) return;
-        t = h->qdt_armed; h->qdt_armed = QuadTables();
-    }
-    ~QuadTablesScope() { if (h) h->qdt = nullptr; }
-    bool on() const { return t.S != nullptr; }
-};
-
-static int qdt_refuse(const QuadTablesScope& qs) {
-    REQUIRE(!qs.on(), "quadratic design tables: only the guided 1-D chains (cindm_ddpm1d_sample_guided / _sample_ddim_guided) read them; the tables were dropped");
-    return 0;
-}
-
-// x, x2: the state buffers the guided update reads a row of as float4 (x2: the guided DDIM chain's second buffer, or null)
-static int qdt_begin(QuadTablesScope& qs, const cindm_design_desc* dz, int Ltot, int n_bodies, int64_t B, const float* x, const float* x2) {
-    const QuadTables& t = qs.t;
-    if (dz->mode == 6) {
-        REQUIRE(!qs.on(), "quadratic design tables are armed but the descriptor's mode is 6, which reads the pair-distance tables of "
-                          "cindm_ddpm1d_set_design_pairdist; the tables were dropped");
-        return 0;
-    }
-    if (dz->mode != 5) {
-        REQUIRE(!qs.on(), "quadratic design tables are armed but the descriptor's mode is 1 .. 4 (the point and waypoint objectives, which do "
-                          "not read them); the tables were dropped");
-        return 0;
-    }
-    REQUIRE(qs.on(), "design objective mode 5 reads S and h from tables: arm them with cindm_ddpm1d_set_design_quadratic before the chain call");
-    if (t.rows != Ltot)
-        return fail("quadratic design tables: " + std::to_string(t.rows) + " rows, the state has " + std::to_string(Ltot));
-    if (t.features != 4 * n_bodies)
-        return fail("quadratic design tables: " + std::to_string(t.features) + " features, the composition's state has " + std::to_string(4 * n_bodies));
-    if (t.batch != B)
-        return fail("quadratic design tables: made for a batch of " + std::to_string(t.batch) + ", the chain runs " + std::to_string(B));
-    REQUIRE((((uintptr_t)t.S | (uintptr_t)t.h) & 15) == 0, "quadratic design tables: S and h must be 16-byte aligned");
-    REQUIRE((((uintptr_t)x | (uintptr_t)x2) & 15) == 0, "quadratic design tables: the state x must be 16-byte aligned (the update reads its rows 16 bytes at a time)");
-    qs.h->qdt = &qs.t;
-    return 0;
-}
-
-static void qdt_key(KeyBuilder& K, const cindm_ddpm1d* h) {
-    if (h->qdt) K(h->qdt->S)(h->qdt->h)(h->qdt->S_per_design)(h->qdt->h_per_design);
+    return design_arm(h, kWaypoint, target, target_per_design, scale, scale_per_design, rows, n_bodies, n_bodies >= 1, batch);
 }
 
 extern "C" int cindm_ddpm1d_set_design_quadratic(cindm_ddpm1d* h, const float* S, int32_t S_per_design, const float* hvec,
                                                  int32_t h_per_design, int32_t rows, int32_t features, int64_t batch) {
-    if (h) h->qdt_armed = QuadTables();      // (a refused call leaves the handle disarmed)
-    REQUIRE(h, "null handle");
-    if (!S && !hvec) return 0;
-    REQUIRE(S && hvec, "quadratic design tables: S and h come together (NULL, NULL disarms)");
-    REQUIRE(rows >= 1 && batch >= 1, "quadratic design tables: rows and batch must be >= 1");
-    REQUIRE(features >= 4 && features <= 32 && (features & 3) == 0, "quadratic design tables: features must be a multiple of 4 in 4 .. 32");
-    QuadTables& t = h->qdt_armed;
-    t.S = S; t.h = hvec; t.S_per_design = S_per_design ? 1 : 0; t.h_per_design = h_per_design ? 1 : 0;
-    t.rows = rows; t.features = features; t.batch = batch;
-    return 0;
-}
-
-// ---- the pair-distance objective's tables (DESIGN 4.5s) ---------------------------------------------------------------------------------
-// cindm_ddpm1d_set_design_pairdist arms the handle; the next chain entry -- 1-D or 2-D -- takes the tables with PairTablesScope, so the
-// call consumes them however it ends, and either refuses them (pdt_refuse: every chain that is not guided) or checks them against its
-// descriptor and state (pdt_begin) and runs with them: run_step reads h->pdt for the whole call, the re-run included.
-struct PairTablesScope {
-    cindm_ddpm1d* h; PairTables t;
-    explicit PairTablesScope(cindm_ddpm1d* h_) : h(h_) {
-        if (!h) return;
-        t = h->pdt_armed; h->pdt_armed = PairTables();
-    }
-    ~PairTablesScope() { if (h) h->pdt = nullptr; }
-    bool on() const { return t.band != nullptr; }
-};
-
-static int pdt_refuse(const PairTablesScope& ps) {
-    REQUIRE(!ps.on(), "pair-distance design tables: only the guided 1-D chains (cindm_ddpm1d_sample_guided / _sample_ddim_guided) read them; the tables were dropped");
-    return 0;
-}
-
-static int pdt_begin(PairTablesScope& ps, const cindm_design_desc* dz, int Ltot, int n_bodies, int64_t B) {
-    const PairTables& t = ps.t;
-    if (dz->mode != 6) {
-        REQUIRE(!ps.on(), "pair-distance design tables are armed but the descriptor's mode is 1 .. 5 (the point, waypoint and quadratic "
-                          "objectives, which do not read them); the tables were dropped");
-        return 0;
-    }
-    REQUIRE(ps.on(), "design objective mode 6 reads band and weight from tables: arm them with cindm_ddpm1d_set_design_pairdist before the chain call");
-    if (t.rows != Ltot)
-        return fail("pair-distance design tables: " + std::to_string(t.rows) + " rows, the state has " + std::to_string(Ltot));
-    if (t.n_bodies != n_bodies)
-        return fail("pair-distance design tables: " + std::to_string(t.n_bodies) + " bodies, the composition has " + std::to_string(n_bodies));
-    if (t.batch != B)
-        return fail("pair-distance design tables: made for a batch of " + std::to_string(t.batch) + ", the chain runs " + std::to_string(B));
-    REQUIRE((((uintptr_t)t.band | (uintptr_t)t.weight) & 3) == 0, "pair-distance design tables: band and weight must be 4-byte aligned");
-    ps.h->pdt = &ps.t;
-    return 0;
-}
-
-static void pdt_key(KeyBuilder& K, const cindm_ddpm1d* h) {
-    if (h->pdt) K(h->pdt->band)(h->pdt->weight)(h->pdt->band_per_design)(h->pdt->weight_per_design);
+    return design_arm(h, kQuadratic, S, S_per_design, hvec, h_per_design, rows, features, features >= 4 && features <= 32 && (features & 3) == 0, batch);
 }
 
 extern "C" int cindm_ddpm1d_set_design_pairdist(cindm_ddpm1d* h, const float* band, int32_t band_per_design, const float* weight,
                                                 int32_t weight_per_design, int32_t rows, int32_t n_bodies, int64_t batch) {
-    if (h) h->pdt_armed = PairTables();      // (a refused call leaves the handle disarmed)
-    REQUIRE(h, "null handle");
-    if (!band && !weight) return 0;
-    REQUIRE(band && weight, "pair-distance design tables: band and weight come together (NULL, NULL disarms)");
-    REQUIRE(rows >= 1 && batch >= 1, "pair-distance design tables: rows and batch must be >= 1");
-    REQUIRE(n_bodies >= 2 && n_bodies <= 8, "pair-distance design tables: n_bodies must be in 2 .. 8");
-    PairTables& t = h->pdt_armed;
-    t.band = band; t.weight = weight; t.band_per_design = band_per_design ? 1 : 0; t.weight_per_design = weight_per_design ? 1 : 0;
-    t.rows = rows; t.n_bodies = n_bodies; t.batch = batch;
-    return 0;
+    return design_arm(h, kPairDist, band, band_per_design, weight, weight_per_design, rows, n_bodies, n_bodies >= 2 && n_bodies <= 8, batch);
 }
 
 // ---- the known region of the 2-D chains (DESIGN 4.5n) ----------------------------------------------------------------------------------
-// cindm_ddpm1d_set_known2d arms the handle; like the recorder, the next chain entry takes the region with Known2DScope -- so the call
-// consumes it however it ends -- and either refuses it (known2_refuse: every 1-D chain) or checks it against its state (known2_begin,
-// ddpm2d_host.inc) and runs with it: the chain body and the captured step read h->kn for the whole call, the re-run included.
-struct Known2DScope {
-    cindm_ddpm1d* h; Known2D k;
-    explicit Known2DScope(cindm_ddpm1d* h_) : h(h_) {
-        if (!h) return;
-        k = h->kn_armed; h->kn_armed = Known2D();
-    }
-    ~Known2DScope() { if (h) h->kn = nullptr; }
-    bool on() const { return k.known != nullptr; }
-};
-
-static int known2_refuse(const Known2DScope& ks) {
-    REQUIRE(!ks.on(), "known region: only the 2-D chains (cindm_ddpm2d_sample / _sample_ddim / _sample_force / _sample_ddim_force) hold one; "
-                      "the 1-D chains inpaint through their own arguments (inpaint_cond, initial_state_overwrite); the region was dropped");
-    return 0;
-}
-
+// cindm_ddpm1d_set_known2d arms the handle; an entry either refuses the region it took (refuse_all_but: every 1-D chain) or checks it
+// against its state (known2_begin, ddpm2d_host.inc) and runs with it: the chain body and the captured step read h->kn for the whole
+// call, the re-run included.
 extern "C" int cindm_ddpm1d_set_known2d(cindm_ddpm1d* h, const float* known, const uint8_t* mask, const float* noise_init_state,
                                         const float* noise_init_boundary, const float* noise_state_steps,
                                         const float* noise_boundary_steps, int64_t state_step_stride, int64_t boundary_step_stride,
                                         int64_t images, int32_t hw, int32_t cp) {
-    if (h) h->kn_armed = Known2D();      // (a refused call leaves the handle disarmed)
+    if (h) h->armed.kn = Known2D();      // (a refused call leaves the handle disarmed)
     REQUIRE(h, "null handle");
     if (!known && !mask) return 0;
     REQUIRE(known && mask, "known region: values and mask come together (NULL, NULL disarms)");
@@ -509,7 +431,7 @@ extern "C" int cindm_ddpm1d_set_known2d(cindm_ddpm1d* h, const float* known, con
     for (const void* p : {(const void*)known, (const void*)mask, (const void*)noise_init_state, (const void*)noise_init_boundary,
                           (const void*)noise_state_steps, (const void*)noise_boundary_steps})
         REQUIRE(((uintptr_t)p & 15) == 0, "known region: values, mask and tapes must be 16-byte aligned");
-    Known2D& k = h->kn_armed;
+    Known2D& k = h->armed.kn;
     k.known = known; k.mask = mask; k.zi_state = noise_init_state; k.zi_bound = noise_init_boundary;
     k.z_state = noise_state_steps; k.z_bound = noise_boundary_steps; k.zs_stride = state_step_stride; k.zb_stride = boundary_step_stride;
     k.images = images; k.hw = hw; k.cp = cp;
@@ -517,29 +439,14 @@ extern "C" int cindm_ddpm1d_set_known2d(cindm_ddpm1d* h, const float* known, con
 }
 
 // ---- the known region of the 1-D chains (DESIGN 4.5o) ----------------------------------------------------------------------------------
-// cindm_ddpm1d_set_known1d arms the handle; the next chain entry takes the region with Known1DScope -- so the call consumes it however
-// it ends -- and either refuses it (known1_refuse: the rollout, the Langevin chain, every 2-D chain) or checks it against its state
-// (known1_begin, ddpm1d_host.inc) and runs with it: the chain body and run_step read h->kn1 for the whole call, the re-run included.
-struct Known1DScope {
-    cindm_ddpm1d* h; Known1D k;
-    explicit Known1DScope(cindm_ddpm1d* h_) : h(h_) {
-        if (!h) return;
-        k = h->kn1_armed; h->kn1_armed = Known1D();
-    }
-    ~Known1DScope() { if (h) h->kn1 = nullptr; }
-    bool on() const { return k.known != nullptr; }
-};
-
-static int known1_refuse(const Known1DScope& ks, const char* why) {
-    if (ks.on()) return fail(std::string("known region (1-D): ") + why + "; the region was dropped");
-    return 0;
-}
-
+// cindm_ddpm1d_set_known1d arms the handle; an entry either refuses the region it took (refuse_all_but with the entry's reason: the
+// rollout, the time composition, the Langevin chain, every 2-D chain) or checks it against its state (known1_begin, ddpm1d_host.inc)
+// and runs with it: the chain body and run_step read h->kn1 for the whole call, the re-run included.
 extern "C" int cindm_ddpm1d_set_known1d(cindm_ddpm1d* h, const float* known, int32_t known_per_design, const uint8_t* mask,
                                         int32_t mask_per_design, const float* noise_init, const float* noise_steps,
                                         int64_t step_stride, const float* noise_recur, int64_t recur_stride, int32_t apply_init,
                                         int64_t batch, int32_t rows, int32_t feats) {
-    if (h) h->kn1_armed = Known1D();      // (a refused call leaves the handle disarmed)
+    if (h) h->armed.kn1 = Known1D();      // (a refused call leaves the handle disarmed)
     REQUIRE(h, "null handle");
     if (!known && !mask) return 0;
     REQUIRE(known && mask, "known region (1-D): values and mask come together (NULL, NULL disarms)");
@@ -550,7 +457,7 @@ extern "C" int cindm_ddpm1d_set_known1d(cindm_ddpm1d* h, const float* known, int
     REQUIRE(step_stride >= 0 && recur_stride >= 0, "known region (1-D): negative tape stride");
     for (const void* p : {(const void*)known, (const void*)mask, (const void*)noise_init, (const void*)noise_steps, (const void*)noise_recur})
         REQUIRE(((uintptr_t)p & 15) == 0, "known region (1-D): values, mask and tapes must be 16-byte aligned");
-    Known1D& k = h->kn1_armed;
+    Known1D& k = h->armed.kn1;
     k.known = known; k.mask = mask; k.known_per_design = known_per_design ? 1 : 0; k.mask_per_design = mask_per_design ? 1 : 0;
     k.z_init = noise_init; k.z_step = noise_steps; k.z_recur = noise_recur; k.step_stride = step_stride; k.recur_stride = recur_stride;
     k.batch = batch; k.rows = rows; k.feats = feats; k.apply_init = apply_init ? 1 : 0;
@@ -558,30 +465,14 @@ extern "C" int cindm_ddpm1d_set_known1d(cindm_ddpm1d* h, const float* known, int
 }
 
 // ---- the second-order multistep solver (DESIGN 4.5r) -----------------------------------------------------------------------------------
-// cindm_ddpm1d_set_multistep arms the handle; the next chain entry takes the solver with MultistepScope -- so the call consumes it
-// however it ends -- and either refuses it (ms_refuse: every chain that is not one of the four DDIM chains) or checks it against its
-// schedule and state (ms_begin) and runs with it: the DDIM update of step i adds kappa[i] (X_i - X_{i-1}) to its value and writes X_i
-// to the history.  kappa[i] == 0 does not read the history: the first step of a chain, and of its recovery re-run, needs none.
-struct MultistepScope {
-    cindm_ddpm1d* h; Multistep m;
-    explicit MultistepScope(cindm_ddpm1d* h_) : h(h_) {
-        if (!h) return;
-        m = std::move(h->ms_armed); h->ms_armed = Multistep();
-    }
-    ~MultistepScope() { if (h) h->ms = nullptr; }
-    bool on() const { return m.hist != nullptr; }
-};
-
-static int ms_refuse(const MultistepScope& ms) {
-    REQUIRE(!ms.on(), "multistep solver: only the DDIM chains (cindm_ddpm1d_sample_ddim / _sample_ddim_guided, cindm_ddpm2d_sample_ddim / "
-                      "_sample_ddim_force) run it; the solver was dropped");
-    return 0;
-}
-
+// cindm_ddpm1d_set_multistep arms the handle; an entry either refuses the solver it took (refuse_all_but: every chain that is not one
+// of the four DDIM chains) or checks it against its schedule and state (ms_begin) and runs with it: the DDIM update of step i adds
+// kappa[i] (X_i - X_{i-1}) to its value and writes X_i to the history.  kappa[i] == 0 does not read the history: the first step of
+// a chain, and of its recovery re-run, needs none.
 // n_steps, coefs: the DDIM call's; state_floats, x, x2: the chain's state (x2: a second state buffer the update may read, or null)
-static int ms_begin(MultistepScope& ms, int32_t n_steps, const float* coefs, int64_t state_floats, const float* x, const float* x2 = nullptr) {
-    if (!ms.on()) return 0;
-    const Multistep& m = ms.m;
+static int ms_begin(ChainArmed& took, int32_t n_steps, const float* coefs, int64_t state_floats, const float* x, const float* x2 = nullptr) {
+    if (!took.ms.on()) return 0;
+    const Multistep& m = took.ms;
     if ((int64_t)m.kappa.size() != (int64_t)n_steps)
         return fail("multistep solver: armed for " + std::to_string(m.kappa.size()) + " steps, the chain runs " + std::to_string(n_steps));
     if (m.hist_floats != state_floats)
@@ -589,7 +480,7 @@ static int ms_begin(MultistepScope& ms, int32_t n_steps, const float* coefs, int
     for (int i = 0; i < n_steps; ++i)
         REQUIRE(coefs[3 * i + 2] == 0.f, "multistep solver: every step's sigma must be zero (ddim_sampling_eta = 0: the solver is deterministic)");
     REQUIRE(m.hist != x && m.hist != x2, "multistep solver: the history may not be a state buffer of the chain");
-    ms.h->ms = &ms.m;
+    took.h->ms = &took.ms;
     return 0;
 }
 
@@ -599,13 +490,27 @@ static void ms_key(KeyBuilder& K, const cindm_ddpm1d* h) {
 }
 
 extern "C" int cindm_ddpm1d_set_multistep(cindm_ddpm1d* h, const float* kappa_host, int32_t n_steps, float* hist, int64_t hist_floats) {
-    if (h) h->ms_armed = Multistep();      // (a refused call leaves the handle disarmed)
+    if (h) h->armed.ms = Multistep();      // (a refused call leaves the handle disarmed)
     REQUIRE(h, "null handle");
     if (!kappa_host) return 0;
     REQUIRE(n_steps >= 1, "multistep solver: n_steps must be >= 1");
     REQUIRE(hist && hist_floats > 0 && ((uintptr_t)hist & 15) == 0, "multistep solver: the history must be 16-byte aligned and not empty");
     for (int i = 0; i < n_steps; ++i) REQUIRE(std::isfinite(kappa_host[i]), "multistep solver: kappa must be finite");
-    Multistep& m = h->ms_armed;
+    Multistep& m = h->armed.ms;
     m.kappa.assign(kappa_host, kappa_host + n_steps); m.hist = hist; m.hist_floats = hist_floats;
+    return 0;
+}
+
+// ---- what an entry does not serve -------------------------------------------------------------------------------------------------------
+int ChainArmed::refuse_all_but(unsigned serves, const char* why_known1) const {
+    if (!(serves & kServesTables) && design_refuse(*this) != 0) return -1;
+    if (!(serves & kServesKnown2))
+        REQUIRE(!kn.on(), "known region: only the 2-D chains (cindm_ddpm2d_sample / _sample_ddim / _sample_force / _sample_ddim_force) hold one; "
+                          "the 1-D chains inpaint through their own arguments (inpaint_cond, initial_state_overwrite); the region was dropped");
+    if (!(serves & kServesKnown1) && kn1.on())
+        return fail(std::string("known region (1-D): ") + (why_known1 ? why_known1 : "this chain holds none") + "; the region was dropped");
+    if (!(serves & kServesMultistep))
+        REQUIRE(!ms.on(), "multistep solver: only the DDIM chains (cindm_ddpm1d_sample_ddim / _sample_ddim_guided, cindm_ddpm2d_sample_ddim / "
+                          "_sample_ddim_force) run it; the solver was dropped");
     return 0;
 }

@@ -14,8 +14,8 @@
 //   ddim_tables1               the DDIM preamble: per-step tables into the workspace's slice
 //   loop_steps, loop_chain     the unguided loop and the chain that is one such loop
 //   guided_step, guided_chain  the recurrence iterations of a guided step and the guided chains' tail
-// An entry is: RecScope, DesignTablesScope, Known2DScope, Known1DScope, QuadTablesScope, PairTablesScope, MultistepScope, Chain1D, refusals, rec_begin, known1_begin,
-// (DDIM: ms_begin,) chain_stream, (DDIM: ddim_tables1,) chain_io plus what it adds, and one call of loop_chain, guided_chain or its own body (the rollout).
+// An entry is: ChainArmed (everything armed on the handle, chain_host.inc), Chain1D, refuse_all_but what it serves, its other refusals, rec_begin,
+// known1_begin, (DDIM: ms_begin,) chain_stream, (DDIM: ddim_tables1,) chain_io plus what it adds, and one call of loop_chain, guided_chain or its own body (the rollout).
 
 extern "C" int cindm_ddpm1d_create(const cindm_sched_desc* d, cindm_ddpm1d** out) {
     REQUIRE(d && out && d->timesteps > 0, "bad schedule descriptor");
@@ -211,9 +211,9 @@ static int prepare_step_ws(const Chain1D& ch) {
 // The known region of a 1-D chain (DESIGN 4.5o): checked against the chain's state before the entry's first launch or copy, then held
 // by the handle for the whole call.  recur_iters: the iterations per step of a guided chain (a relaxation tape holds that many records
 // per row), 0 for the unguided ones.
-static int known1_begin(Known1DScope& ks, const Chain1D& ch, const float* x, int recur_iters) {
-    if (!ks.on()) return 0;
-    const Known1D& k = ks.k;
+static int known1_begin(ChainArmed& took, const Chain1D& ch, const float* x, int recur_iters) {
+    if (!took.kn1.on()) return 0;
+    const Known1D& k = took.kn1;
     const int F = ch.c->n_bodies * 4;
     if (k.batch != ch.B || k.rows != ch.Ltot() || k.feats != F)
         return fail("known region (1-D): made for " + std::to_string(k.batch) + " designs of " + std::to_string(k.rows) + " rows x " +
@@ -229,7 +229,7 @@ static int known1_begin(Known1DScope& ks, const Chain1D& ch, const float* x, int
                     "known region (1-D): the relaxation tape's stride is smaller than the step's iterations x one state, or no multiple of 4");
         }
     }
-    ks.h->kn1 = &ks.k;
+    took.h->kn1 = &took.kn1;
     return 0;
 }
 
@@ -292,18 +292,13 @@ static int run_step(const Chain1D& ch, const StepIO& io, int32_t t, const int32_
     const bool guided = io.dz && io.x_out;
     if (guided) {
         a.dz_mode = io.dz->mode; a.dz_alpha = io.dz->alpha; a.dz_tc = io.dz->time_consistency_coef;
-        if (io.dz->mode == 6) {     // pair-distance objective: likewise
-            REQUIRE(h->pdt, "design objective mode 6 outside a chain that took pair-distance design tables (internal error)");
-            a.dz_band = h->pdt->band; a.dz_weight = h->pdt->weight;
-            a.dz_mode |= (h->pdt->band_per_design ? kDzTargetPerDesign : 0) | (h->pdt->weight_per_design ? kDzScalePerDesign : 0);
-        } else if (io.dz->mode == 5) {     // quadratic objective: its tables' addresses and flags are operands of the captured update as well
-            REQUIRE(h->qdt, "design objective mode 5 outside a chain that took quadratic design tables (internal error)");
-            a.dz_S = h->qdt->S; a.dz_h = h->qdt->h;
-            a.dz_mode |= (h->qdt->S_per_design ? kDzTargetPerDesign : 0) | (h->qdt->h_per_design ? kDzScalePerDesign : 0);
-        } else if (io.dz->mode >= 3) {     // table objective: the addresses and the per-design flags are operands of the captured update
-            REQUIRE(h->dzt, "design objective mode 3 / 4 outside a chain that took design tables (internal error)");
-            a.dz_target = h->dzt->target; a.dz_scale = h->dzt->scale;
-            a.dz_mode |= (h->dzt->target_per_design ? kDzTargetPerDesign : 0) | (h->dzt->scale_per_design ? kDzScalePerDesign : 0);
+        const int kind = design_kind_of(io.dz->mode);
+        if (kind >= 0) {     // table objective: the addresses and the per-design flags are operands of the captured update
+            const DesignKind& k = kDesignKinds[kind]; const DesignTables* t = h->dzt;
+            if (!t || t->kind != kind)
+                return fail(std::string("design objective mode ") + k.modes + " outside a chain that took " + k.label + " (internal error)");
+            a.*k.arg_a = t->a; a.*k.arg_b = t->b;
+            a.dz_mode |= (t->a_per_design ? kDzTargetPerDesign : 0) | (t->b_per_design ? kDzScalePerDesign : 0);
         } else {
             a.dz_last_n = io.dz->last_n_step; a.dz_coef = io.dz->coef; a.dz_tx = io.dz->pos_target[0]; a.dz_ty = io.dz->pos_target[1];
         }
@@ -439,20 +434,17 @@ static int chain1_refuse(const Chain1D& ch, const float* x, const float* cond, c
     return 0;
 }
 
-// What a guided entry refuses on top of chain1_refuse (after it): the objective, its tables (dzt_begin takes them for the call) and
-// the rows it overwrites; likewise the quadratic objective's tables (qdt_begin; x: the state its update reads 16 bytes at a time)
-// and the pair-distance objective's (pdt_begin).
+// What a guided entry refuses on top of chain1_refuse (after it): the objective, its tables (design_begin hands them to the handle
+// for the call; x: the state the quadratic update reads 16 bytes at a time) and the rows it overwrites.
 // min_recurrence: 0 for the DDPM chain (no recurrence: one plain guided iteration), 1 for the DDIM chain.
-static int guided_refuse(const Chain1D& ch, DesignTablesScope& ts, QuadTablesScope& qs, PairTablesScope& ps, const cindm_design_desc* dz, const float* x, int min_recurrence,
+static int guided_refuse(const Chain1D& ch, ChainArmed& took, const cindm_design_desc* dz, const float* x, int min_recurrence,
                          const float* initial_state_overwrite, int overwrite_steps) {
     REQUIRE(dz, "null argument");
     REQUIRE(dz->mode >= 1 && dz->mode <= 6, "design objective mode must be 1 (L2), 2 (L2square), 3 (table L2), 4 (table L2square), 5 (quadratic tables) or 6 (pair-distance tables)");
     if (min_recurrence == 0) REQUIRE(dz->recurrence >= 0 && dz->recurrence <= 64, "recurrence count out of range");
     else REQUIRE(dz->recurrence >= 1 && dz->recurrence <= 64,
                  "guided DDIM needs a recurrence count in 1 .. 64 (without recurrence the reference returns no noise prediction)");
-    if (dzt_begin(ts, dz, ch.Ltot(), ch.c->n_bodies, ch.B) != 0) return -1;
-    if (qdt_begin(qs, dz, ch.Ltot(), ch.c->n_bodies, ch.B, x, ch.stage()) != 0) return -1;
-    if (pdt_begin(ps, dz, ch.Ltot(), ch.c->n_bodies, ch.B) != 0) return -1;
+    if (design_begin(took, dz, ch.Ltot(), ch.c->n_bodies, ch.B, x, ch.stage()) != 0) return -1;
     REQUIRE(dz->mode >= 3 || (dz->last_n_step >= 1 && dz->last_n_step <= ch.Ltot()), "last_n_step out of range");
     REQUIRE(!initial_state_overwrite || (overwrite_steps >= 1 && overwrite_steps <= ch.Ltot()), "bad overwrite_steps");
     return 0;
@@ -662,8 +654,8 @@ static int loop_steps(const Chain1D& ch, StepIO io, int kind, int t0, int nsteps
 }
 
 // the chain that is one such loop (DDPM, DDIM, Langevin) from the (seed, sample_off) of its io: what a recovery re-run repeats
-static int loop_chain(RecScope& rs, const Chain1D& ch, const StepIO& io, int kind, int t0, int nsteps) {
-    return rec_done(rs, run_chain_with_recovery(ch, io.x_out, [&]() -> int {
+static int loop_chain(ChainArmed& took, const Chain1D& ch, const StepIO& io, int kind, int t0, int nsteps) {
+    return rec_done(took, run_chain_with_recovery(ch, io.x_out, [&]() -> int {
         if (prepare_step_ws(ch) != 0) return -1;
         return loop_steps(ch, io, kind, t0, nsteps, io.seed, io.sample_off);
     }));
@@ -694,14 +686,14 @@ static int guided_step(const Chain1D& ch, const StepIO& io, int iters, const flo
 // or 4 (DDIM: R iterations per step, ping-pong between the caller's x and x2, the workspace's second state buffer; the record word
 // is the step index).  The key carries the objective, its tables and the recurrence tape; after() runs behind a chain that ended well.
 template <typename After>
-static int guided_chain(RecScope& rs, const Chain1D& ch, StepIO io, int kind, const float* recur_noise_steps, int t0, int nsteps, float* x2, After after) {
+static int guided_chain(ChainArmed& took, const Chain1D& ch, StepIO io, int kind, const float* recur_noise_steps, int t0, int nsteps, float* x2, After after) {
     const bool pp = x2 != nullptr;
     const int R = io.dz->recurrence, iters = pp ? R : std::max(R, 1);
     float* const buf[2] = {io.x_out, x2};
     io.recur_t_stride = (int64_t)iters * ch.n_state();
     io.pingpong = pp ? 1 : 0; io.state_pp = pp ? 1 : 0;
     auto step = [&](int q) -> int { return guided_step(ch, io, iters, recur_noise_steps, pp ? buf : nullptr, q); };
-    return rec_done(rs, run_chain_with_recovery(ch, io.x_out, [&]() -> int {
+    return rec_done(took, run_chain_with_recovery(ch, io.x_out, [&]() -> int {
         if (prepare_step_ws(ch) != 0) return -1;
         start_loop(ch, t0, io.seed, io.sample_off);
         rec_arm(ch.h, pp ? -1 : t0, pp ? 2 : 0, pp ? 4 : 0, ch.stream);
@@ -709,9 +701,7 @@ static int guided_chain(RecScope& rs, const Chain1D& ch, StepIO io, int kind, co
         KeyBuilder K;
         key_common(K, kind, ch, io);
         K(*io.dz)(recur_noise_steps)(R);
-        dzt_key(K, ch.h);
-        qdt_key(K, ch.h);
-        pdt_key(K, ch.h);
+        design_key(K, ch.h);
         const int rc = replay_steps(ch, K.k, nsteps, step, pp);
         return rc == 0 ? after() : rc;
     }));
@@ -727,20 +717,14 @@ extern "C" int cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_un
                                    const float* inpaint_cond, int32_t inpaint_steps, const float* inpaint_noise_steps,
                                    int32_t t_start, int32_t t_end, int64_t B, void* ws, size_t ws_bytes, void* stream_,
                                    int32_t use_graph) {
-    RecScope rs(h);
-    DesignTablesScope ts(h);
-    Known2DScope ks(h);
-    Known1DScope k1(h);
-    QuadTablesScope qs(h);
-    PairTablesScope ps(h);
-    MultistepScope ms(h);
+    ChainArmed took(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
-    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0) return -1;
-    if (rec_begin(rs, x, nsteps, ch.n_state()) != 0 || known1_begin(k1, ch, x, 0) != 0) return -1;
+    if (took.refuse_all_but(kServesKnown1) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0) return -1;
+    if (rec_begin(took, x, nsteps, ch.n_state()) != 0 || known1_begin(took, ch, x, 0) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     const StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
-    return loop_chain(rs, ch, io, 0, (int)t_start, nsteps);
+    return loop_chain(took, ch, io, 0, (int)t_start, nsteps);
 }
 
 extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, const cindm_compose_desc* c,
@@ -748,22 +732,16 @@ extern "C" int cindm_ddpm1d_sample_ddim(cindm_ddpm1d* h, cindm_unet1d* pair, cin
                                         const float* coefs, const float* noise_steps, uint64_t seed, int64_t sample_offset,
                                         const float* inpaint_cond, int32_t inpaint_steps, const float* inpaint_noise_steps,
                                         int64_t B, void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
-    RecScope rs(h);
-    DesignTablesScope ts(h);
-    Known2DScope ks(h);
-    Known1DScope k1(h);
-    QuadTablesScope qs(h);
-    PairTablesScope ps(h);
-    MultistepScope ms(h);
+    ChainArmed took(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
-    if (dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, &dd) != 0) return -1;
-    if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    if (rec_begin(rs, x, n_steps, ch.n_state()) != 0 || known1_begin(k1, ch, x, 0) != 0 || ms_begin(ms, n_steps, coefs, ch.n_state(), x) != 0) return -1;
+    if (took.refuse_all_but(kServesKnown1 | kServesMultistep) != 0 || chain1_refuse(ch, x, cond, &dd) != 0) return -1;
+    if (took.rec.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    if (rec_begin(took, x, n_steps, ch.n_state()) != 0 || known1_begin(took, ch, x, 0) != 0 || ms_begin(took, n_steps, coefs, ch.n_state(), x) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     if (ddim_tables1(ch, dd, io) != 0) return -1;
-    return loop_chain(rs, ch, io, 1, (int)times[0], n_steps);
+    return loop_chain(took, ch, io, 1, (int)times[0], n_steps);
 }
 
 // Autoregressive time composition (autoregress_time_compose_sample, model/diffusion_1d.py:2240-2327): n_seg unguided DDIM chains, each
@@ -777,19 +755,12 @@ extern "C" int cindm_ddpm1d_sample_autoregress(cindm_ddpm1d* h, cindm_unet1d* pa
                                                int32_t n_steps, const int32_t* times, const float* coefs, const uint64_t* seeds,
                                                const float* init_tape, const float* noise_steps, int64_t sample_offset, int64_t B,
                                                void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
-    RecScope rs(h);
-    DesignTablesScope ts(h);
-    Known2DScope ks(h);
-    Known1DScope k1(h);
-    QuadTablesScope qs(h);
-    PairTablesScope ps(h);
-    MultistepScope ms(h);
+    ChainArmed took(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
-    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0 || known2_refuse(ks) != 0) return -1;
-    if (known1_refuse(k1, "the autoregressive rollout draws a fresh state per segment and hands rows over between segments: a region of "
-                          "one [B, rows, F] state does not name a place in it") != 0) return -1;
-    REQUIRE(!rs.on(), "recorder: the autoregressive rollout is not recorded (its step index is (segment, step)); the recorder was dropped");
+    if (took.refuse_all_but(0, "the autoregressive rollout draws a fresh state per segment and hands rows over between segments: a region of "
+                               "one [B, rows, F] state does not name a place in it") != 0) return -1;
+    REQUIRE(!took.rec.on(), "recorder: the autoregressive rollout is not recorded (its step index is (segment, step)); the recorder was dropped");
     REQUIRE(h && pair && c && x && cond && cond_buf && out && times && coefs && seeds, "null argument");
     REQUIRE(c->mode == CINDM_COMPOSE_PLAIN || c->mode == CINDM_COMPOSE_MULTIBODY, "the rollout runs the plain (or multibody) prediction");
     REQUIRE(c->cond_steps >= 1, "conditioned_steps == 0: the reference's img[:, -0:] hands over the whole state and its slice assignment fails");
@@ -837,18 +808,11 @@ extern "C" int cindm_ddpm1d_sample_ula(cindm_ddpm1d* h, cindm_unet1d* pair, cind
                                        const float* step_size, const float* noise_std, void* tab, size_t tab_bytes,
                                        const float* noise_tape, uint64_t seed, int64_t sample_offset, int64_t B,
                                        void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
-    RecScope rs(h);
-    DesignTablesScope ts(h);
-    Known2DScope ks(h);
-    Known1DScope k1(h);
-    QuadTablesScope qs(h);
-    PairTablesScope ps(h);
-    MultistepScope ms(h);
+    ChainArmed took(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
-    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0 || known2_refuse(ks) != 0) return -1;
-    if (known1_refuse(k1, "the Langevin chain moves the whole state, conditioning rows included, at one noise level per timestep without a "
-                          "reverse update: the region's forward-diffusion trajectory is not defined for it") != 0) return -1;
-    REQUIRE(!rs.on(), "recorder: the Langevin chain is not recorded (its step index is (timestep, inner iteration)); the recorder was dropped");
+    if (took.refuse_all_but(0, "the Langevin chain moves the whole state, conditioning rows included, at one noise level per timestep without a "
+                               "reverse update: the region's forward-diffusion trajectory is not defined for it") != 0) return -1;
+    REQUIRE(!took.rec.on(), "recorder: the Langevin chain is not recorded (its step index is (timestep, inner iteration)); the recorder was dropped");
     REQUIRE(h && pair && c && x && scalar && step_size && noise_std && tab, "null argument");
     REQUIRE(c->mode == CINDM_COMPOSE_MULTIBODY && uncond, "the Langevin phase runs the multibody composition (pair + unconditioned model)");
     REQUIRE(c->cond_steps == 0, "the Langevin phase moves the whole state: pass cat(cond, x) as x with cond_steps = 0");
@@ -871,7 +835,7 @@ extern "C" int cindm_ddpm1d_sample_ula(cindm_ddpm1d* h, cindm_unet1d* pair, cind
     }
     StepIO io = chain_io(ch, x, nullptr, noise_tape, seed, sample_offset, nullptr, 0, nullptr);
     io.ula_tab = reinterpret_cast<const float*>(tab); io.ula_L = L; io.ula_t_hi = t_start;
-    return loop_chain(rs, ch, io, 3, (int)t_start, n_t * L);
+    return loop_chain(took, ch, io, 3, (int)t_start, n_t * L);
 }
 
 extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* uncond, const cindm_compose_desc* c,
@@ -881,21 +845,16 @@ extern "C" int cindm_ddpm1d_sample_guided(cindm_ddpm1d* h, cindm_unet1d* pair, c
                                           const float* initial_state_overwrite, int32_t overwrite_steps,
                                           int32_t t_start, int32_t t_end, int64_t B, void* ws, size_t ws_bytes, void* stream_,
                                           int32_t use_graph) {
-    RecScope rs(h);
-    DesignTablesScope ts(h);
-    Known2DScope ks(h);
-    Known1DScope k1(h);
-    QuadTablesScope qs(h);
-    PairTablesScope ps(h);
-    MultistepScope ms(h);
+    ChainArmed took(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
-    if (ms_refuse(ms) != 0 || known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0 || guided_refuse(ch, ts, qs, ps, dz, x, 0, initial_state_overwrite, overwrite_steps) != 0) return -1;
-    if (rec_begin(rs, x, nsteps, ch.n_state()) != 0 || known1_begin(k1, ch, x, std::max(dz->recurrence, 1)) != 0) return -1;
+    if (took.refuse_all_but(kServesTables | kServesKnown1) != 0 || chain1_refuse(ch, x, cond, nullptr, t_start, t_end) != 0 ||
+        guided_refuse(ch, took, dz, x, 0, initial_state_overwrite, overwrite_steps) != 0) return -1;
+    if (rec_begin(took, x, nsteps, ch.n_state()) != 0 || known1_begin(took, ch, x, std::max(dz->recurrence, 1)) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     guided_io(io, dz, initial_state_overwrite, overwrite_steps);
-    return guided_chain(rs, ch, io, 2, recur_noise_steps, (int)t_start, nsteps, nullptr, []() -> int { return 0; });
+    return guided_chain(took, ch, io, 2, recur_noise_steps, (int)t_start, nsteps, nullptr, []() -> int { return 0; });
 }
 
 // Guided DDIM (ddim_sample :1724-1804 with design_fn = the built-in objective and "-recurrence-N" guidance, i.e. through the DDIM
@@ -913,26 +872,21 @@ extern "C" int cindm_ddpm1d_sample_ddim_guided(cindm_ddpm1d* h, cindm_unet1d* pa
                                                const float* inpaint_cond, int32_t inpaint_steps, const float* inpaint_noise_steps,
                                                const float* initial_state_overwrite, int32_t overwrite_steps, int64_t B,
                                                void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
-    RecScope rs(h);
-    DesignTablesScope ts(h);
-    Known2DScope ks(h);
-    Known1DScope k1(h);
-    QuadTablesScope qs(h);
-    PairTablesScope ps(h);
-    MultistepScope ms(h);
+    ChainArmed took(h);
     Chain1D ch(h, pair, uncond, c, B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
-    if (known2_refuse(ks) != 0 || chain1_refuse(ch, x, cond, &dd) != 0 || guided_refuse(ch, ts, qs, ps, dz, x, 1, initial_state_overwrite, overwrite_steps) != 0) return -1;
+    if (took.refuse_all_but(kServesTables | kServesKnown1 | kServesMultistep) != 0 || chain1_refuse(ch, x, cond, &dd) != 0 ||
+        guided_refuse(ch, took, dz, x, 1, initial_state_overwrite, overwrite_steps) != 0) return -1;
     REQUIRE(!inpaint_cond || (inpaint_steps >= 1 && inpaint_steps <= ch.Ltot()), "bad inpaint_steps");
-    if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    if (rec_begin(rs, x, n_steps, ch.n_state()) != 0 || known1_begin(k1, ch, x, dz->recurrence) != 0 ||
-        ms_begin(ms, n_steps, coefs, ch.n_state(), x, ch.stage()) != 0) return -1;
+    if (took.rec.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    if (rec_begin(took, x, n_steps, ch.n_state()) != 0 || known1_begin(took, ch, x, dz->recurrence) != 0 ||
+        ms_begin(took, n_steps, coefs, ch.n_state(), x, ch.stage()) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     StepIO io = chain_io(ch, x, cond, noise_steps, seed, sample_offset, inpaint_cond, inpaint_steps, inpaint_noise_steps);
     if (ddim_tables1(ch, dd, io) != 0) return -1;
     guided_io(io, dz, initial_state_overwrite, overwrite_steps);
     float* x2 = ch.stage();
-    return guided_chain(rs, ch, io, 4, recur_noise_steps, (int)times[0], n_steps, x2, [&]() -> int {
+    return guided_chain(took, ch, io, 4, recur_noise_steps, (int)times[0], n_steps, x2, [&]() -> int {
         if (((int64_t)n_steps * dz->recurrence) & 1) {        // the last iteration wrote the workspace buffer
             HIPCHK(hipMemcpyAsync(x, x2, (size_t)ch.n_state() * sizeof(float), hipMemcpyDeviceToDevice, ch.stream));
             if (use_graph) HIPCHK(hipStreamSynchronize(ch.stream));

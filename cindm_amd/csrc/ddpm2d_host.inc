@@ -12,7 +12,8 @@
 //   ddpm_step2, ddim_step2     the captured step: [gradient,] step, [shift,] [known node,] [record node]
 //   run_chain2                 the tail: counter, rec_arm, [known node: rule 1,] replay -- under force_chain_with_recovery when guided -- and rec_done
 //   ms_begin2, ms_tables2      the multistep solver of a DDIM chain (cindm_ddpm1d_set_multistep): its checks, and kappa behind the caller's tables
-// An entry is: RecScope, Known2DScope, Known1DScope, QuadTablesScope, PairTablesScope, MultistepScope, refusals, (DDIM: ms_begin2,) rec_begin2, known2_begin, chain_stream,
+// An entry is: ChainArmed (everything armed on the handle, chain_host.inc), refuse_all_but what it serves, its other refusals, (DDIM: ms_begin2,)
+// rec_begin2, known2_begin, chain_stream,
 // (DDIM: upload_ddim_tables, ms_tables2,) build the step, run_chain2.
 
 // Returns the bytes of a diffusion workspace for `images` images; the offsets of its second and third slice go to *o_unet / *o_xT.
@@ -157,17 +158,20 @@ static int force_refuse(const Chain2D& ch, const ForceGuide& g, const float* x, 
     return 0;
 }
 
+// why a 2-D entry refuses an armed 1-D known region
+static const char* const kKnown1Not2D = "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D chains take theirs from cindm_ddpm1d_set_known2d";
+
 // the recorder of a 2-D chain: one record is the whole state in the library's layout, [B * nb][H * W][padded channels]
 static const char* const kNoX0Ddim2d = "recorder: the 2-D DDIM update kernels have no x0 operand: the x0 stream is served by the DDPM entries only";
-static int rec_begin2(RecScope& rs, const Chain2D& ch, const float* x, int n_steps, const char* x0_refusal = nullptr) {
-    return rs.on() ? rec_begin(rs, x, n_steps, ch.state_floats(), x0_refusal) : 0;
+static int rec_begin2(ChainArmed& took, const Chain2D& ch, const float* x, int n_steps, const char* x0_refusal = nullptr) {
+    return took.rec.on() ? rec_begin(took, x, n_steps, ch.state_floats(), x0_refusal) : 0;
 }
 
 // The known region of a 2-D chain (DESIGN 4.5n): checked against the chain's state before the entry's first launch or copy, then held
 // by the handle for the whole call.  The draws are the chain's own (seed, sample_offset), under known2d_kernel's seed word.
-static int known2_begin(Known2DScope& ks, const Chain2D& ch, const float* x, const Draws2& z) {
-    if (!ks.on()) return 0;
-    Known2D& k = ks.k;
+static int known2_begin(ChainArmed& took, const Chain2D& ch, const float* x, const Draws2& z) {
+    if (!took.kn.on()) return 0;
+    Known2D& k = took.kn;
     if (k.images != ch.NI() || k.hw != ch.HW() || k.cp != ch.CP())
         return fail("known region: made for " + std::to_string(k.images) + " images of " + std::to_string(k.hw) + " pixels x " + std::to_string(k.cp) +
                     " padded channels, the chain runs " + std::to_string(ch.NI()) + " x " + std::to_string(ch.HW()) + " x " + std::to_string(ch.CP()));
@@ -175,7 +179,7 @@ static int known2_begin(Known2DScope& ks, const Chain2D& ch, const float* x, con
     if (k.z_state && (k.zs_stride < ch.B * (int64_t)ch.HW() * (ch.u->d.channels - 3) || k.zb_stride < ch.NI() * (int64_t)ch.HW() * 3))
         return fail("known region: a tape stride is smaller than one row ([B, H*W, C-3] state floats, [B*nb, H*W, 3] boundary floats)");
     k.seed = z.seed; k.sample_off = z.sample_offset;
-    ks.h->kn = &ks.k;
+    took.h->kn = &took.kn;
     return 0;
 }
 
@@ -233,11 +237,11 @@ static int ms_tables2(const Chain2D& ch, const Ddim2dCall& dd, const float** kap
 }
 
 // what a 2-D DDIM entry checks of an armed multistep solver, after chain2_refuse
-static int ms_begin2(MultistepScope& ms, const Chain2D& ch, const Ddim2dCall& dd, const float* x) {
-    if (!ms.on()) return 0;
+static int ms_begin2(ChainArmed& took, const Chain2D& ch, const Ddim2dCall& dd, const float* x) {
+    if (!took.ms.on()) return 0;
     REQUIRE(dd.tab_bytes >= (size_t)dd.n_steps * 6 * sizeof(float), "multistep solver: the DDIM table buffer needs 6 words per step (24 bytes)");
     REQUIRE(((uintptr_t)x & 15) == 0, "multistep solver: the state x must be 16-byte aligned");
-    return ms_begin(ms, dd.n_steps, dd.coefs, ch.state_floats(), x);
+    return ms_begin(took, dd.n_steps, dd.coefs, ch.state_floats(), x);
 }
 
 // One DDIM step of the 2-D path (ddim_sample; DESIGN 4.5g): the U-Net + ddim2d_update_kernel + step_counter_kernel (t and the step
@@ -325,66 +329,52 @@ static int force_chain_with_recovery(const Chain2D& ch, cindm_forceunet* f, floa
 // The tail of every entry: the device counter at t0, the recorder armed, `step` replayed nsteps times (one hipGraph with use_graph);
 // a guided chain runs that under force_chain_with_recovery, behind the x_T snapshot.  ddim: the counter's word is the step index.
 template <typename StepFn>
-static int run_chain2(RecScope& rs, const Chain2D& ch, const ForceGuide* g, float* x, int t0, bool ddim, int nsteps, StepFn step) {
+static int run_chain2(ChainArmed& took, const Chain2D& ch, const ForceGuide* g, float* x, int t0, bool ddim, int nsteps, StepFn step) {
     auto chain = [&]() -> int {
         hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(64), 0, ch.stream, ch.s->t_dev, t0, 0ull, 0ll);
         rec_arm(ch.s, ddim ? -1 : t0, ddim ? 2 : 0, 0, ch.stream);
         if (ch.s->kn && known2_node(ch, x, 1) != 0) return -1;      // (rule 1; a recovery re-run starts from it again)
         return replay_once(ch.stream, nsteps, ch.use_graph, step);
     };
-    return rec_done(rs, g ? force_chain_with_recovery(ch, g->f, x, chain) : chain());
+    return rec_done(took, g ? force_chain_with_recovery(ch, g->f, x, chain) : chain());
 }
 
 extern "C" int cindm_ddpm2d_sample(cindm_ddpm1d* s, cindm_unet2d* u, float* x, int64_t B, int32_t nb, int32_t use_average_share,
                                    const float* noise_state_steps, const float* noise_boundary_steps, uint64_t seed,
                                    int64_t sample_offset, int32_t t_start, int32_t t_end, void* ws, size_t ws_bytes,
                                    void* stream_, int32_t use_graph) {
-    RecScope rs(s);
-    Known2DScope ks(s);
-    Known1DScope k1(s);
-    QuadTablesScope qs(s);
-    PairTablesScope ps(s);
-    MultistepScope ms(s);
-    if (qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0) return -1;
-    if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
-                          "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
+    ChainArmed took(s);
+    if (took.refuse_all_but(kServesKnown2, kKnown1Not2D) != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const int nsteps = t_start - t_end + 1;
-    if (ms_refuse(ms) != 0 || chain2_refuse(ch, x, nullptr, t_start, t_end) != 0) return -1;
+    if (chain2_refuse(ch, x, nullptr, t_start, t_end) != 0) return -1;
     const Draws2 z{noise_state_steps, noise_boundary_steps, seed, sample_offset};
-    if (rec_begin2(rs, ch, x, nsteps) != 0 || known2_begin(ks, ch, x, z) != 0) return -1;
+    if (rec_begin2(took, ch, x, nsteps) != 0 || known2_begin(took, ch, x, z) != 0) return -1;
     if (chain_stream(s, stream_, use_graph, &ch.stream) != 0) return -1;
     const Step2IO io = chain_io2(ch, x, z);
-    return run_chain2(rs, ch, nullptr, x, t_start, false, nsteps, ddpm_step2(ch, io, x));
+    return run_chain2(took, ch, nullptr, x, t_start, false, nsteps, ddpm_step2(ch, io, x));
 }
 
 extern "C" int cindm_ddpm2d_sample_ddim(cindm_ddpm1d* s, cindm_unet2d* u, float* x, int64_t B, int32_t nb, int32_t use_average_share,
                                         int32_t n_steps, const int32_t* times, const float* coefs, void* tab, size_t tab_bytes,
                                         const float* noise_state_steps, const float* noise_boundary_steps, uint64_t seed,
                                         int64_t sample_offset, void* ws, size_t ws_bytes, void* stream_, int32_t use_graph) {
-    RecScope rs(s);
-    Known2DScope ks(s);
-    Known1DScope k1(s);
-    QuadTablesScope qs(s);
-    PairTablesScope ps(s);
-    MultistepScope ms(s);
-    if (qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0) return -1;
-    if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
-                          "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
+    ChainArmed took(s);
+    if (took.refuse_all_but(kServesKnown2 | kServesMultistep, kKnown1Not2D) != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const Ddim2dCall dd{n_steps, times, coefs, nullptr, tab, tab_bytes};
-    if (chain2_refuse(ch, x, &dd) != 0 || ms_begin2(ms, ch, dd, x) != 0) return -1;
-    if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    if (chain2_refuse(ch, x, &dd) != 0 || ms_begin2(took, ch, dd, x) != 0) return -1;
+    if (took.rec.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     const Draws2 z{noise_state_steps, noise_boundary_steps, seed, sample_offset};
-    if (rec_begin2(rs, ch, x, n_steps, kNoX0Ddim2d) != 0 || known2_begin(ks, ch, x, z) != 0) return -1;
+    if (rec_begin2(took, ch, x, n_steps, kNoX0Ddim2d) != 0 || known2_begin(took, ch, x, z) != 0) return -1;
     if (chain_stream(s, stream_, use_graph, &ch.stream) != 0) return -1;
     int* tn_dev = nullptr;      // the per-step tables go to the caller's device buffer
     if (upload_ddim_tables(s->T, n_steps, times, coefs, (float*)tab, ch.stream, &tn_dev) != 0) return -1;
     const float* kappa_dev = nullptr;
     if (ms_tables2(ch, dd, &kappa_dev) != 0) return -1;
-    ks.k.tnext = tn_dev;
+    took.kn.tnext = tn_dev;
     const Ddim2dArgs a = ddim_args2(ch, x, dd, tn_dev, z);
-    return run_chain2(rs, ch, nullptr, x, times[0], true, n_steps, ddim_step2(ch, a, x, nullptr, kappa_dev, kappa_dev ? ms.m.hist : nullptr));
+    return run_chain2(took, ch, nullptr, x, times[0], true, n_steps, ddim_step2(ch, a, x, nullptr, kappa_dev, kappa_dev ? took.ms.hist : nullptr));
 }
 
 // Design-guided 2-D sampling with the airfoil objective INSIDE the captured step (ddpm_step2)
@@ -395,24 +385,17 @@ extern "C" int cindm_ddpm2d_sample_force(cindm_ddpm1d* s, cindm_unet2d* u, cindm
                                          float lambda_force, float lambda_overlap, int32_t down_factor, int32_t sum_boundary,
                                          const float* eta, float* grad, void* ws, size_t ws_bytes, void* ws_force,
                                          size_t ws_force_bytes, void* stream_, int32_t use_graph) {
-    RecScope rs(s);
-    Known2DScope ks(s);
-    Known1DScope k1(s);
-    QuadTablesScope qs(s);
-    PairTablesScope ps(s);
-    MultistepScope ms(s);
-    if (qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0) return -1;
-    if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
-                          "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
+    ChainArmed took(s);
+    if (took.refuse_all_but(kServesKnown2, kKnown1Not2D) != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const ForceGuide g{f, frames, p_min, p_max, lambda_force, lambda_overlap, down_factor, sum_boundary, grad, ws_force, ws_force_bytes};
     const int nsteps = t_start - t_end + 1;
-    if (ms_refuse(ms) != 0 || chain2_refuse(ch, x, nullptr, t_start, t_end) != 0 || force_refuse(ch, g, x, eta) != 0) return -1;
+    if (chain2_refuse(ch, x, nullptr, t_start, t_end) != 0 || force_refuse(ch, g, x, eta) != 0) return -1;
     const Draws2 z{noise_state_steps, noise_boundary_steps, seed, sample_offset};
-    if (rec_begin2(rs, ch, x, nsteps) != 0 || known2_begin(ks, ch, x, z) != 0) return -1;
+    if (rec_begin2(took, ch, x, nsteps) != 0 || known2_begin(took, ch, x, z) != 0) return -1;
     if (chain_stream(s, stream_, use_graph, &ch.stream) != 0) return -1;
     const Step2IO io = chain_io2(ch, x, z);
-    return run_chain2(rs, ch, &g, x, t_start, false, nsteps, ddpm_step2(ch, io, x, &g, eta));
+    return run_chain2(took, ch, &g, x, t_start, false, nsteps, ddpm_step2(ch, io, x, &g, eta));
 }
 
 // Guided DDIM of the 2-D path with the airfoil objective inside the captured step (ddim_step2)
@@ -423,28 +406,21 @@ extern "C" int cindm_ddpm2d_sample_ddim_force(cindm_ddpm1d* s, cindm_unet2d* u, 
                                               float p_min, float p_max, float lambda_force, float lambda_overlap, int32_t down_factor,
                                               int32_t sum_boundary, float* grad, void* ws, size_t ws_bytes, void* ws_force,
                                               size_t ws_force_bytes, void* stream_, int32_t use_graph) {
-    RecScope rs(s);
-    Known2DScope ks(s);
-    Known1DScope k1(s);
-    QuadTablesScope qs(s);
-    PairTablesScope ps(s);
-    MultistepScope ms(s);
-    if (qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0) return -1;
-    if (known1_refuse(k1, "it belongs to the 1-D chains (cindm_ddpm1d_sample / _sample_guided / _sample_ddim / _sample_ddim_guided); the 2-D "
-                          "chains take theirs from cindm_ddpm1d_set_known2d") != 0) return -1;
+    ChainArmed took(s);
+    if (took.refuse_all_but(kServesKnown2 | kServesMultistep, kKnown1Not2D) != 0) return -1;
     Chain2D ch(s, u, B, nb, use_average_share, ws, ws_bytes, nullptr, use_graph);
     const Ddim2dCall dd{n_steps, times, coefs, weights, tab, tab_bytes};
     const ForceGuide g{f, frames, p_min, p_max, lambda_force, lambda_overlap, down_factor, sum_boundary, grad, ws_force, ws_force_bytes};
-    if (chain2_refuse(ch, x, &dd) != 0 || force_refuse(ch, g, x, weights) != 0 || ms_begin2(ms, ch, dd, x) != 0) return -1;
-    if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    if (chain2_refuse(ch, x, &dd) != 0 || force_refuse(ch, g, x, weights) != 0 || ms_begin2(took, ch, dd, x) != 0) return -1;
+    if (took.rec.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
     const Draws2 z{noise_state_steps, noise_boundary_steps, seed, sample_offset};
-    if (rec_begin2(rs, ch, x, n_steps, kNoX0Ddim2d) != 0 || known2_begin(ks, ch, x, z) != 0) return -1;
+    if (rec_begin2(took, ch, x, n_steps, kNoX0Ddim2d) != 0 || known2_begin(took, ch, x, z) != 0) return -1;
     if (chain_stream(s, stream_, use_graph, &ch.stream) != 0) return -1;
     int* tn_dev = nullptr;
     if (upload_ddim_tables(s->T, n_steps, times, coefs, (float*)tab, ch.stream, &tn_dev, weights) != 0) return -1;
     const float* kappa_dev = nullptr;
     if (ms_tables2(ch, dd, &kappa_dev) != 0) return -1;
-    ks.k.tnext = tn_dev;
+    took.kn.tnext = tn_dev;
     const Ddim2dArgs a = ddim_args2(ch, x, dd, tn_dev, z);
-    return run_chain2(rs, ch, &g, x, times[0], true, n_steps, ddim_step2(ch, a, x, &g, kappa_dev, kappa_dev ? ms.m.hist : nullptr));
+    return run_chain2(took, ch, &g, x, times[0], true, n_steps, ddim_step2(ch, a, x, &g, kappa_dev, kappa_dev ? took.ms.hist : nullptr));
 }

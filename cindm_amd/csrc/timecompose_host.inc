@@ -14,19 +14,12 @@ extern "C" int cindm_ddpm1d_sample_timecompose(cindm_ddpm1d* h, cindm_unet1d* pa
                                                const int32_t* times, const float* coefs, const uint64_t* seeds, const float* init_tape,
                                                const float* noise_steps, int64_t sample_offset, int64_t B, void* ws, size_t ws_bytes,
                                                void* stream_, int32_t use_graph) {
-    RecScope rs(h);
-    DesignTablesScope ts(h);
-    Known2DScope ks(h);
-    Known1DScope k1(h);
-    QuadTablesScope qs(h);
-    PairTablesScope ps(h);
-    MultistepScope ms(h);
+    ChainArmed took(h);
     REQUIRE(n_seg >= 2 && B >= 1 && (int64_t)n_seg * B <= 65535, "n_seg must be >= 2 and n_seg * B <= 65535 (the update derives a row's segment by a 32-bit multiply)");
     Chain1D ch(h, pair, uncond, c, (int64_t)n_seg * B, ws, ws_bytes, nullptr, use_graph);
     const Ddim1Call dd{n_steps, times, coefs};
-    if (ms_refuse(ms) != 0 || dzt_refuse(ts) != 0 || qdt_refuse(qs) != 0 || pdt_refuse(ps) != 0 || known2_refuse(ks) != 0) return -1;
-    if (known1_refuse(k1, "the parallel time composition hands rows of one segment's state over to the next one's condition at every "
-                          "step: a region of one [B, rows, F] state does not name a place in its n_seg * B rows") != 0) return -1;
+    if (took.refuse_all_but(0, "the parallel time composition hands rows of one segment's state over to the next one's condition at every "
+                               "step: a region of one [B, rows, F] state does not name a place in its n_seg * B rows") != 0) return -1;
     REQUIRE(h && pair && c && x && cond && cond_buf && times && coefs && seeds, "null argument");
     REQUIRE(c->mode == CINDM_COMPOSE_PLAIN || c->mode == CINDM_COMPOSE_MULTIBODY, "the time composition runs the plain (or multibody) prediction");
     REQUIRE(c->cond_steps >= 1, "conditioned_steps == 0: the reference's img_infered[:, -0:] hands over the whole state and its slice assignment fails");
@@ -35,8 +28,8 @@ extern "C" int cindm_ddpm1d_sample_timecompose(cindm_ddpm1d* h, cindm_unet1d* pa
     for (const void* p : {(const void*)x, (const void*)cond, (const void*)cond_buf, (const void*)init_tape, (const void*)noise_steps})
         REQUIRE(((uintptr_t)p & 15) == 0, "x, cond, cond_buf, init_tape and noise_steps must be 16-byte aligned");
     if (chain1_refuse(ch, x, cond_buf, &dd) != 0) return -1;
-    if (rs.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
-    if (rec_begin(rs, x, n_steps, ch.n_state()) != 0) return -1;
+    if (took.rec.on()) REQUIRE(n_steps >= 1, "n_steps must be >= 1");
+    if (rec_begin(took, x, n_steps, ch.n_state()) != 0) return -1;
     if (chain_stream(h, stream_, use_graph, &ch.stream) != 0) return -1;
     const int64_t n_state = ch.n_state();
     hipStream_t stream = ch.stream;
@@ -52,7 +45,7 @@ extern "C" int cindm_ddpm1d_sample_timecompose(cindm_ddpm1d* h, cindm_unet1d* pa
     tc.seg_magic = ((1ull << 32) + (unsigned long long)B - 1) / (unsigned long long)B;
     io.tc = &tc;
     const unsigned iblocks = (unsigned)((n_state / 4 + 255) / 256);
-    return rec_done(rs, run_chain_with_recovery(ch, x, [&]() -> int {
+    return rec_done(took, run_chain_with_recovery(ch, x, [&]() -> int {
         if (prepare_step_ws(ch) != 0) return -1;
         hipLaunchKernelGGL(timecompose_init_kernel, dim3(iblocks), dim3(256), 0, stream, x, cond_buf, cond, init_tape,
                            (const unsigned long long*)seeds_dev, B, tc.seg_magic, (int)n_seg, R, F, Lc, sample_offset, (uint32_t)h->T);

@@ -33,7 +33,7 @@ from torch import nn
 
 from . import _ffi
 from .diffusion_base import DiffusionHandle
-from .objectives import PairDistanceObjective, PointObjective, QuadraticObjective, WaypointObjective
+from .objectives import PointObjective, _TableObjective
 from .record import DeviceRecorder, LoopRecorder, record_schedule, stream_mask
 from .schedule import check_solver, make_schedule, ula_schedule
 
@@ -284,7 +284,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         """(descriptor, tables) when ``design_fn`` under ``design_guidance`` runs inside the captured step -- a PointObjective whose
         last_n_step fits the state, a WaypointObjective, a QuadraticObjective or a PairDistanceObjective -- else (None, None).  A table objective whose tables
         do not fit the state [B, L, 4 * n_bodies] is a ValueError on every route, before any device work."""
-        if isinstance(design_fn, (WaypointObjective, QuadraticObjective, PairDistanceObjective)):
+        if isinstance(design_fn, _TableObjective):
             design_fn.check_state(B, L, n_bodies)
             dz = design_fn.descriptor(design_guidance)
             return dz, (design_fn if dz is not None else None)

@@ -33,6 +33,23 @@ import torch
 from . import _ffi
 
 
+def _parse_guidance(design_guidance):
+    """(alpha, recurrence) of a guidance the library's guided chains evaluate -- "standard" / "standard-alpha", optionally with
+    ``-recurrence-N``, N >= 1 an integer -- or None when it needs the generic (autograd) path."""
+    g, rec = design_guidance, 0
+    if "recurrence" in g:
+        try:
+            rec = int(g.split("-")[-1])
+        except ValueError:
+            return None
+        g = g[:g.index("-recurrence")]
+        if rec < 1:
+            return None
+    if g not in ("standard", "standard-alpha"):
+        return None
+    return int(g == "standard-alpha"), rec
+
+
 class PointObjective:
     def __init__(self, pos_target, last_n_step, gamma=2, coef=100, time_consistency_coef=0, design_fn_mode="L2"):
         pos_target = torch.as_tensor(pos_target, dtype=torch.float32).reshape(-1)
@@ -63,25 +80,100 @@ class PointObjective:
     def descriptor(self, design_guidance):
         """cindm_design_desc for this objective under ``design_guidance``, or None when that guidance needs the generic
         (autograd) path."""
-        g = design_guidance
-        rec = 0
-        if "recurrence" in g:
-            rec = int(g.split("-")[-1])
-            g = g[:g.index("-recurrence")]
-            if rec < 1:
-                return None
-        if g not in ("standard", "standard-alpha"):
+        parsed = _parse_guidance(design_guidance)
+        if parsed is None:
             return None
         d = _ffi.DesignDesc()
         d.mode = 1 if self.design_fn_mode == "L2" else 2
-        d.alpha = int(g == "standard-alpha")
-        d.recurrence, d.last_n_step = rec, self.last_n_step
+        d.alpha, d.recurrence = parsed
+        d.last_n_step = self.last_n_step
         d.coef, d.time_consistency_coef = self.coef, self.time_consistency_coef
         d.pos_target[0], d.pos_target[1] = float(self.pos_target[0]), float(self.pos_target[1])
         return d
 
 
-class WaypointObjective:
+class _TableObjective:
+    """What the table objectives share.  A subclass declares ``_TABLES``, its table attributes with the rank each has when it is
+    shared by every design (one more: per design); ``_WIDTH``, the attribute that counts what a row of its tables holds, the noun
+    for it and how many a body has; ``_SETTER``, the library entry that arms its two device tables; ``mode``, its descriptor mode.
+    ``rows`` and the width attribute are the subclass's own."""
+    _TABLES, _WIDTH, _SETTER = (), ("n_bodies", "bodies", 1), ""
+
+    @property
+    def per_design(self):
+        """Designs the per-design tables are for, or None when all tables are shared by every design."""
+        for name, rank in self._TABLES:
+            v = getattr(self, name)
+            if v.dim() == rank + 1:
+                return v.shape[0]
+        return None
+
+    def check_state(self, B, L, n_bodies):
+        """ValueError unless the tables fit a state [B, L, 4 * n_bodies]."""
+        cls = type(self).__name__
+        attr, noun, per_body = self._WIDTH
+        if self.rows != L:
+            raise ValueError(f"{cls}: tables of {self.rows} rows, the state has {L}")
+        if getattr(self, attr) != per_body * n_bodies:
+            raise ValueError(f"{cls}: tables of {getattr(self, attr)} {noun}, the state has {per_body * n_bodies}")
+        if self.per_design is not None and self.per_design != B:
+            raise ValueError(f"{cls}: per-design tables for {self.per_design} designs, the batch has {B} "
+                             "(shard(lo, hi) slices them for a part of the batch)")
+
+    def shard(self, lo, hi):
+        """The objective of designs lo .. hi-1: per-design tables sliced, tables shared by every design passed through."""
+        o = copy.copy(self)
+        for name, rank in self._TABLES:
+            v = getattr(self, name)
+            setattr(o, name, v[lo:hi].contiguous() if v.dim() == rank + 1 else v)
+        o._dev = {}
+        return o
+
+    def _host_tables(self):
+        """The two tables the kernel reads, on the CPU: [L, ..] or [B, L, ..] each."""
+        return tuple(getattr(self, name) for name, _ in self._TABLES)
+
+    def tables(self, device):
+        """The two contiguous fp32 tensors on ``device`` (cached per device) the kernel reads."""
+        device = torch.device(device)
+        if device not in self._dev:
+            self._dev[device] = tuple(v.to(device).contiguous() for v in self._host_tables())
+        return self._dev[device]
+
+    def _time_consistency(self, pos, n_bodies):
+        idx = torch.cat([torch.arange(ii * 4, ii * 4 + 2) for ii in range(n_bodies)]).to(pos.device)
+        return (pos[:, 1:, idx] - pos[:, :-1, idx]).square().sum(-1).mean(-1).sum() * self.time_consistency_coef
+
+    def _time_consistency_grad(self, x):
+        """The time-consistency term of ``closed_form_grad`` on the positions x [B, L, nb, 2], L > 1, as the kernels evaluate it:
+        ((tc * 2) * lap) / (L - 1),  lap = (x_l - x_{l-1}) [l >= 1] - (x_{l+1} - x_l) [l + 1 < L]."""
+        lap = torch.zeros_like(x)
+        lap[:, 1:] += x[:, 1:] - x[:, :-1]
+        lap[:, :-1] -= x[:, 1:] - x[:, :-1]
+        return self.time_consistency_coef * 2.0 * lap / float(x.shape[1] - 1)
+
+    def descriptor(self, design_guidance):
+        """cindm_design_desc (the tables are armed per call) for this objective under ``design_guidance``, or None when that
+        guidance needs the generic (autograd) path."""
+        parsed = _parse_guidance(design_guidance)
+        if parsed is None:
+            return None
+        d = _ffi.DesignDesc()
+        d.mode = self.mode
+        d.alpha, d.recurrence = parsed
+        d.time_consistency_coef = self.time_consistency_coef
+        return d
+
+    def arm(self, handle, B, device):
+        """Arms the next guided chain call on ``handle`` (a cindm_ddpm1d) with this objective's tables, for a batch of ``B`` designs
+        (per-design tables declare their own extent: the chain call refuses another batch)."""
+        a, b = self.tables(device)          # [B | -, L, .., ..] and [B | -, L, ..]
+        batch = B if self.per_design is None else self.per_design
+        _ffi.check(getattr(_ffi.lib(), self._SETTER)(handle, _ffi.ptr(a), int(a.dim() == 4), _ffi.ptr(b), int(b.dim() == 3),
+                                                     self.rows, getattr(self, self._WIDTH[0]), batch))
+
+
+class WaypointObjective(_TableObjective):
     """``target`` [L, nb, 2] or [B, L, nb, 2]: the position (features 4j, 4j+1) body j is drawn to at that row, in state units.
     ``weight`` [L, nb] or [B, L, nb]: finite, >= 0; 0 = no waypoint at that (row, body).  The value for pos [B, L, 4*nb] is
 
@@ -133,6 +225,12 @@ class WaypointObjective:
         return cls(pt.expand(L, nb, 2), None, time_consistency_coef=time_consistency_coef, design_fn_mode=design_fn_mode, _scale=scale)
 
     # ------------------------------------------------------------------ shapes
+    _TABLES, _SETTER = (("target", 3), ("scale", 2)), "cindm_ddpm1d_set_design_tables"
+
+    @property
+    def mode(self):
+        return 3 if self.design_fn_mode == "L2" else 4
+
     @property
     def rows(self):
         return self.scale.shape[-2]
@@ -141,43 +239,7 @@ class WaypointObjective:
     def n_bodies(self):
         return self.scale.shape[-1]
 
-    @property
-    def per_design(self):
-        """Designs the per-design tables are for, or None when both tables are shared by every design."""
-        if self.target.dim() == 4:
-            return self.target.shape[0]
-        return self.scale.shape[0] if self.scale.dim() == 3 else None
-
-    def check_state(self, B, L, n_bodies):
-        """ValueError unless the tables fit a state [B, L, 4 * n_bodies]."""
-        if self.rows != L:
-            raise ValueError(f"WaypointObjective: tables of {self.rows} rows, the state has {L}")
-        if self.n_bodies != n_bodies:
-            raise ValueError(f"WaypointObjective: tables of {self.n_bodies} bodies, the state has {n_bodies}")
-        if self.per_design is not None and self.per_design != B:
-            raise ValueError(f"WaypointObjective: per-design tables for {self.per_design} designs, the batch has {B} "
-                             "(shard(lo, hi) slices them for a part of the batch)")
-
-    def shard(self, lo, hi):
-        """The objective of designs lo .. hi-1: per-design tables sliced, tables shared by every design passed through."""
-        o = copy.copy(self)
-        o.target = self.target[lo:hi].contiguous() if self.target.dim() == 4 else self.target
-        o.scale = self.scale[lo:hi].contiguous() if self.scale.dim() == 3 else self.scale
-        o._dev = {}
-        return o
-
-    def tables(self, device):
-        """(target, scale): the two contiguous fp32 tensors on ``device`` (cached per device) the kernel reads."""
-        device = torch.device(device)
-        if device not in self._dev:
-            self._dev[device] = (self.target.to(device).contiguous(), self.scale.to(device).contiguous())
-        return self._dev[device]
-
     # ------------------------------------------------------------------ value and gradient
-    def _time_consistency(self, pos, n_bodies):
-        idx = torch.cat([torch.arange(ii * 4, ii * 4 + 2) for ii in range(n_bodies)]).to(pos.device)
-        return (pos[:, 1:, idx] - pos[:, :-1, idx]).square().sum(-1).mean(-1).sum() * self.time_consistency_coef
-
     def __call__(self, pos):
         """pos: [B, L, n_bodies*4] -> scalar loss (summed over the batch)."""
         B, L, F = pos.shape
@@ -213,42 +275,13 @@ class WaypointObjective:
             g = s * 2.0 * d
         g = torch.where(on, g, torch.zeros_like(g))
         if self.time_consistency_coef > 0 and L > 1:
-            lap = torch.zeros_like(x)
-            lap[:, 1:] += x[:, 1:] - x[:, :-1]
-            lap[:, :-1] -= x[:, 1:] - x[:, :-1]
-            g = g + self.time_consistency_coef * 2.0 * lap / float(L - 1)
+            g = g + self._time_consistency_grad(x)
         out = torch.zeros_like(pos).reshape(B, L, F // 4, 4)
         out[..., :2] = g
         return out.reshape(B, L, F)
 
-    def descriptor(self, design_guidance):
-        """cindm_design_desc (mode 3 / 4: the tables are armed per call) for this objective under ``design_guidance``, or None when
-        that guidance needs the generic (autograd) path."""
-        g = design_guidance
-        rec = 0
-        if "recurrence" in g:
-            rec = int(g.split("-")[-1])
-            g = g[:g.index("-recurrence")]
-            if rec < 1:
-                return None
-        if g not in ("standard", "standard-alpha"):
-            return None
-        d = _ffi.DesignDesc()
-        d.mode = 3 if self.design_fn_mode == "L2" else 4
-        d.alpha = int(g == "standard-alpha")
-        d.recurrence, d.time_consistency_coef = rec, self.time_consistency_coef
-        return d
 
-    def arm(self, handle, B, device):
-        """Arms the next guided chain call on ``handle`` (a cindm_ddpm1d) with this objective's tables, for a batch of ``B`` designs
-        (per-design tables declare their own extent: the chain call refuses another batch)."""
-        target, scale = self.tables(device)
-        batch = B if self.per_design is None else self.per_design
-        _ffi.check(_ffi.lib().cindm_ddpm1d_set_design_tables(handle, _ffi.ptr(target), int(target.dim() == 4), _ffi.ptr(scale),
-                                                            int(scale.dim() == 3), self.rows, self.n_bodies, batch))
-
-
-class QuadraticObjective:
+class QuadraticObjective(_TableObjective):
     """``S`` [L, F, F] or [B, L, F, F]: a symmetric matrix per row (exactly: S[.., f, g] == S[.., g, f]); ``h`` [L, F] or [B, L, F].
     F = 4 * n_bodies, a multiple of 4 up to 32.  The value for pos [B, L, F] is
 
@@ -315,6 +348,8 @@ class QuadraticObjective:
         return cls(S.to(torch.float32), hh.to(torch.float32), time_consistency_coef=time_consistency_coef)
 
     # ------------------------------------------------------------------ shapes
+    _TABLES, _WIDTH, _SETTER, mode = (("S", 3), ("h", 2)), ("features", "features", 4), "cindm_ddpm1d_set_design_quadratic", 5
+
     @property
     def rows(self):
         return self.h.shape[-2]
@@ -323,43 +358,7 @@ class QuadraticObjective:
     def features(self):
         return self.h.shape[-1]
 
-    @property
-    def per_design(self):
-        """Designs the per-design tables are for, or None when both tables are shared by every design."""
-        if self.S.dim() == 4:
-            return self.S.shape[0]
-        return self.h.shape[0] if self.h.dim() == 3 else None
-
-    def check_state(self, B, L, n_bodies):
-        """ValueError unless the tables fit a state [B, L, 4 * n_bodies]."""
-        if self.rows != L:
-            raise ValueError(f"QuadraticObjective: tables of {self.rows} rows, the state has {L}")
-        if self.features != 4 * n_bodies:
-            raise ValueError(f"QuadraticObjective: tables of {self.features} features, the state has {4 * n_bodies}")
-        if self.per_design is not None and self.per_design != B:
-            raise ValueError(f"QuadraticObjective: per-design tables for {self.per_design} designs, the batch has {B} "
-                             "(shard(lo, hi) slices them for a part of the batch)")
-
-    def shard(self, lo, hi):
-        """The objective of designs lo .. hi-1: per-design tables sliced, tables shared by every design passed through."""
-        o = copy.copy(self)
-        o.S = self.S[lo:hi].contiguous() if self.S.dim() == 4 else self.S
-        o.h = self.h[lo:hi].contiguous() if self.h.dim() == 3 else self.h
-        o._dev = {}
-        return o
-
-    def tables(self, device):
-        """(S, h): the two contiguous fp32 tensors on ``device`` (cached per device) the kernel reads."""
-        device = torch.device(device)
-        if device not in self._dev:
-            self._dev[device] = (self.S.to(device).contiguous(), self.h.to(device).contiguous())
-        return self._dev[device]
-
     # ------------------------------------------------------------------ value and gradient
-    def _time_consistency(self, pos, n_bodies):
-        idx = torch.cat([torch.arange(ii * 4, ii * 4 + 2) for ii in range(n_bodies)]).to(pos.device)
-        return (pos[:, 1:, idx] - pos[:, :-1, idx]).square().sum(-1).mean(-1).sum() * self.time_consistency_coef
-
     def __call__(self, pos):
         """pos: [B, L, F] -> scalar loss (summed over the batch)."""
         B, L, F = pos.shape
@@ -384,42 +383,10 @@ class QuadraticObjective:
         g = acc - h
         if self.time_consistency_coef > 0 and L > 1:
             x = pos.reshape(B, L, F // 4, 4)[..., :2]
-            lap = torch.zeros_like(x)
-            lap[:, 1:] += x[:, 1:] - x[:, :-1]
-            lap[:, :-1] -= x[:, 1:] - x[:, :-1]
             g = g.reshape(B, L, F // 4, 4).clone()
-            g[..., :2] = g[..., :2] + self.time_consistency_coef * 2.0 * lap / float(L - 1)
+            g[..., :2] = g[..., :2] + self._time_consistency_grad(x)
             g = g.reshape(B, L, F)
         return g
-
-    def descriptor(self, design_guidance):
-        """cindm_design_desc (mode 5: the tables are armed per call) for this objective under ``design_guidance``, or None when that
-        guidance needs the generic (autograd) path."""
-        g = design_guidance
-        rec = 0
-        if "recurrence" in g:
-            try:
-                rec = int(g.split("-")[-1])
-            except ValueError:
-                return None
-            g = g[:g.index("-recurrence")]
-            if rec < 1:
-                return None
-        if g not in ("standard", "standard-alpha"):
-            return None
-        d = _ffi.DesignDesc()
-        d.mode = 5
-        d.alpha = int(g == "standard-alpha")
-        d.recurrence, d.time_consistency_coef = rec, self.time_consistency_coef
-        return d
-
-    def arm(self, handle, B, device):
-        """Arms the next guided chain call on ``handle`` (a cindm_ddpm1d) with this objective's tables, for a batch of ``B`` designs
-        (per-design tables declare their own extent: the chain call refuses another batch)."""
-        S, h = self.tables(device)
-        batch = B if self.per_design is None else self.per_design
-        _ffi.check(_ffi.lib().cindm_ddpm1d_set_design_quadratic(handle, _ffi.ptr(S), int(S.dim() == 4), _ffi.ptr(h), int(h.dim() == 3),
-                                                               self.rows, self.features, batch))
 
 
 _PAIR_COUNTS = {nb * (nb - 1) // 2: nb for nb in range(2, 9)}        # P -> n_bodies, 2 .. 8 bodies
@@ -430,7 +397,7 @@ def pair_index(i, j, n_bodies):
     return i * n_bodies - (i * (i + 1)) // 2 + (j - i - 1)
 
 
-class PairDistanceObjective:
+class PairDistanceObjective(_TableObjective):
     """``lo``, ``hi``, ``weight``: each [L, P] or [B, L, P], P = nb (nb - 1) / 2 pairs (i, j), i < j, in the order of ``pair_index``.
     0 <= lo <= hi, lo finite, hi finite or +inf; weight finite, >= 0 (0 = no relation at that (row, pair)).  With r the distance
     between the positions (features 4i, 4i+1 and 4j, 4j+1) of the pair's bodies, the value for pos [B, L, 4 * nb] is
@@ -495,6 +462,8 @@ class PairDistanceObjective:
         return cls(lo, lo.clone(), weight, time_consistency_coef=time_consistency_coef)
 
     # ------------------------------------------------------------------ shapes
+    _TABLES, _SETTER, mode = (("lo", 2), ("hi", 2), ("weight", 2)), "cindm_ddpm1d_set_design_pairdist", 6
+
     @property
     def rows(self):
         return self.weight.shape[-2]
@@ -503,52 +472,20 @@ class PairDistanceObjective:
     def n_bodies(self):
         return _PAIR_COUNTS[self.weight.shape[-1]]
 
-    @property
-    def per_design(self):
-        """Designs the per-design tables are for, or None when all tables are shared by every design."""
-        for v in (self.lo, self.hi, self.weight):
-            if v.dim() == 3:
-                return v.shape[0]
-        return None
-
-    def check_state(self, B, L, n_bodies):
-        """ValueError unless the tables fit a state [B, L, 4 * n_bodies]."""
-        if self.rows != L:
-            raise ValueError(f"PairDistanceObjective: tables of {self.rows} rows, the state has {L}")
-        if self.n_bodies != n_bodies:
-            raise ValueError(f"PairDistanceObjective: tables of {self.n_bodies} bodies, the state has {n_bodies}")
-        if self.per_design is not None and self.per_design != B:
-            raise ValueError(f"PairDistanceObjective: per-design tables for {self.per_design} designs, the batch has {B} "
-                             "(shard(lo, hi) slices them for a part of the batch)")
-
-    def shard(self, lo, hi):
-        """The objective of designs lo .. hi-1: per-design tables sliced, tables shared by every design passed through."""
-        o = copy.copy(self)
-        o.lo, o.hi, o.weight = (v[lo:hi].contiguous() if v.dim() == 3 else v for v in (self.lo, self.hi, self.weight))
-        o._dev = {}
-        return o
-
-    def tables(self, device):
-        """(band, weight): the two contiguous fp32 tensors on ``device`` (cached per device) the kernel reads.  band [B | -, L, P, 2]
-        holds (lo, hi) interleaved; lo and hi share one per-design flag: where either is per design both are materialised."""
-        device = torch.device(device)
-        if device not in self._dev:
-            lo, hi = self.lo, self.hi
-            if lo.dim() != hi.dim():
-                shape = lo.shape if lo.dim() == 3 else hi.shape
-                lo, hi = lo.expand(shape), hi.expand(shape)
-            self._dev[device] = (torch.stack((lo, hi), dim=-1).contiguous().to(device), self.weight.to(device).contiguous())
-        return self._dev[device]
+    def _host_tables(self):
+        """(band, weight): band [B | -, L, P, 2] holds (lo, hi) interleaved; lo and hi share one per-design flag: where either is per
+        design both are materialised."""
+        lo, hi = self.lo, self.hi
+        if lo.dim() != hi.dim():
+            shape = lo.shape if lo.dim() == 3 else hi.shape
+            lo, hi = lo.expand(shape), hi.expand(shape)
+        return torch.stack((lo, hi), dim=-1), self.weight
 
     # ------------------------------------------------------------------ value and gradient
     def _pairs(self):
         nb = self.n_bodies
         ij = [(i, j) for i in range(nb) for j in range(i + 1, nb)]
         return torch.tensor([i for i, _ in ij]), torch.tensor([j for _, j in ij])
-
-    def _time_consistency(self, pos, n_bodies):
-        idx = torch.cat([torch.arange(ii * 4, ii * 4 + 2) for ii in range(n_bodies)]).to(pos.device)
-        return (pos[:, 1:, idx] - pos[:, :-1, idx]).square().sum(-1).mean(-1).sum() * self.time_consistency_coef
 
     def __call__(self, pos):
         """pos: [B, L, n_bodies*4] -> scalar loss (summed over the batch)."""
@@ -600,39 +537,7 @@ class PairDistanceObjective:
                 acc = acc + torch.where(active, term, torch.zeros_like(term))
             g[:, :, i] = acc
         if self.time_consistency_coef > 0 and L > 1:
-            lap = torch.zeros_like(x)
-            lap[:, 1:] += x[:, 1:] - x[:, :-1]
-            lap[:, :-1] -= x[:, 1:] - x[:, :-1]
-            g = g + self.time_consistency_coef * 2.0 * lap / float(L - 1)
+            g = g + self._time_consistency_grad(x)
         out = torch.zeros_like(pos).reshape(B, L, nb, 4)
         out[..., :2] = g
         return out.reshape(B, L, F)
-
-    def descriptor(self, design_guidance):
-        """cindm_design_desc (mode 6: the tables are armed per call) for this objective under ``design_guidance``, or None when that
-        guidance needs the generic (autograd) path."""
-        g = design_guidance
-        rec = 0
-        if "recurrence" in g:
-            try:
-                rec = int(g.split("-")[-1])
-            except ValueError:
-                return None
-            g = g[:g.index("-recurrence")]
-            if rec < 1:
-                return None
-        if g not in ("standard", "standard-alpha"):
-            return None
-        d = _ffi.DesignDesc()
-        d.mode = 6
-        d.alpha = int(g == "standard-alpha")
-        d.recurrence, d.time_consistency_coef = rec, self.time_consistency_coef
-        return d
-
-    def arm(self, handle, B, device):
-        """Arms the next guided chain call on ``handle`` (a cindm_ddpm1d) with this objective's tables, for a batch of ``B`` designs
-        (per-design tables declare their own extent: the chain call refuses another batch)."""
-        band, weight = self.tables(device)
-        batch = B if self.per_design is None else self.per_design
-        _ffi.check(_ffi.lib().cindm_ddpm1d_set_design_pairdist(handle, _ffi.ptr(band), int(band.dim() == 4), _ffi.ptr(weight),
-                                                              int(weight.dim() == 3), self.rows, self.n_bodies, batch))

@@ -487,7 +487,7 @@ int  cindm_ddpm1d_recorder_info(const cindm_ddpm1d* h, int32_t info[4]);
  * cindm_ddpm1d_set_design_tables arms the NEXT chain call on this handle; that call consumes the tables whether it succeeds or
  * fails, and (NULL, NULL) disarms.  cindm_ddpm1d_sample_guided / _sample_ddim_guided check rows == L_tot, n_bodies == c->n_bodies,
  * batch == B and that both tables are 16-byte aligned before they launch or copy anything, and refuse modes 3 / 4 with nothing
- * armed and armed tables with modes 1 / 2; every other chain entry refuses armed tables.  The tables must stay alive and
+ * armed and armed tables with modes 1 / 2; every other chain entry, 1-D or 2-D, refuses armed tables.  The tables must stay alive and
  * unchanged until the chain's work has finished: with use_graph that is when the call returns (it synchronises; an exchange-free
  * re-run inside the call reads them again); with use_graph = 0 the steps are only enqueued on the caller's stream, so the tables
  * must outlive that stream's work (free or overwrite them after a synchronise, or in stream order).  Their addresses and the two

@@ -16,6 +16,7 @@ import torch
 import cindm_amd
 from cindm_amd import _ffi
 from test_ddim_guided_2d_host import WORK, _chunks, _with_helpers
+from test_host_logic import chain_entries
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "cindm_ddpm1d_sample_ddim_guided"
@@ -55,17 +56,16 @@ def test_entry_allocates_nothing():
         assert "chain_stream(" in body
         first_work = min(body.index(k) for k in WORK if k in body)
         assert max(body.rindex(k) for k in ("REQUIRE(", "_refuse(") if k in body) < first_work, entry
-        stmts = [ln.strip() for ln in body[body.index(") {") + 3:].split("\n") if ln.strip()]
-        assert stmts[:2] == ["RecScope rs(h);", "DesignTablesScope ts(h);"], entry      # the call consumes what was armed however it ends
+        # (that the call consumes what was armed however it ends: test_host_logic.py::test_every_chain_entry_takes_everything_armed)
         assert "chain1_refuse(" in body and "step1_refuse(" in used["chain1_refuse"]
-        assert ("guided_refuse(" in body) == entry.endswith("guided") and ("dzt_refuse(" in body) != entry.endswith("guided")
+        assert ("guided_refuse(" in body) == entry.endswith("guided") == ("kServesTables" in chain_entries()[entry]["serves"])
         # the chain runs under run_chain_with_recovery through replay_steps
         assert "run_chain_with_recovery" in used and "replay_steps" in used, entry
         assert "body()" in used["run_chain_with_recovery"]
     # the refusal functions themselves, the recorder's check and the design tables' issue no work
     for k in ("step1_refuse", "chain1_refuse", "guided_refuse"):
         assert not any(w in chunks[k] for w in WORK), k
-    for k in ("rec_begin", "dzt_begin", "dzt_refuse"):
+    for k in ("rec_begin", "design_begin", "design_refuse", "refuse_all_but"):
         assert not any(w in driver[k] for w in WORK), k
     # one layout per call: Chain1D's constructor computes it, the size query is the only other caller
     callers = sorted(k for k, v in chunks.items() if k != "step_layout" and "step_layout(" in v)

@@ -337,3 +337,30 @@ def test_refusals_leave_the_handle_usable(device, unet8, diff8):
     assert bool(torch.isfinite(diff8.sample(batch_size=B, n_composed=0, seed=3, t_stop=998)).all())
     assert torch.equal(run(obj.descriptor(guid), obj), good)
     assert bool(torch.isfinite(diff8.sample(design_fn=obj, **kw)).all())
+
+
+def test_2d_entries_refuse_armed_tables(device):
+    """The four 2-D chain entries take armed waypoint tables like everything else that is armed, and refuse them: the call fails with
+    the tables' message, and the same call passes afterwards -- the refused call consumed the tables."""
+    from test_gpu_multistep import CH, HW, _diff2, _force_objective          # (that module imports this one)
+    from test_gpu_parity_2d import build_unet2d
+    unet2d = build_unet2d(device)
+    force = cindm_amd.ForceUnet(dim=64, dim_mults=(1, 2, 4, 8), channels=4)
+    force.load_state_dict(O.synth_state_dict_2d(O.force_unet_param_shapes(), 7), strict=True)
+    force = force.to(device)
+    shape = (1, 2, CH, HW, HW)
+    fn = _force_objective(force, 1, 2)
+    target, scale = torch.zeros((2, 4, 2, 2), device=device), torch.ones((2, 4, 2), device=device)      # batch 2, 4 rows, 2 bodies
+
+    def armed_refusal(d, run):
+        _ffi.check(_ffi.lib().cindm_ddpm1d_set_design_tables(d._handle(), _ffi.ptr(target), 1, _ffi.ptr(scale), 1, 4, 2, 2))
+        with pytest.raises(cindm_amd.CindmError, match="design tables: only the guided chains"):
+            run()
+        assert bool(torch.isfinite(run()).all())
+
+    d = _diff2(device, unet2d, 1000)
+    armed_refusal(d, lambda: d.p_sample_loop(shape, seed=1, t_stop=998))                                  # cindm_ddpm2d_sample
+    armed_refusal(d, lambda: d.p_sample_loop(shape, fn, "standard-alpha", seed=1, t_stop=998))            # _sample_force
+    d2 = _diff2(device, unet2d, 2)
+    armed_refusal(d2, lambda: d2.ddim_sample(shape, seed=1))                                              # _sample_ddim
+    armed_refusal(d2, lambda: d2.ddim_sample(shape, fn, "standard-alpha", seed=1))                        # _sample_ddim_force

@@ -672,3 +672,88 @@ def test_graft_entry_build_checks_the_current_abi():
     import re
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "__graft_entry__.py")).read()
     assert "cindm_abi_version() == _ffi.ABI_VERSION" in src and not re.search(r"ABI_VERSION\s*==\s*\d", src)
+
+
+# ------------------------------------------------------------------ the rule of everything a caller arms for the next chain call
+CSRC = os.path.join(ROOT, "cindm_amd", "csrc")
+ENTRY_FILES = ("ddpm1d_host.inc", "timecompose_host.inc", "ddpm2d_host.inc")
+ENTRY_WORK = ("chain_stream(", "upload_ddim_tables(", "ddim_tables1(", "run_chain_with_recovery(", "run_chain2(", "loop_chain(", "guided_chain(",
+              "hipLaunchKernelGGL", "hipMemcpy", "hipMemset", "hipStreamSynchronize", "hipDeviceSynchronize")
+
+
+def chain_entries():
+    """name -> {"file", "body", "serves"} of every chain entry, comments stripped: the body from the signature to the closing brace in
+    column 0, and the flags the entry hands to refuse_all_but ("kServesKnown1", ..)."""
+    out = {}
+    for fn in ENTRY_FILES:
+        src = "\n".join(re.sub(r"//.*", "", ln).rstrip() for ln in open(os.path.join(CSRC, fn)).read().split("\n"))
+        for m in re.finditer(r'extern "C" int (cindm_ddpm[12]d_sample\w*)\(', src):
+            body = src[m.start():src.index("\n}", m.start()) + 2]
+            call = re.search(r"\.refuse_all_but\(([^,)]*)", body)
+            out[m.group(1)] = {"file": fn, "body": body, "serves": set(re.findall(r"kServes\w+", call.group(1))) if call else None}
+    return out
+
+
+def test_every_chain_entry_takes_everything_armed():
+    """The rule, stated once (chain_host.inc: ChainArmed): a chain entry's first statement takes everything armed on the handle --
+    recorder, the three kinds of design tables, both known regions, the multistep solver -- so the call consumes it however it ends;
+    the entry names what it serves in ONE refuse_all_but call ahead of its first work, and never reaches past the bundle into the
+    handle's armed state.  Nothing else constructs the bundle."""
+    entries = chain_entries()
+    assert sorted(entries) == sorted(
+        ["cindm_ddpm1d_sample", "cindm_ddpm1d_sample_ddim", "cindm_ddpm1d_sample_autoregress", "cindm_ddpm1d_sample_ula", "cindm_ddpm1d_sample_guided",
+         "cindm_ddpm1d_sample_ddim_guided", "cindm_ddpm1d_sample_timecompose", "cindm_ddpm2d_sample", "cindm_ddpm2d_sample_ddim",
+         "cindm_ddpm2d_sample_force", "cindm_ddpm2d_sample_ddim_force"])
+    for name, e in entries.items():
+        body = e["body"]
+        handle = re.search(r"\(cindm_ddpm1d\* (\w+),", body).group(1)              # the entry's first parameter
+        stmts = [ln.strip() for ln in body[body.index(") {") + 3:].split("\n") if ln.strip()]
+        assert stmts[0] == f"ChainArmed took({handle});", name
+        assert len(re.findall(r"\bChainArmed\b", body)) == 1, name
+        assert not re.search(r"(->|\.)armed\b", body), name                        # only through the bundle
+        assert body.count(".refuse_all_but(") == 1 and body.count("took.refuse_all_but(") == 1, name
+        first_work = min(body.index(k) for k in ENTRY_WORK if k in body)
+        assert body.index("took.refuse_all_but(") < first_work, name
+        assert "chain_stream(" in body, name
+    # no other function constructs one: outside the entries and the struct itself the type occurs as a reference parameter or as the
+    # qualifier of its member's definition
+    files = sorted(f for f in os.listdir(CSRC) if f.endswith((".inc", ".hip", ".h")))
+    assert set(ENTRY_FILES) <= set(files) and "chain_host.inc" in files
+    for fn in files:
+        src = "\n".join(re.sub(r"//.*", "", ln).rstrip() for ln in open(os.path.join(CSRC, fn)).read().split("\n"))
+        for e in entries.values():
+            if e["file"] == fn:
+                src = src.replace(e["body"].split("\n", 1)[1], "")
+        if fn == "chain_host.inc":
+            a = src.index("struct ChainArmed : Armed {")
+            src = src[:a] + src[src.index("\n};", a):]
+        for m in re.finditer(r"\bChainArmed\b", src):
+            assert src[m.end():m.end() + 2] in ("& ", "::"), (fn, src[m.start():m.start() + 60])
+    # the bundle: the handle keeps ONE armed struct, the constructor empties it and the last record's info, and the destructor clears
+    # every pointer a running chain holds into the bundle
+    driver = "\n".join(re.sub(r"//.*", "", ln) for ln in open(os.path.join(CSRC, "chain_host.inc")).read().split("\n"))
+    handle = driver[driver.index("struct cindm_ddpm1d {"):]
+    handle = handle[:handle.index("\n};")]
+    assert handle.count("Armed armed;") == 1 and "_armed" not in driver
+    held = re.findall(r"const (?:RecSpec|DesignTables|Known2D|Known1D|Multistep)\* (\w+) = nullptr", handle)
+    assert sorted(held) == ["dzt", "kn", "kn1", "ms", "rec"]
+    bundle = driver[driver.index("struct ChainArmed : Armed {"):]
+    bundle = bundle[:bundle.index("\n};")]
+    assert "if (!h) return;" in bundle and "= std::move(h->armed); h->armed = Armed();" in bundle and "for (int& v : h->rec_info) v = 0;" in bundle
+    dtor = re.search(r"~ChainArmed\(\) \{([^\n]*)\}", bundle).group(1)
+    assert dtor.startswith(" if (h) {") and sorted(re.findall(r"h->(\w+) = nullptr;", dtor)) == sorted(held)
+    assert re.search(r"struct Armed \{\s*RecSpec rec; DesignTables tables\[kNumDesignKinds\]; Known2D kn; Known1D kn1; Multistep ms;\s*\};", driver)
+    # what each entry serves
+    serves = {k: v["serves"] for k, v in entries.items()}
+    ddim = {k for k in serves if "_ddim" in k}
+    assert {k for k, v in serves.items() if "kServesMultistep" in v} == ddim and len(ddim) == 4
+    assert {k for k, v in serves.items() if "kServesTables" in v} == {"cindm_ddpm1d_sample_guided", "cindm_ddpm1d_sample_ddim_guided"}
+    assert {k for k, v in serves.items() if "kServesKnown2" in v} == {k for k in serves if k.startswith("cindm_ddpm2d_")}
+    assert {k for k, v in serves.items() if "kServesKnown1" in v} == {"cindm_ddpm1d_sample", "cindm_ddpm1d_sample_ddim", "cindm_ddpm1d_sample_guided",
+                                                                      "cindm_ddpm1d_sample_ddim_guided"}
+    for name, e in entries.items():          # a served thing is begun by the entry, an unserved one is not
+        body = e["body"]
+        assert ("guided_refuse(ch, took," in body) == ("kServesTables" in e["serves"]), name
+        assert ("known2_begin(took," in body) == ("kServesKnown2" in e["serves"]), name
+        assert ("known1_begin(took," in body) == ("kServesKnown1" in e["serves"]), name
+        assert (re.search(r"ms_begin2?\(took,", body) is not None) == ("kServesMultistep" in e["serves"]), name

@@ -48,15 +48,21 @@ def test_entry_is_declared_bound_and_exported():
 
 
 def test_every_chain_entry_takes_the_region():
-    """The ten chain entries take the armed region right after the scopes they had; four 1-D entries check it before their first
-    work and run it, the rollout, the Langevin chain and the 2-D entries refuse it with the reason."""
-    csrc = os.path.join(ROOT, "cindm_amd", "csrc")
-    one = open(os.path.join(csrc, "ddpm1d_host.inc")).read()
-    two = open(os.path.join(csrc, "ddpm2d_host.inc")).read()
-    assert one.count("    Known2DScope ks(h);\n    Known1DScope k1(h);\n") == 6
-    assert two.count("    Known2DScope ks(s);\n    Known1DScope k1(s);\n") == 4
-    assert len(re.findall(r"known1_begin\(k1, ch, x, [^;]*\) != 0\) return -1;\n    if \(chain_stream\(", one)) == 4
-    assert one.count("known1_refuse(k1, ") == 2 and two.count("known1_refuse(k1, ") == 4
+    """Every chain entry takes the armed region with everything else that is armed (test_host_logic.py states that rule); four 1-D
+    entries check it before their first work and run it, the rollout, the Langevin chain, the time composition and the 2-D entries
+    refuse it with the reason."""
+    from test_host_logic import chain_entries
+    entries = chain_entries()
+    one = {k: v for k, v in entries.items() if v["file"] == "ddpm1d_host.inc"}
+    two = {k: v for k, v in entries.items() if v["file"] == "ddpm2d_host.inc"}
+    assert len(one) == 6 and len(two) == 4
+    begin = re.compile(r"known1_begin\(took, ch, x, [^;]*\) != 0\) return -1;\n    if \(chain_stream\(")
+    assert sorted(k for k, v in entries.items() if begin.search(v["body"])) == sorted(k for k, v in one.items() if "kServesKnown1" in v["serves"])
+    assert sum("kServesKnown1" in v["serves"] for v in one.values()) == 4
+    # the others hand refuse_all_but their reason: two 1-D entries of that file, the time composition and the four 2-D entries
+    reason = lambda v: re.search(r"took\.refuse_all_but\([^,)]*, (\"|kKnown1Not2D\))", v["body"]) is not None
+    assert sum(reason(v) for v in one.values()) == 2 and sum(reason(v) for v in two.values()) == 4
+    assert all(reason(v) != ("kServesKnown1" in v["serves"]) for v in entries.values())
 
 
 def _case(seed):

@@ -48,14 +48,17 @@ def test_entry_is_declared_bound_and_exported():
 
 
 def test_every_chain_entry_takes_the_region():
-    """The four 2-D entries take the armed region as their second statement and check it before their first work; the six 1-D
-    entries take it too and refuse it."""
+    """Every chain entry takes the armed region with everything else that is armed (test_host_logic.py states that rule); the four 2-D
+    entries check it before their first work, the 1-D entries do not serve it: refuse_all_but refuses it for them."""
+    from test_host_logic import chain_entries
     csrc = os.path.join(ROOT, "cindm_amd", "csrc")
     two = open(os.path.join(csrc, "ddpm2d_host.inc")).read()
-    one = open(os.path.join(csrc, "ddpm1d_host.inc")).read()
-    assert two.count("    RecScope rs(s);\n    Known2DScope ks(s);\n") == 4
-    assert len(re.findall(r"known2_begin\(ks, ch, x, z\) != 0\) return -1;\n    if \(chain_stream\(", two)) == 4
-    assert one.count("    DesignTablesScope ts(h);\n    Known2DScope ks(h);\n") == 6 and one.count("known2_refuse(ks) != 0") == 6
+    entries = chain_entries()
+    begin = re.compile(r"known2_begin\(took, ch, x, z\) != 0\) return -1;\n    if \(chain_stream\(")
+    began = sorted(k for k, v in entries.items() if begin.search(v["body"]))
+    assert began == sorted(k for k, v in entries.items() if v["file"] == "ddpm2d_host.inc") and len(began) == 4
+    assert sum("kServesKnown2" not in v["serves"] for v in entries.values()) == 7
+    assert all(("kServesKnown2" in v["serves"]) == (k in began) for k, v in entries.items())
     assert two.count("known2_node(ch, x, 0)") == 2 and two.count("known2_node(ch, x, 1)") == 1
 
 
