@@ -36,6 +36,7 @@ enum { kWaypoint = 0, kQuadratic = 1, kPairDist = 2, kNumDesignKinds = 3 };
 struct DesignTables {
     int kind = 0; const float* a = nullptr; const float* b = nullptr; int a_per_design = 0, b_per_design = 0;
     int rows = 0, width = 0; int64_t batch = 0;
+    bool taken = false;      // set by design_begin: the running chain reads these tables
     bool on() const { return a != nullptr; }
 };
 
@@ -84,7 +85,9 @@ struct cindm_ddpm1d {
     hipGraph_t graph1 = nullptr; hipGraphExec_t gexec1 = nullptr;      // ping-pong loops: the one-step graph that ends an odd count
     Armed armed;                        // what the next chain call will take (the cindm_ddpm1d_set_* entries write it)
     int rec_info[4] = {0, 0, 0, 0};     // what the last chain recorded (cindm_ddpm1d_recorder_info)
-    // what the running chain holds of what it took (null: none): its recorder, the tables of its objective, its known region (2-D,
+    // what the running chain holds of what it took (null: none): its recorder, the tables of its objective (the bundle's slots, one per
+    // kind: the chain runs with those design_begin marked `taken` -- one kind under descriptor modes 3 - 6, every armed kind under
+    // mode 7), its known region (2-D,
     // 1-D), its multistep solver.  They point into the entry's ChainArmed, which clears them when the entry returns.
     const RecSpec* rec = nullptr; const DesignTables* dzt = nullptr; const Known2D* kn = nullptr; const Known1D* kn1 = nullptr;
     const Multistep* ms = nullptr;
@@ -299,7 +302,8 @@ extern "C" int cindm_ddpm1d_recorder_info(const cindm_ddpm1d* h, int32_t info[4]
 // ---- the table objectives: waypoint (DESIGN 4.5m), quadratic (4.5q), pair-distance (4.5s) ----------------------------------------------
 // cindm_ddpm1d_set_design_tables / _quadratic / _pairdist arm the handle, one slot per kind.  An entry either refuses the tables it
 // took (design_refuse, through refuse_all_but: every chain that is not guided) or checks them against its descriptor and state
-// (design_begin) and runs with the kind its descriptor's mode reads: run_step reads h->dzt for the whole call, the re-run included.
+// (design_begin) and runs with the kind its descriptor's mode reads -- mode 7, the sum, with every kind armed: run_step reads h->dzt
+// for the whole call, the re-run included.
 // What differs between the kinds is data: the modes that read them, how messages name the kind and its two tables, what `width`
 // counts, the alignment the update kernel needs and the ComposeArgs operands the tables become.
 struct DesignKind {
@@ -331,7 +335,10 @@ static const DesignKind kDesignKinds[kNumDesignKinds] = {
      "pair-distance tables of cindm_ddpm1d_set_design_pairdist", &ComposeArgs::dz_band, &ComposeArgs::dz_weight},
 };
 
-// the kind whose tables a descriptor mode reads, or -1 (the point objective's modes read none)
+// the descriptor mode that reads every armed kind: the sum of the table objectives (DESIGN 4.5t)
+constexpr int kDesignSumMode = 7;
+
+// the kind whose tables a descriptor mode reads, or -1 (the point objective's modes read none; the sum's mode reads every armed kind)
 static int design_kind_of(int mode) {
     for (int kind = 0; kind < kNumDesignKinds; ++kind)
         if (mode >= kDesignKinds[kind].mode_lo && mode <= kDesignKinds[kind].mode_hi) return kind;
@@ -347,21 +354,28 @@ static int design_refuse(const ChainArmed& took) {
     return 0;
 }
 
-// For each kind: when it serves dz->mode it must be armed and fit the state, otherwise it must not be armed.
+// For each kind: when it serves dz->mode it must be armed and fit the state, otherwise it must not be armed.  Mode 7 (the sum, DESIGN
+// 4.5t) is served by every kind: each armed one must fit the state, by that kind's own messages, and at least one must be armed; its
+// last_n_step names the waypoint term's norm (1 = L2, 2 = L2square) and is read only when waypoint tables are armed.
 // x, x2: the state buffers the guided update reads a row of as float4 (x2: the guided DDIM chain's second buffer, or null)
 static int design_begin(ChainArmed& took, const cindm_design_desc* dz, int Ltot, int n_bodies, int64_t B, const float* x, const float* x2) {
     for (int kind = 0; kind < kNumDesignKinds; ++kind) {
-        const DesignKind& k = kDesignKinds[kind]; const DesignTables& t = took.tables[kind];
+        const DesignKind& k = kDesignKinds[kind]; DesignTables& t = took.tables[kind];
         const std::string label = k.label;
-        if (design_kind_of(dz->mode) != kind) {
+        if (dz->mode == kDesignSumMode) {
+            if (!t.on()) continue;
+            if (kind == kWaypoint && dz->last_n_step != 1 && dz->last_n_step != 2)
+                return fail("design objective mode 7 with design tables armed: last_n_step names the waypoint term's norm, 1 (L2) or 2 (L2square), not " +
+                            std::to_string(dz->last_n_step) + "; the tables were dropped");
+        } else if (design_kind_of(dz->mode) != kind) {
             if (!t.on()) continue;
             if (dz->mode > k.mode_hi)
                 return fail(std::string(k.armed_as) + " are armed but the descriptor's mode is " + std::to_string(dz->mode) + ", which reads the " +
                             kDesignKinds[design_kind_of(dz->mode)].tables_of + "; the tables were dropped");
             return fail(label + " are armed but the descriptor's mode is " + k.lower_modes + "; the tables were dropped");
-        }
-        if (!t.on())
+        } else if (!t.on()) {
             return fail(std::string("design objective mode ") + k.modes + " reads " + k.reads + " from tables: arm them with " + k.setter + " before the chain call");
+        }
         if (t.rows != Ltot)
             return fail(label + ": " + std::to_string(t.rows) + " rows, the state has " + std::to_string(Ltot));
         if (t.width != k.per_body * n_bodies)
@@ -372,13 +386,23 @@ static int design_begin(ChainArmed& took, const cindm_design_desc* dz, int Ltot,
             return fail(label + ": " + k.a_name + " and " + k.b_name + " must be " + std::to_string(k.align) + "-byte aligned");
         if (kind == kQuadratic)
             REQUIRE((((uintptr_t)x | (uintptr_t)x2) & 15) == 0, "quadratic design tables: the state x must be 16-byte aligned (the update reads its rows 16 bytes at a time)");
-        took.h->dzt = &t;
+        t.taken = true;
+        took.h->dzt = took.tables;
+    }
+    if (dz->mode == kDesignSumMode) {
+        bool any = false;
+        for (const DesignTables& t : took.tables) any = any || t.taken;
+        REQUIRE(any, "design objective mode 7 sums the table objectives armed on the handle: arm at least one with cindm_ddpm1d_set_design_tables, "
+                     "_set_design_quadratic or _set_design_pairdist before the chain call");
     }
     return 0;
 }
 
 static void design_key(KeyBuilder& K, const cindm_ddpm1d* h) {
-    if (h->dzt) K(h->dzt->a)(h->dzt->b)(h->dzt->a_per_design)(h->dzt->b_per_design);
+    for (int kind = 0; h->dzt && kind < kNumDesignKinds; ++kind) {
+        const DesignTables& t = h->dzt[kind];
+        if (t.taken) K(kind)(t.a)(t.b)(t.a_per_design)(t.b_per_design);
+    }
 }
 
 // what the three setters share; width_ok: the setter's own rule for the width

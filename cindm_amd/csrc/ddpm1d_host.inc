@@ -290,11 +290,29 @@ static int run_step(const Chain1D& ch, const StepIO& io, int32_t t, const int32_
         if (io.pingpong) { a.step_idx = h->t_dev + 4 * q + 2; a.sidx_next = h->t_dev + 4 * (1 - q) + 2; }      // the slot's own step index
     }
     const bool guided = io.dz && io.x_out;
+    DesignSum dsum; std::memset(&dsum, 0, sizeof(dsum));      // (read under dz_mode 7 only)
     if (guided) {
         a.dz_mode = io.dz->mode; a.dz_alpha = io.dz->alpha; a.dz_tc = io.dz->time_consistency_coef;
         const int kind = design_kind_of(io.dz->mode);
-        if (kind >= 0) {     // table objective: the addresses and the per-design flags are operands of the captured update
-            const DesignKind& k = kDesignKinds[kind]; const DesignTables* t = h->dzt;
+        if (io.dz->mode == kDesignSumMode) {     // the sum: every kind the chain took, in the update's second argument
+            auto taken = [&](int k) -> const DesignTables* { return (h->dzt && h->dzt[k].taken) ? &h->dzt[k] : nullptr; };
+            const DesignTables* w = taken(kWaypoint); const DesignTables* qd = taken(kQuadratic); const DesignTables* pd = taken(kPairDist);
+            if (!w && !qd && !pd) return fail("design objective mode 7 outside a chain that took design tables (internal error)");
+            if (w) {
+                dsum.way_target = w->a; dsum.way_scale = w->b;
+                dsum.flags |= kSumWay | (w->a_per_design ? kSumWayTargetPerDesign : 0) | (w->b_per_design ? kSumWayScalePerDesign : 0) |
+                              (io.dz->last_n_step == 1 ? kSumWayL2 : 0);
+            }
+            if (qd) {
+                dsum.quad_S = qd->a; dsum.quad_h = qd->b;
+                dsum.flags |= kSumQuad | (qd->a_per_design ? kSumQuadSPerDesign : 0) | (qd->b_per_design ? kSumQuadHPerDesign : 0);
+            }
+            if (pd) {
+                dsum.pair_band = pd->a; dsum.pair_weight = pd->b;
+                dsum.flags |= kSumPair | (pd->a_per_design ? kSumPairBandPerDesign : 0) | (pd->b_per_design ? kSumPairWeightPerDesign : 0);
+            }
+        } else if (kind >= 0) {     // table objective: the addresses and the per-design flags are operands of the captured update
+            const DesignKind& k = kDesignKinds[kind]; const DesignTables* t = (h->dzt && h->dzt[kind].taken) ? &h->dzt[kind] : nullptr;
             if (!t || t->kind != kind)
                 return fail(std::string("design objective mode ") + k.modes + " outside a chain that took " + k.label + " (internal error)");
             a.*k.arg_a = t->a; a.*k.arg_b = t->b;
@@ -360,9 +378,12 @@ static int run_step(const Chain1D& ch, const StepIO& io, int32_t t, const int32_
         launch_compose_update_clamped(a, io.ms_hist, ne, stream);
     } else if (io.ms_hist && io.ddim_tab && !(guided && io.relax)) {
         // the multistep solver's update (never fused; a relaxation iteration is not an update and keeps the kernels below)
-        if ((a.dz_mode & kDzModeMask) == 6) launch_compose_update_pair(a, io.ms_hist, ne, stream);
+        if ((a.dz_mode & kDzModeMask) == kDesignSumMode) launch_compose_update_sum(a, dsum, io.ms_hist, ne, stream);
+        else if ((a.dz_mode & kDzModeMask) == 6) launch_compose_update_pair(a, io.ms_hist, ne, stream);
         else if ((a.dz_mode & kDzModeMask) == 5) hipLaunchKernelGGL(compose_update_ms_quad_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a, io.ms_hist);
         else hipLaunchKernelGGL(compose_update_ms_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a, io.ms_hist);
+    } else if ((a.dz_mode & kDzModeMask) == kDesignSumMode) {      // (guided: never fused)
+        launch_compose_update_sum(a, dsum, nullptr, ne, stream);
     } else if ((a.dz_mode & kDzModeMask) == 6) {      // (guided: never fused)
         launch_compose_update_pair(a, nullptr, ne, stream);
     } else if ((a.dz_mode & kDzModeMask) == 5) {      // (guided: never fused)
@@ -440,7 +461,7 @@ static int chain1_refuse(const Chain1D& ch, const float* x, const float* cond, c
 static int guided_refuse(const Chain1D& ch, ChainArmed& took, const cindm_design_desc* dz, const float* x, int min_recurrence,
                          const float* initial_state_overwrite, int overwrite_steps) {
     REQUIRE(dz, "null argument");
-    REQUIRE(dz->mode >= 1 && dz->mode <= 6, "design objective mode must be 1 (L2), 2 (L2square), 3 (table L2), 4 (table L2square), 5 (quadratic tables) or 6 (pair-distance tables)");
+    REQUIRE(dz->mode >= 1 && dz->mode <= 7, "design objective mode must be 1 (L2), 2 (L2square), 3 (table L2), 4 (table L2square), 5 (quadratic tables), 6 (pair-distance tables) or 7 (the sum of the tables armed)");
     if (min_recurrence == 0) REQUIRE(dz->recurrence >= 0 && dz->recurrence <= 64, "recurrence count out of range");
     else REQUIRE(dz->recurrence >= 1 && dz->recurrence <= 64,
                  "guided DDIM needs a recurrence count in 1 .. 64 (without recurrence the reference returns no noise prediction)");

@@ -2574,7 +2574,7 @@ struct ComposeArgs {
     // and the same two per-design bits; its gradient is compiled into compose_update_quad_kernel only.
     // The pair-distance objective (mode 6) reads band [B | 1, Ltot, P, 2] = (lo, hi) and weight [B | 1, Ltot, P], P = nb (nb - 1) / 2 in
     // pair_index order, likewise; its gradient is compiled into compose_update_pair_kernel only.
-    int dz_mode;                 // 0 off; bits 0-2: 1 "L2", 2 "L2square" (point), 3 "L2", 4 "L2square" (tables), 5 quadratic (tables), 6 pair distance (tables); kDzTargetPerDesign, kDzScalePerDesign
+    int dz_mode;                 // 0 off; bits 0-2: 1 "L2", 2 "L2square" (point), 3 "L2", 4 "L2square" (tables), 5 quadratic (tables), 6 pair distance (tables), 7 their sum (DesignSum: the union and the two bits below are not read); kDzTargetPerDesign, kDzScalePerDesign
     int dz_alpha;                // 1: scale the gradient by eta_t = beta_t / sqrt(alphas_cumprod_prev_t) (standard-alpha)
     union {
         struct { int dz_last_n; float dz_coef, dz_tx, dz_ty; };              // modes 1, 2
@@ -2596,6 +2596,18 @@ struct ComposeArgs {
 };
 constexpr int kDzModeMask = 7, kDzTargetPerDesign = 0x100, kDzScalePerDesign = 0x200;
 static_assert(offsetof(ComposeArgs, recur_noise) - offsetof(ComposeArgs, dz_mode) == 32, "the design objective's fields must not grow ComposeArgs");
+// The sum of the table objectives (dz_mode 7): the six table addresses do not fit the union's two words, so they travel in a
+// second by-value argument of compose_update_sum_kernel (kernels_tail.h), as hist does for the multistep kernels.  flags: per kind its
+// present bit and its two per-design bits, and the waypoint term's norm.  The addresses of an absent kind are null and never read.
+struct DesignSum {
+    const float* way_target; const float* way_scale;      // [B | 1, Ltot, nb, 2] and [B | 1, Ltot, nb]
+    const float* quad_S; const float* quad_h;             // [B | 1, Ltot, F, F] and [B | 1, Ltot, F]
+    const float* pair_band; const float* pair_weight;     // [B | 1, Ltot, P, 2] and [B | 1, Ltot, P]
+    int flags;
+};
+constexpr int kSumQuad = 0x1, kSumQuadSPerDesign = 0x2, kSumQuadHPerDesign = 0x4,
+              kSumWay = 0x10, kSumWayTargetPerDesign = 0x20, kSumWayScalePerDesign = 0x40, kSumWayL2 = 0x80,
+              kSumPair = 0x100, kSumPairBandPerDesign = 0x200, kSumPairWeightPerDesign = 0x400;
 __device__ __forceinline__ void compose_advance(const ComposeArgs& a, int t) {
     if (!a.t_next) return;
     if (a.ddim_tab && a.relax) { a.t_next[0] = t; a.sidx_next[0] = a.step_idx[0]; }      // guided DDIM: a relaxation iteration stays on its step
@@ -3573,9 +3585,11 @@ __global__ void compose_gather_kernel(const ComposeArgs a) {
 // model_predictions (:1755), which re-derives pred_noise from the CLAMPED x_start (:1018-1027); eps of the branches below is
 // p_mean_variance's, from the unclamped one (the guided chain's DDIM return and every predict caller keep it).  An instantiation of
 // its own (compose_update_clamped_kernel in kernels_tail.h), so that the other kernels are the code they were.
-constexpr int kObjPosition = 0, kObjQuad = 1, kObjPair = 2;
+// kObjSum: the sum of the table objectives armed (dz_mode 7); `sum` holds their tables and is read by this instantiation
+// only (compose_update_sum_kernel in kernels_tail.h).
+constexpr int kObjPosition = 0, kObjQuad = 1, kObjPair = 2, kObjSum = 3;
 template <int kObj, bool kMulti = false, bool kClampedEps = false>
-__device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_t i, float* hist = nullptr) {
+__device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_t i, float* hist = nullptr, const DesignSum* sum = nullptr) {
     const int Lfull = a.Ltot + a.cond_steps;
     const int t = step_scalar(a.t_ptr, a.t_imm);
     const int sidx = a.ddim_tab ? *a.step_idx : 0;
@@ -3699,9 +3713,72 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
             }
             g = __fsub_rn(acc, a.dz_h[(bh * a.Ltot + lx) * a.F + f]);
         }
+        if constexpr (kObj == kObjSum) {
+            // the sum of the armed table objectives: each present term exactly as its own instantiation evaluates it (the kObjQuad
+            // expression above, the table branch and the kObjPair accumulation below), then g = the first present term's value and
+            // g = g + next, rounded once each, in the order quadratic, waypoint, pair-distance.  An absent kind contributes no
+            // operation; velocity components see the quadratic term only.  Table indices are bounded as in the three originals, by
+            // design_begin's rows == Ltot, width and batch == B checks of every kind taken.
+            const int fl = sum->flags;
+            bool have = false;
+            if (fl & kSumQuad) {
+                const int64_t bS = (fl & kSumQuadSPerDesign) ? b : 0, bh = (fl & kSumQuadHPerDesign) ? b : 0;
+                const int64_t srow = (bS * a.Ltot + lx) * a.F + f;
+                const float4* sp = reinterpret_cast<const float4*>(sum->quad_S + srow * a.F);
+                const float4* xp = reinterpret_cast<const float4*>(a.x + (i - f));
+                float acc = 0.f;
+                for (int k = 0; k < (a.F >> 2); ++k) {
+                    const float4 sv = sp[k], xq = xp[k];
+                    acc = __fadd_rn(acc, __fmul_rn(sv.x, xq.x)); acc = __fadd_rn(acc, __fmul_rn(sv.y, xq.y));
+                    acc = __fadd_rn(acc, __fmul_rn(sv.z, xq.z)); acc = __fadd_rn(acc, __fmul_rn(sv.w, xq.w));
+                }
+                g = __fsub_rn(acc, sum->quad_h[(bh * a.Ltot + lx) * a.F + f]);
+                have = true;
+            }
+            if (comp < 2 && (fl & kSumWay)) {
+                const int64_t bs = (fl & kSumWayScalePerDesign) ? b : 0, bt = (fl & kSumWayTargetPerDesign) ? b : 0;
+                const float s = sum->way_scale[(bs * a.Ltot + lx) * a.nb + body];
+                float gw = 0.f;
+                if (s != 0.f) {
+                    const float* tp = sum->way_target + ((bt * a.Ltot + lx) * a.nb + body) * 2;
+                    const float d = xv - tp[comp];
+                    if (fl & kSumWayL2) {
+                        const float dother = a.x[i ^ 1] - tp[comp ^ 1];
+                        gw = s * d / sqrtf(d * d + dother * dother);
+                    } else {
+                        gw = s * 2.0f * d;
+                    }
+                }
+                g = have ? __fadd_rn(g, gw) : gw;
+                have = true;
+            }
+            if (comp < 2 && (fl & kSumPair)) {
+                const int64_t bb = (fl & kSumPairBandPerDesign) ? b : 0, bw = (fl & kSumPairWeightPerDesign) ? b : 0;
+                const float* xr = a.x + (i - f);
+                const float* wp = sum->pair_weight + (bw * a.Ltot + lx) * P;
+                const float* bp = sum->pair_band + (bb * a.Ltot + lx) * P * 2;
+                const float xw = a.x[i ^ 1];
+                float gp = 0.f;
+                for (int o = 0; o < a.nb; ++o) {
+                    if (o == body) continue;
+                    const int p = pair_index(min(body, o), max(body, o), a.nb);
+                    const float w = wp[p];
+                    float term = 0.f;
+                    if (w != 0.f) {
+                        const float lo = bp[2 * p], hi = bp[2 * p + 1];
+                        const float d = __fsub_rn(xv, xr[4 * o + comp]), dw = __fsub_rn(xw, xr[4 * o + (comp ^ 1)]);
+                        const float r = sqrtf(__fadd_rn(__fmul_rn(d, d), __fmul_rn(dw, dw)));
+                        if (r != 0.f && (r < lo || r > hi))
+                            term = __fmul_rn(__fmul_rn(__fmul_rn(w, 2.0f), __fsub_rn(r, r < lo ? lo : hi)), d) / r;
+                    }
+                    gp = __fadd_rn(gp, term);
+                }
+                g = have ? __fadd_rn(g, gp) : gp;
+            }
+        }
         if (comp < 2) {
-            if constexpr (kObj == kObjQuad) {
-                // (the position objectives of modes 1 - 4 are not part of this instantiation; the time-consistency term below is)
+            if constexpr (kObj == kObjQuad || kObj == kObjSum) {
+                // (the position objectives of modes 1 - 4 are not part of these instantiations; the time-consistency term below is)
             } else if constexpr (kObj == kObjPair) {
                 // pair-distance objective: g = sum over the other bodies o, ascending, from 0.f, of the pair {body, o}'s term
                 //   w * 2 * (r - lo) * d / r  where r < lo,   w * 2 * (r - hi) * d / r  where r > hi,   0.f otherwise and where w == 0 or r == 0,
@@ -3867,6 +3944,9 @@ __global__ void compose_update_quad_kernel(const ComposeArgs a) {
 // unit includes that file last and the kernel is a template first used there, so the code object holds the two behind every kernel
 // that exists and those keep their places in it (4.5r has what moving them may cost).  hist: null for the guided update.
 void launch_compose_update_pair(const ComposeArgs& a, float* hist, int64_t n_elements, hipStream_t stream);
+// the guided update with the sum of the armed table objectives (dz_mode 7) and its DDIM update under the multistep solver: likewise,
+// compose_update_sum_kernel<kMulti> in kernels_tail.h
+void launch_compose_update_sum(const ComposeArgs& a, const DesignSum& sum, float* hist, int64_t n_elements, hipStream_t stream);
 // the unguided DDIM update with pred_noise re-derived from the clamped x_start (kClampedEps), with or without the multistep term: likewise
 void launch_compose_update_clamped(const ComposeArgs& a, float* hist, int64_t n_elements, hipStream_t stream);
 

@@ -33,4 +33,17 @@ void launch_compose_update_clamped(const ComposeArgs& a, float* hist, int64_t n_
     else hipLaunchKernelGGL(compose_update_clamped_kernel<false>, grid, dim3(256), 0, stream, a, (float*)nullptr);
 }
 
+// the guided update with the sum of the armed table objectives (dz_mode 7; kMulti: its DDIM update under the multistep
+// solver): compose_update_body's kObjSum.  The tables' addresses and flags are the second by-value argument; never fused
+template <bool kMulti>
+__global__ void compose_update_sum_kernel(const ComposeArgs a, const DesignSum s, float* hist) {
+    compose_update_body<kObjSum, kMulti>(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, hist, &s);
+}
+
+void launch_compose_update_sum(const ComposeArgs& a, const DesignSum& sum, float* hist, int64_t n_elements, hipStream_t stream) {
+    const dim3 grid((unsigned)((n_elements + 255) / 256));
+    if (hist) hipLaunchKernelGGL(compose_update_sum_kernel<true>, grid, dim3(256), 0, stream, a, sum, hist);
+    else hipLaunchKernelGGL(compose_update_sum_kernel<false>, grid, dim3(256), 0, stream, a, sum, (float*)nullptr);
+}
+
 }  // namespace cindm

@@ -33,7 +33,7 @@ from torch import nn
 
 from . import _ffi
 from .diffusion_base import DiffusionHandle
-from .objectives import PointObjective, _TableObjective
+from .objectives import PointObjective, SumObjective, _TableObjective
 from .record import DeviceRecorder, LoopRecorder, record_schedule, stream_mask
 from .schedule import check_solver, make_schedule, ula_schedule
 
@@ -274,7 +274,7 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
 
     @staticmethod
     def _arm_tables(obj, h, img):
-        """A WaypointObjective's, QuadraticObjective's or PairDistanceObjective's tables, armed like the recorder: the guided chain call consumes them, so every
+        """A WaypointObjective's, QuadraticObjective's, PairDistanceObjective's or SumObjective's tables, armed like the recorder: the guided chain call consumes them, so every
         issue arms again."""
         if obj is not None:
             obj.arm(h, img.shape[0], img.device)
@@ -282,9 +282,9 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
     @staticmethod
     def _builtin(design_fn, design_guidance, B, L, n_bodies):
         """(descriptor, tables) when ``design_fn`` under ``design_guidance`` runs inside the captured step -- a PointObjective whose
-        last_n_step fits the state, a WaypointObjective, a QuadraticObjective or a PairDistanceObjective -- else (None, None).  A table objective whose tables
+        last_n_step fits the state, a WaypointObjective, a QuadraticObjective, a PairDistanceObjective or a SumObjective of these -- else (None, None).  A table objective whose tables
         do not fit the state [B, L, 4 * n_bodies] is a ValueError on every route, before any device work."""
-        if isinstance(design_fn, _TableObjective):
+        if isinstance(design_fn, (_TableObjective, SumObjective)):
             design_fn.check_state(B, L, n_bodies)
             dz = design_fn.descriptor(design_guidance)
             return dz, (design_fn if dz is not None else None)

@@ -25,8 +25,14 @@ two library chains (``cindm_ddpm1d_set_design_quadratic``, descriptor mode 5: th
 ``PairDistanceObjective`` states a relation between the positions of two bodies that is not quadratic: a band ``[lo, hi]`` for the
 distance of every (design | all designs, row, pair) with a weight, penalised quadratically outside the band.  "Stay at least d apart"
 (``apart``), "come within d" (``within``) and "meet at distance d" (``at``) are such bands and mix freely in one table; the first and
-the last are non-convex.  It takes the same two library chains (``cindm_ddpm1d_set_design_pairdist``, descriptor mode 6)."""
+the last are non-convex.  It takes the same two library chains (``cindm_ddpm1d_set_design_pairdist``, descriptor mode 6).
+
+``SumObjective`` is the conjunction of these: at most one waypoint (or point), one quadratic and one pair-distance objective, added.
+``a + b`` builds it and ``w * a`` folds a weight into a term's tables.  It takes the same two library chains with every term's tables
+armed at once (descriptor mode 7: the guided update evaluates each term as its own kernel does and adds them in the order quadratic,
+waypoint, pair-distance)."""
 import copy
+import math
 
 import torch
 
@@ -50,7 +56,47 @@ def _parse_guidance(design_guidance):
     return int(g == "standard-alpha"), rec
 
 
-class PointObjective:
+def _check_multiple(w, cls, any_sign=False):
+    """fp32(w) of a scalar multiple ``w * objective``: finite, and >= 0 unless the objective's tables may carry either sign."""
+    if isinstance(w, bool) or not isinstance(w, (int, float)):
+        raise TypeError(f"{cls}: a scalar multiple is a real number, not {type(w).__name__}")
+    if not math.isfinite(w) or (w < 0 and not any_sign):
+        raise ValueError(f"{cls}: the multiple must be finite" + ("" if any_sign else " and >= 0 (its weights are >= 0 by contract)") + f", not {w}")
+    return torch.tensor(float(w), dtype=torch.float32)
+
+
+def _scaled_table(w32, table, cls, name):
+    out = w32 * table          # (one fp32 product per entry)
+    if not bool(torch.isfinite(out).all()):
+        raise ValueError(f"{cls}: the multiple overflows {name}")
+    return out.contiguous()
+
+
+class _Summable:
+    """``a + b`` of two built-in objectives is their SumObjective; ``w * a`` is ``a`` with w folded into its tables (``_scaled``)."""
+
+    def __add__(self, other):
+        return SumObjective(self, other)
+
+    def __radd__(self, other):
+        return SumObjective(other, self)
+
+    def __mul__(self, w):
+        return self._scaled(w)
+
+    __rmul__ = __mul__
+
+
+class PointObjective(_Summable):
+    def _scaled(self, w):
+        w32 = _check_multiple(w, "PointObjective")
+        o = copy.copy(self)
+        o.coef = float(w32 * torch.tensor(self.coef, dtype=torch.float32))
+        if not math.isfinite(o.coef):
+            raise ValueError("PointObjective: the multiple overflows coef")
+        o.time_consistency_coef = float(w) * self.time_consistency_coef
+        return o
+
     def __init__(self, pos_target, last_n_step, gamma=2, coef=100, time_consistency_coef=0, design_fn_mode="L2"):
         pos_target = torch.as_tensor(pos_target, dtype=torch.float32).reshape(-1)
         assert pos_target.numel() == 2, "pos_target is a 2-D position"
@@ -92,12 +138,32 @@ class PointObjective:
         return d
 
 
-class _TableObjective:
+class _TableObjective(_Summable):
     """What the table objectives share.  A subclass declares ``_TABLES``, its table attributes with the rank each has when it is
     shared by every design (one more: per design); ``_WIDTH``, the attribute that counts what a row of its tables holds, the noun
     for it and how many a body has; ``_SETTER``, the library entry that arms its two device tables; ``mode``, its descriptor mode.
     ``rows`` and the width attribute are the subclass's own."""
     _TABLES, _WIDTH, _SETTER = (), ("n_bodies", "bodies", 1), ""
+    _SCALED, _ANY_SIGN = (), False          # the tables a scalar multiple scales; whether it may be negative
+
+    def _scaled(self, w):
+        """``w * self``: a copy with fp32(w) folded into the ``_SCALED`` tables (one fp32 product per entry) and w into the
+        time-consistency coefficient.  The kernels have no per-term weight."""
+        cls = type(self).__name__
+        w32 = _check_multiple(w, cls, self._ANY_SIGN)
+        if w < 0 and self.time_consistency_coef != 0:
+            raise ValueError(f"{cls}: a negative multiple of an objective with a time-consistency term (the kernels apply that term for a coefficient > 0 only)")
+        o = copy.copy(self)
+        for name in self._SCALED:
+            setattr(o, name, _scaled_table(w32, getattr(self, name), cls, name))
+        o.time_consistency_coef = float(w) * self.time_consistency_coef
+        o._dev = {}
+        return o
+
+    def _without_time_consistency(self):
+        o = copy.copy(self)
+        o.time_consistency_coef = 0.0
+        return o
 
     @property
     def per_design(self):
@@ -225,7 +291,7 @@ class WaypointObjective(_TableObjective):
         return cls(pt.expand(L, nb, 2), None, time_consistency_coef=time_consistency_coef, design_fn_mode=design_fn_mode, _scale=scale)
 
     # ------------------------------------------------------------------ shapes
-    _TABLES, _SETTER = (("target", 3), ("scale", 2)), "cindm_ddpm1d_set_design_tables"
+    _TABLES, _SETTER, _SCALED = (("target", 3), ("scale", 2)), "cindm_ddpm1d_set_design_tables", ("scale",)
 
     @property
     def mode(self):
@@ -349,6 +415,7 @@ class QuadraticObjective(_TableObjective):
 
     # ------------------------------------------------------------------ shapes
     _TABLES, _WIDTH, _SETTER, mode = (("S", 3), ("h", 2)), ("features", "features", 4), "cindm_ddpm1d_set_design_quadratic", 5
+    _SCALED, _ANY_SIGN = ("S", "h"), True
 
     @property
     def rows(self):
@@ -463,6 +530,7 @@ class PairDistanceObjective(_TableObjective):
 
     # ------------------------------------------------------------------ shapes
     _TABLES, _SETTER, mode = (("lo", 2), ("hi", 2), ("weight", 2)), "cindm_ddpm1d_set_design_pairdist", 6
+    _SCALED = ("weight",)
 
     @property
     def rows(self):
@@ -541,3 +609,156 @@ class PairDistanceObjective(_TableObjective):
         out = torch.zeros_like(pos).reshape(B, L, nb, 4)
         out[..., :2] = g
         return out.reshape(B, L, F)
+
+
+_SUM_KINDS = ("quadratic", "waypoint", "pair-distance")          # the order the kernel adds the terms in
+
+
+def _sum_kind(term):
+    if isinstance(term, QuadraticObjective):
+        return "quadratic"
+    if isinstance(term, (WaypointObjective, PointObjective)):
+        return "waypoint"
+    if isinstance(term, PairDistanceObjective):
+        return "pair-distance"
+    raise TypeError(f"SumObjective: a term is a WaypointObjective, QuadraticObjective, PairDistanceObjective or PointObjective, not {type(term).__name__}")
+
+
+class SumObjective:
+    """The sum of built-in objectives: at most one term of each kind -- quadratic, waypoint (a ``PointObjective`` counts as its table
+    form, ``WaypointObjective.from_point``, made once the state's (L, n_bodies) are known), pair-distance.  ``a + b`` builds it and adding
+    a further term flattens; two terms of a kind are refused (merging tables would change roundings: merge them yourself).  There is no
+    per-term weight in the kernel: ``w * term`` folds one into the term's tables.
+
+    The value is the sum of the terms' values in the order quadratic, waypoint, pair-distance; the time-consistency coefficient is the
+    sum of the terms' and the kernel applies that term once.  The library's guided chains run it with every term's tables armed
+    (descriptor mode 7, compose_update_sum_kernel); a sum of one term is that term, bit for bit."""
+
+    def __init__(self, *terms):
+        flat = []
+        for t in terms:
+            flat.extend(t.terms if isinstance(t, SumObjective) else (t,))
+        if not flat:
+            raise ValueError("SumObjective: no terms")
+        by_kind = {}
+        for t in flat:
+            kind = _sum_kind(t)
+            if kind in by_kind:
+                raise ValueError(f"SumObjective: two {kind} terms ({type(by_kind[kind]).__name__} and {type(t).__name__}); a sum holds at most one "
+                                 "term of a kind and does not merge tables")
+            by_kind[kind] = t
+        self.terms = tuple(by_kind[k] for k in _SUM_KINDS if k in by_kind)          # kernel order, whatever the operand order
+        self._agree()
+        self._tabled, self._last = {}, None
+
+    def _agree(self):
+        """ValueError unless the table terms agree on (L, n_bodies) and on the per-design extent."""
+        shapes = {(t.rows, getattr(t, t._WIDTH[0]) // t._WIDTH[2]) for t in self.terms if isinstance(t, _TableObjective)}
+        if len(shapes) > 1:
+            raise ValueError(f"SumObjective: the terms disagree on (L, n_bodies): {sorted(shapes)}")
+        extents = {t.per_design for t in self.terms if isinstance(t, _TableObjective) and t.per_design is not None}
+        if len(extents) > 1:
+            raise ValueError(f"SumObjective: the terms' per-design tables are for different numbers of designs: {sorted(extents)}")
+
+    # ------------------------------------------------------------------ algebra
+    def __add__(self, other):
+        return SumObjective(self, other)
+
+    def __radd__(self, other):
+        return SumObjective(other, self)
+
+    def __mul__(self, w):
+        return SumObjective(*(t * w for t in self.terms))
+
+    __rmul__ = __mul__
+
+    # ------------------------------------------------------------------ shapes
+    @property
+    def time_consistency_coef(self):
+        return float(sum(float(t.time_consistency_coef) for t in self.terms))
+
+    @property
+    def per_design(self):
+        """Designs the terms' per-design tables are for, or None when every table is shared by every design."""
+        for t in self.terms:
+            if isinstance(t, _TableObjective) and t.per_design is not None:
+                return t.per_design
+        return None
+
+    def table_terms(self, L, n_bodies):
+        """The terms as table objectives on a state of ``L`` rows and ``n_bodies`` bodies, in kernel order: a PointObjective term becomes
+        ``WaypointObjective.from_point`` (cached per (L, n_bodies), so its device tables are made once)."""
+        key = (int(L), int(n_bodies))
+        if key not in self._tabled:
+            self._tabled[key] = tuple(
+                WaypointObjective.from_point(t.pos_target, t.last_n_step, L, n_bodies, coef=t.coef, time_consistency_coef=t.time_consistency_coef,
+                                             design_fn_mode=t.design_fn_mode) if isinstance(t, PointObjective) else t
+                for t in self.terms)
+        return self._tabled[key]
+
+    def check_state(self, B, L, n_bodies):
+        """ValueError unless every term fits a state [B, L, 4 * n_bodies] (each term's own check) and the terms' per-design extents agree."""
+        self._agree()
+        for t in self.table_terms(L, n_bodies):
+            t.check_state(B, L, n_bodies)
+        self._last = (int(L), int(n_bodies))
+
+    def shard(self, lo, hi):
+        """The objective of designs lo .. hi-1: every term sharded (a PointObjective term has nothing per design)."""
+        return type(self)(*(t.shard(lo, hi) if isinstance(t, _TableObjective) else t for t in self.terms))
+
+    # ------------------------------------------------------------------ value and gradient
+    def __call__(self, pos):
+        """pos: [B, L, n_bodies*4] -> scalar loss (summed over the batch): the terms' values added in kernel order."""
+        B, L, F = pos.shape
+        self.check_state(B, L, F // 4)
+        total = None
+        for t in self.table_terms(L, F // 4):
+            v = t(pos)
+            total = v if total is None else total + v
+        return total
+
+    def closed_form_grad(self, pos):
+        """The gradient of ``__call__`` as compose_update_sum_kernel evaluates it, operation for operation, in the dtype of ``pos``:
+        each term's ``closed_form_grad`` without its time-consistency term; g = the first term's, then g = g + the next (rounded once) in
+        the order quadratic, waypoint, pair-distance -- on the position features, the velocity features see the quadratic term only --
+        and last, on the position features, g = g + ((tc * 2) * lap) / (L - 1) once with tc the sum of the terms' coefficients."""
+        B, L, F = pos.shape
+        nb = F // 4
+        self.check_state(B, L, nb)
+        g, have = torch.zeros_like(pos).reshape(B, L, nb, 4), False
+        for t in self.table_terms(L, nb):
+            gt = t._without_time_consistency().closed_form_grad(pos).reshape(B, L, nb, 4)
+            if isinstance(t, QuadraticObjective):
+                g = gt.clone()
+            elif have:
+                g[..., :2] = g[..., :2] + gt[..., :2]
+            else:
+                g[..., :2] = gt[..., :2]
+            have = True
+        if self.time_consistency_coef > 0 and L > 1:
+            g[..., :2] = g[..., :2] + _TableObjective._time_consistency_grad(self, pos.reshape(B, L, nb, 4)[..., :2])
+        return g.reshape(B, L, F)
+
+    # ------------------------------------------------------------------ the library's guided chains
+    def descriptor(self, design_guidance):
+        """cindm_design_desc (mode 7; the tables are armed per call) under ``design_guidance``, or None when that guidance needs the
+        generic (autograd) path.  In mode 7 ``last_n_step`` names the waypoint term's norm: 1 = L2, 2 = L2square, 0 without one."""
+        parsed = _parse_guidance(design_guidance)
+        if parsed is None:
+            return None
+        d = _ffi.DesignDesc()
+        d.mode = 7
+        d.alpha, d.recurrence = parsed
+        way = [t for t in self.terms if _sum_kind(t) == "waypoint"]
+        d.last_n_step = (1 if way[0].design_fn_mode == "L2" else 2) if way else 0
+        d.time_consistency_coef = self.time_consistency_coef
+        return d
+
+    def arm(self, handle, B, device):
+        """Arms the next guided chain call on ``handle`` with every term's tables, for the state ``check_state`` last saw."""
+        terms = self.terms if self._last is None else self.table_terms(*self._last)
+        if any(isinstance(t, PointObjective) for t in terms):
+            raise RuntimeError("SumObjective.arm before check_state: a PointObjective term needs the state's (L, n_bodies)")
+        for t in terms:
+            t.arm(handle, B, device)

@@ -275,9 +275,15 @@ int  cindm_ddpm1d_sample(cindm_ddpm1d* h, cindm_unet1d* pair, cindm_unet1d* unco
  * Mode 6 is the pair-distance objective, read from device tables as well (cindm_ddpm1d_set_design_pairdist below):
  *   sum_b sum_l sum_p weight[b | 0, l, p] * ( max(lo[b | 0, l, p] - r, 0)^2 + max(r - hi[b | 0, l, p], 0)^2 )
  *   with r the distance between the positions of the bodies of pair p at row l (+ the time-consistency term); last_n_step, coef and
- *   pos_target are not read either. */
+ *   pos_target are not read either.
+ * Mode 7 is the sum of every kind of table armed on the handle, at least one: the values of modes 3 | 4, 5 and 6 added, with the
+ *   time-consistency term once.  The three setters arm the terms; each armed kind is checked against the state as under its own mode.
+ *   The update evaluates each present term as that mode's own kernel does and adds them in the order quadratic, waypoint,
+ *   pair-distance, each sum rounded once (compose_update_sum_kernel; a sum of one kind is that kind's mode bit for bit).  In mode 7
+ *   last_n_step is not a row count: it names the waypoint term's norm, 1 = "L2", 2 = "L2square" (the point modes' numbering); it is
+ *   ignored when no waypoint tables are armed and any other value is refused when they are.  coef and pos_target are not read. */
 typedef struct {
-    int32_t mode;               /* 1 = "L2", 2 = "L2square"; 3 = table "L2", 4 = table "L2square"; 5 = quadratic tables; 6 = pair-distance tables */
+    int32_t mode;               /* 1 = "L2", 2 = "L2square"; 3 = table "L2", 4 = table "L2square"; 5 = quadratic tables; 6 = pair-distance tables; 7 = the sum of the tables armed */
     int32_t alpha;              /* 0: "standard" (gradient as is), 1: "standard-alpha" (x eta_t)   :1243-1248 */
     int32_t recurrence;         /* 0: non-recurrence branch; N >= 1: "-recurrence-N"                :1284-1370 */
     int32_t last_n_step;
