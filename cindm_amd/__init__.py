@@ -12,8 +12,10 @@ from .forceunet import ForceObjective, ForceUnet
 from .objectives import PairDistanceObjective, PointObjective, QuadraticObjective, SumObjective, WaypointObjective
 from .record import ChainRecord
 from .schedule import make_schedule
+from .simulate import design_report, simulation
 from .unet1d import TemporalUnet1D
 from .unet2d import Unet
 
 __all__ = ["TemporalUnet1D", "GaussianDiffusion1D", "NoiseTape", "Unet", "GaussianDiffusion", "NoiseTape2D", "ChainRecord",
-           "PointObjective", "WaypointObjective", "QuadraticObjective", "PairDistanceObjective", "SumObjective", "ForceUnet", "ForceObjective", "Trainer", "make_schedule", "CindmError", "get_item_1d", "to_simulator_units", "eval_simu"]
+           "PointObjective", "WaypointObjective", "QuadraticObjective", "PairDistanceObjective", "SumObjective", "ForceUnet", "ForceObjective", "Trainer", "make_schedule", "CindmError", "get_item_1d", "to_simulator_units", "eval_simu", "simulation",
+           "design_report"]

@@ -55,6 +55,11 @@ class DesignDesc(C.Structure):
                 ("coef", C.c_float), ("time_consistency_coef", C.c_float), ("pos_target", C.c_float * 2)]
 
 
+class NBodyDesc(C.Structure):
+    _fields_ = [("width", C.c_double), ("height", C.c_double), ("radius", C.c_double), ("wall_radius", C.c_double),
+                ("dt", C.c_double), ("max_events_per_frame", C.c_int32)]
+
+
 COMPOSE_PLAIN, COMPOSE_MEAN_INSIDE, COMPOSE_SUM_INSIDE, COMPOSE_MEAN_OUTSIDE, COMPOSE_NOISESUM_OUTSIDE, \
     COMPOSE_MULTIBODY = range(6)
 OBJECTIVES = {"pred_noise": 0, "pred_x0": 1, "pred_v": 2}
@@ -130,7 +135,8 @@ SIGNATURES = {
     "cindm_ddpm1d_sample_ddim_guided": (C.c_int, [_vp, _vp, _vp, C.POINTER(ComposeDesc), C.POINTER(DesignDesc), _vp, _vp, _i32, _vp, _vp,
                                                   _vp, _vp, _u64, _i64, _vp, _i32, _vp, _vp, _i32, _i64, _vp, _sz, _vp, _i32]),
     "cindm_fill_normal": (C.c_int, [_vp, _i64, _i64, _u64, _i64, _i32, _vp]),
-    "cindm_ddpm1d_launches_per_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(ComposeDesc)]),
+    "cindm_nbody_simulate": (C.c_int, [C.POINTER(NBodyDesc), _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "cindm_ddpm1d_launches_per_step":(C.c_int, [_vp, _vp, _vp, C.POINTER(ComposeDesc)]),
     "cindm_ddpm1d_last_step_info": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "cindm_unet2d_create": (C.c_int, [C.POINTER(Unet2dDesc), C.POINTER(_vp)]),
     "cindm_unet2d_destroy": (None, [_vp]),

@@ -1,11 +1,13 @@
 // Host side of libcindm_hip.so: C ABI declared in include/cindm_hip.h.  This file holds the globals, the error macros and
 // the RCCL block; the launch sequence of TemporalUnet1D.forward (model/diffusion_1d.py:610-646 of the reference) is in
 // unet1d_host.inc, that of one DDPM reverse step (model/diffusion_1d.py:951-1044, :1047-1186, :1190-1376, :1380-1652) in
-// ddpm1d_host.inc, the 2-D path in unet2d_host.inc / forceunet_host.inc / ddpm2d_host.inc.  gfx950 only.
+// ddpm1d_host.inc, the 2-D path in unet2d_host.inc / forceunet_host.inc / ddpm2d_host.inc, the n-body re-simulation in nbody_host.inc.
+// gfx950 only.
 #include "kernels.h"
 #include "kernels_dconv.h"
 #include "kernels2d.h"
 #include "kernels2d_v2.h"
+#include "nbody.h"
 #include "../../include/cindm_hip.h"
 
 #include <hip/hip_ext.h>
@@ -74,6 +76,9 @@ static std::atomic<int> g_generation{0};
 #include "unet2d_host.inc"
 #include "forceunet_host.inc"
 #include "ddpm2d_host.inc"
+
+// ============================================================================ n-body re-simulation
+#include "nbody_host.inc"
 
 // ---- multi-GPU: the one all-gather of the path, on RCCL (include/cindm_hip.h) -----------------------------------------------
 #include <dlfcn.h>

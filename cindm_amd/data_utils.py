@@ -7,10 +7,12 @@ between the reference's PyG batches and the diffusion state.
 what the inference scripts do by hand before re-simulating a design (``pred * 200``,
 inference/inverse_design_diffusion_1d.py:286-300).  Pure tensor reshapes: host or device, no library call.
 ``eval_simu`` mirrors utils.py:1127-1148 around a REQUIRED ``simulation`` callable: the reference's own simulator
-(utils.py:1076-1124) is a pymunk / pygame program and neither package is installed in this image, so the simulator itself stays out
-of reach -- everything eval_simu does AROUND it (units, layout, sub-sampling, the objective) is here and pinned against the reference
-function run with the same stand-in simulator (tests/golden/eval_simu_r4.npz and the script that made it).  Nothing in this package
-imports the reference (tests/test_host_logic.py::test_package_never_imports_the_reference)."""
+(utils.py:1076-1124) is a pymunk / pygame program that this package neither imports nor needs -- everything eval_simu does AROUND the
+simulator (units, layout, sub-sampling, the objective) is here and pinned against the reference function run with the same stand-in
+simulator (tests/golden/eval_simu_r4.npz and the script that made it).  The package's own simulator is ``cindm_amd.simulation``
+(simulate.py: one kernel launch for the whole batch; the continuous-time dynamics of the same scene, not Chipmunk's step), passed
+as ``simulation=cindm_amd.simulation``; a caller that has pymunk passes the reference's and compares.  Nothing in this package imports
+the reference (tests/test_host_logic.py::test_package_never_imports_the_reference)."""
 import torch
 
 NBODY_SCALE = 200.0
@@ -42,9 +44,10 @@ def eval_simu(cond_design, design_fn, n_bodies, rollout_steps, time_interval=4, 
 
     cond_design: [batch, conditioned_steps, n_bodies * 4] in diffusion units; returns ``(pred_simu [batch, rollout_steps,
     n_bodies * 4] in diffusion units on cond_design's device, design_fn(pred_simu))``.  ``simulation(features=[batch, n_bodies, 4]
-    in simulator units, n_steps=rollout_steps * time_interval) -> [batch, n_steps, n_bodies, 4]`` is REQUIRED: the reference's
-    simulator (utils.py:1076-1124) is a pymunk / pygame program outside this package -- a caller that has it passes it in
-    (``from utils import simulation`` in the caller's own script); this package never imports the reference."""
+    in simulator units, n_steps=rollout_steps * time_interval) -> [batch, n_steps, n_bodies, 4]`` is REQUIRED:
+    ``cindm_amd.simulation`` (on the device; continuous-time dynamics, not Chipmunk's step) or the reference's simulator
+    (utils.py:1076-1124, a pymunk / pygame program outside this package -- a caller that has it passes it in, ``from utils import
+    simulation`` in the caller's own script); this package never imports the reference."""
     if not callable(simulation):
         raise TypeError("eval_simu: simulation= must be a callable simulator (the reference's utils.simulation needs pymunk / pygame "
                         "and is not part of this package)")

@@ -870,6 +870,29 @@ int  cindm_ddpm2d_sample_ddim_force(cindm_ddpm1d* sched, cindm_unet2d* u, cindm_
                                     int32_t down_factor, int32_t sum_boundary, float* grad, void* ws, size_t ws_bytes,
                                     void* ws_force, size_t ws_force_bytes, void* stream, int32_t use_graph);
 
+/* ------------------------------------------------------------------ n-body re-simulation of designs
+ * Stands where the reference calls utils.simulation (utils.py:1071-1125, a pymunk / pygame program): B independent scenes of n_bodies
+ * equal, frictionless, perfectly elastic discs of radius `radius` in a box whose walls are segments of half-thickness wall_radius on
+ * x = 0, width, y = 0, height (add_body / add_walls, utils.py:1009-1033), no gravity, no damping, advanced by the continuous-time
+ * dynamics: centres live in [lo, hi] = [radius + wall_radius, extent - radius - wall_radius] per axis; inside a frame of length dt the
+ * earliest wall or pair contact is found in closed form, every body is moved to it, the contact is resolved (wall: that velocity
+ * component changes sign; pair: the normal components exchange) and the search repeats, at most max_events_per_frame times per frame,
+ * after which the rest of the frame is ballistic.  NOT an emulation of Chipmunk's fixed-step impulse solver: trajectories differ from
+ * pymunk's by about one step's travel per contact (DESIGN 4.10b states the rule in full and what has not been measured).
+ * features [B, n_bodies, 4] = (x, y, vx, vy) and out [B, n_steps, n_bodies, 4] are DEVICE float64 (the reference's simulator returns
+ * float64); frame i of out is the state at time i * dt, frame 0 the input.  status [B], DEVICE: bit 1 = the input starts with an
+ * overlap or a centre outside [lo, hi]; 2 = the event cap was reached in some frame; 4 = coincident centres at a pair event (skipped,
+ * that frame ends ballistically); 8 = a non-finite input (every output row of that design is NaN, nothing else is set).  events [B],
+ * DEVICE: contacts resolved over the n_steps - 1 frames stepped.  Asynchronous on `stream`; no allocation, no handle, no workspace.
+ * Checked before the launch: non-null pointers, 1 <= n_bodies <= 8, 1 <= n_steps <= 65535, 1 <= B <= 2^22, radius > 0,
+ * wall_radius >= 0, hi > lo on both axes, dt > 0 and finite, 1 <= max_events_per_frame <= 4096. */
+typedef struct {
+    double width, height, radius, wall_radius, dt;
+    int32_t max_events_per_frame;
+} cindm_nbody_desc;
+int  cindm_nbody_simulate(const cindm_nbody_desc* desc, const double* features, int64_t B, int32_t n_bodies, int32_t n_steps,
+                          double* out, int32_t* status, int32_t* events, void* stream);
+
 /* ------------------------------------------------------------------ multi-GPU: the one collective of the path
  * the design batch is sharded over the ranks with no communication inside the reverse loop;
  * the final designs are all-gathered ONCE.  The reference has no counterpart (inference/inverse_design_diffusion_1d.py:161 is
