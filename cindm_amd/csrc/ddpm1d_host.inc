@@ -251,6 +251,20 @@ static int known1_node(const Chain1D& ch, const StepIO& io, float* x, const int*
     return 0;
 }
 
+// One launch of the element-wise update: the instantiation of compose_update_body by the armed objective (dz_mode: 5 quadratic, 6 pair
+// distance, 7 the sum, whose tables `dsum` holds; anything else the position objectives or none) and by `hist`, the multistep
+// solver's history (null: the update without the multistep term).
+static void launch_compose_update(const ComposeArgs& a, const DesignSum& dsum, float* hist, int64_t ne, hipStream_t stream) {
+    const dim3 grid((unsigned)((ne + 255) / 256));
+    const int dzm = a.dz_mode & kDzModeMask;
+    if (dzm == kDesignSumMode) launch_compose_update_sum(a, dsum, hist, ne, stream);
+    else if (dzm == 6) launch_compose_update_pair(a, hist, ne, stream);
+    else if (dzm == 5 && hist) hipLaunchKernelGGL(compose_update_ms_quad_kernel, grid, dim3(256), 0, stream, a, hist);
+    else if (dzm == 5) hipLaunchKernelGGL(compose_update_quad_kernel, grid, dim3(256), 0, stream, a);
+    else if (hist) hipLaunchKernelGGL(compose_update_ms_kernel, grid, dim3(256), 0, stream, a, hist);
+    else hipLaunchKernelGGL(compose_update_kernel, grid, dim3(256), 0, stream, a);
+}
+
 static int run_step(const Chain1D& ch, const StepIO& io, int32_t t, const int32_t* t_dev) {
     if (step1_refuse(ch, io.x, io.cond) != 0) return -1;
     cindm_ddpm1d* h = ch.h; cindm_unet1d* pair = ch.pair; cindm_unet1d* uncond = ch.uncond; const cindm_compose_desc* c = ch.c;
@@ -376,19 +390,11 @@ static int run_step(const Chain1D& ch, const StepIO& io, int32_t t, const int32_
         // the unguided DDIM update under pred_x0 / pred_v with the clamp on: pred_noise re-derived from the clamped x_start, as
         // model_predictions(clip_x_start = True) does (never fused: the fused update serves pred_noise only)
         launch_compose_update_clamped(a, io.ms_hist, ne, stream);
-    } else if (io.ms_hist && io.ddim_tab && !(guided && io.relax)) {
-        // the multistep solver's update (never fused; a relaxation iteration is not an update and keeps the kernels below)
-        if ((a.dz_mode & kDzModeMask) == kDesignSumMode) launch_compose_update_sum(a, dsum, io.ms_hist, ne, stream);
-        else if ((a.dz_mode & kDzModeMask) == 6) launch_compose_update_pair(a, io.ms_hist, ne, stream);
-        else if ((a.dz_mode & kDzModeMask) == 5) hipLaunchKernelGGL(compose_update_ms_quad_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a, io.ms_hist);
-        else hipLaunchKernelGGL(compose_update_ms_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a, io.ms_hist);
-    } else if ((a.dz_mode & kDzModeMask) == kDesignSumMode) {      // (guided: never fused)
-        launch_compose_update_sum(a, dsum, nullptr, ne, stream);
-    } else if ((a.dz_mode & kDzModeMask) == 6) {      // (guided: never fused)
-        launch_compose_update_pair(a, nullptr, ne, stream);
-    } else if ((a.dz_mode & kDzModeMask) == 5) {      // (guided: never fused)
-        hipLaunchKernelGGL(compose_update_quad_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a);
-    } else if (!pair->fused_done) hipLaunchKernelGGL(compose_update_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, stream, a);
+    } else if (!pair->fused_done) {
+        // (a guided step and a multistep chain are never fused.)  The multistep solver's history goes to a step's update only: a
+        // relaxation iteration is not an update and leaves it alone
+        launch_compose_update(a, dsum, (io.ms_hist && io.ddim_tab && !(guided && io.relax)) ? io.ms_hist : nullptr, ne, stream);
+    }
     pair->epoch_slot = 0;
     if (uncond) uncond->epoch_slot = 0;
     if (io.pingpong) {                       // the update has advanced t and the epochs for the next step

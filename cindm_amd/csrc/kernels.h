@@ -2650,7 +2650,7 @@ __device__ __forceinline__ bool plain_step_draws(const ComposeArgs& a, const Ste
     if (a.ddim_tab) return c.tn >= 0 && (a.noise != nullptr || c.sg != 0.f);
     return a.add_noise && t > 0;
 }
-// plain_step_value with the coefficients in hand: operation for operation the same expression
+// plain_step_value (above), given the step's coefficients
 __device__ __forceinline__ float plain_step_value(const ComposeArgs& a, const StepCoefs& c, int t, float xv, float o, float z) {
     float x0 = (a.objective == 1) ? o : __fsub_rn(__fmul_rn(c.cx, xv), __fmul_rn(c.co, o));
     if (a.clip) x0 = clamp_pm1(x0);
@@ -2660,16 +2660,6 @@ __device__ __forceinline__ float plain_step_value(const ComposeArgs& a, const St
     }
     float v = __fadd_rn(__fmul_rn(c.k1, x0), __fmul_rn(c.k2, xv));
     if (a.add_noise && t > 0) v += c.sigma * z;
-    return v;
-}
-__device__ __forceinline__ float plain_step_value(const ComposeArgs& a, int t, float xv, float o, float z) {
-    float x0;
-    if (a.objective == 0) x0 = __fsub_rn(__fmul_rn(a.sqrt_recip[t], xv), __fmul_rn(a.sqrt_recipm1[t], o));
-    else if (a.objective == 1) x0 = o;
-    else x0 = __fsub_rn(__fmul_rn(a.sqrt_ac[t], xv), __fmul_rn(a.sqrt_1mac[t], o));
-    if (a.clip) x0 = clamp_pm1(x0);
-    float v = __fadd_rn(__fmul_rn(a.coef1[t], x0), __fmul_rn(a.coef2[t], xv));
-    if (a.add_noise && t > 0) v += expf(0.5f * a.logvar[t]) * z;
     return v;
 }
 
@@ -3693,139 +3683,136 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
     if (a.mean_out) a.mean_out[i] = mean;
     if (a.x0_out) a.x0_out[i] = x0;
     if (a.eps_out) a.eps_out[i] = eps;
+    // The gradients of the table objectives, each stated once: the instantiation of a single objective and the sum (kObjSum) call the
+    // same helper, with their own two table addresses and per-design bits.
+    // quadratic objective: (sum_f' S[l, f, f'] x[b, l, f']) - h[l, f], from 0.f in ascending f', every product and sum rounded once, h
+    // subtracted last.  F % 4 == 0 and 16-byte aligned tables and states (qdt_begin): both rows are read as float4.
+    auto grad_quad = [&](const float* S, const float* h, bool S_per_design, bool h_per_design) -> float {
+        const int64_t bS = S_per_design ? b : 0, bh = h_per_design ? b : 0;
+        const int64_t srow = (bS * a.Ltot + lx) * a.F + f;
+        const float4* sp = reinterpret_cast<const float4*>(S + srow * a.F);
+        const float4* xp = reinterpret_cast<const float4*>(a.x + (i - f));
+        float acc = 0.f;
+        for (int k = 0; k < (a.F >> 2); ++k) {
+            const float4 sv = sp[k], xq = xp[k];
+            acc = __fadd_rn(acc, __fmul_rn(sv.x, xq.x)); acc = __fadd_rn(acc, __fmul_rn(sv.y, xq.y));
+            acc = __fadd_rn(acc, __fmul_rn(sv.z, xq.z)); acc = __fadd_rn(acc, __fmul_rn(sv.w, xq.w));
+        }
+        return __fsub_rn(acc, h[(bh * a.Ltot + lx) * a.F + f]);
+    };
+    // waypoint objective (position components only): the point branch's expressions with the scale and the target read per
+    // (design | all, row, body); 0.f where the scale is
+    auto grad_way = [&](const float* target, const float* scale, bool target_per_design, bool scale_per_design, bool l2) -> float {
+        const int64_t bs = scale_per_design ? b : 0, bt = target_per_design ? b : 0;
+        const float s = scale[(bs * a.Ltot + lx) * a.nb + body];
+        if (s == 0.f) return 0.f;
+        const float* tp = target + ((bt * a.Ltot + lx) * a.nb + body) * 2;
+        const float d = xv - tp[comp];
+        if (!l2) return s * 2.0f * d;
+        const float dother = a.x[i ^ 1] - tp[comp ^ 1];
+        return s * d / sqrtf(d * d + dother * dother);
+    };
+    // pair-distance objective (position components only): the sum over the other bodies o, ascending, from 0.f, of the pair {body, o}'s term
+    //   w * 2 * (r - lo) * d / r  where r < lo,   w * 2 * (r - hi) * d / r  where r > hi,   0.f otherwise and where w == 0 or r == 0,
+    // d = x[body, comp] - x[o, comp], r = sqrt(dx dx + dy dy): every product, sum, square root and quotient rounded once, in the order
+    // ((((w * 2) * (r - bound)) * d) / r).  Every state load is in the thread's own row of x (F floats at i - f); the tables' indices
+    // are bounded by pdt_begin's rows == Ltot, n_bodies == nb, batch == B.
+    auto grad_pair = [&](const float* band, const float* weight, bool band_per_design, bool weight_per_design) -> float {
+        const int64_t bb = band_per_design ? b : 0, bw = weight_per_design ? b : 0;
+        const float* xr = a.x + (i - f);
+        const float* wp = weight + (bw * a.Ltot + lx) * P;
+        const float* bp = band + (bb * a.Ltot + lx) * P * 2;
+        const float xw = a.x[i ^ 1];
+        float gp = 0.f;
+        for (int o = 0; o < a.nb; ++o) {
+            if (o == body) continue;
+            const int p = pair_index(min(body, o), max(body, o), a.nb);
+            const float w = wp[p];
+            float term = 0.f;
+            if (w != 0.f) {
+                const float lo = bp[2 * p], hi = bp[2 * p + 1];
+                const float d = __fsub_rn(xv, xr[4 * o + comp]), dw = __fsub_rn(xw, xr[4 * o + (comp ^ 1)]);
+                const float r = sqrtf(__fadd_rn(__fmul_rn(d, d), __fmul_rn(dw, dw)));
+                if (r != 0.f && (r < lo || r > hi))
+                    term = __fmul_rn(__fmul_rn(__fmul_rn(w, 2.0f), __fsub_rn(r, r < lo ? lo : hi)), d) / r;
+            }
+            gp = __fadd_rn(gp, term);
+        }
+        return gp;
+    };
+    // The tails of a reverse step, each stated once for the guided and the unguided branch.
+    const uint32_t el = (uint32_t)(lx * a.F + f);
+    // inpainting overwrite with q_sample(cond, t) (:1715-1718, DDIM :1790-1793); tape_row: t on the DDPM loops, the step index on the DDIM loops
+    auto overwrite_known = [&](float v, int tape_row) -> float {
+        if (!(a.inp_cond && lx < a.inp_steps)) return v;
+        const size_t ci = ((size_t)b * a.inp_steps + lx) * a.F + f;
+        const float z = a.inp_noise ? a.inp_noise[(size_t)tape_row * a.inp_noise_t_stride + ci]
+                                    : counter_normal(dseed ^ 0x5bd1e995u, (uint64_t)(dsoff + b), (uint32_t)t, el);
+        return a.sqrt_ac[t] * a.inp_cond[ci] + a.sqrt_1mac[t] * z;
+    };
+    auto ddpm_tail = [&](float v) -> float {
+        if (a.add_noise && t > 0) {
+            const float z = a.noise ? a.noise[(size_t)t * a.noise_t_stride + i]
+                                    : counter_normal(dseed, (uint64_t)(dsoff + b), (uint32_t)t, el);
+            v += expf(0.5f * a.logvar[t]) * z;
+        }
+        return overwrite_known(v, t);
+    };
+    // x_{next} = x0 * sqrt(alpha_next) + c * e + sigma * z (ddim_sample :1781-1783), each product and sum rounded once; the last step
+    // returns x0 (:1784-1789).  e: eps, or eps + g on the guided loop.
+    auto ddim_tail = [&](float e) -> float {
+        const int tn = a.ddim_tnext[sidx];
+        float v = x0;
+        if (tn >= 0) {
+            const float san = a.ddim_tab[4 * sidx], cc = a.ddim_tab[4 * sidx + 1], sg = a.ddim_tab[4 * sidx + 2];
+            const float z = a.noise ? a.noise[(size_t)sidx * a.noise_t_stride + i]
+                            : (sg != 0.f ? counter_normal(dseed, (uint64_t)(dsoff + b), (uint32_t)t, el) : 0.f);
+            v = __fadd_rn(__fadd_rn(__fmul_rn(x0, san), __fmul_rn(cc, e)), __fmul_rn(sg, z));
+            if constexpr (kMulti) {
+                const float kap = a.ddim_tab[4 * sidx + 3];
+                if (kap != 0.f) v = __fadd_rn(v, __fmul_rn(kap, __fsub_rn(x0, hist[i])));
+            }
+            v = overwrite_known(v, sidx);
+        }
+        if constexpr (kMulti) hist[i] = x0;
+        return v;
+    };
+
     if (a.x_out && a.dz_mode) {
         // guided update with the built-in objective (x_out never aliases x here: the gradient reads neighbours).  With ddim_tab set
         // too this is the guided DDIM loop: relaxation iterations as below, the last iteration is the DDIM update on (eps + g, x0).
         float g = 0.f;
         const int dzm = a.dz_mode & kDzModeMask;
-        if constexpr (kObj == kObjQuad) {
-            // quadratic objective: g = (sum_f' S[l, f, f'] x[b, l, f']) - h[l, f], from 0.f in ascending f', every product and sum rounded
-            // once, h subtracted last.  F % 4 == 0 and 16-byte aligned tables and states (qdt_begin): both rows are read as float4.
-            const int64_t bS = (a.dz_mode & kDzTargetPerDesign) ? b : 0, bh = (a.dz_mode & kDzScalePerDesign) ? b : 0;
-            const int64_t srow = (bS * a.Ltot + lx) * a.F + f;
-            const float4* sp = reinterpret_cast<const float4*>(a.dz_S + srow * a.F);
-            const float4* xp = reinterpret_cast<const float4*>(a.x + (i - f));
-            float acc = 0.f;
-            for (int k = 0; k < (a.F >> 2); ++k) {
-                const float4 sv = sp[k], xq = xp[k];
-                acc = __fadd_rn(acc, __fmul_rn(sv.x, xq.x)); acc = __fadd_rn(acc, __fmul_rn(sv.y, xq.y));
-                acc = __fadd_rn(acc, __fmul_rn(sv.z, xq.z)); acc = __fadd_rn(acc, __fmul_rn(sv.w, xq.w));
-            }
-            g = __fsub_rn(acc, a.dz_h[(bh * a.Ltot + lx) * a.F + f]);
-        }
+        if constexpr (kObj == kObjQuad) g = grad_quad(a.dz_S, a.dz_h, a.dz_mode & kDzTargetPerDesign, a.dz_mode & kDzScalePerDesign);
         if constexpr (kObj == kObjSum) {
-            // the sum of the armed table objectives: each present term exactly as its own instantiation evaluates it (the kObjQuad
-            // expression above, the table branch and the kObjPair accumulation below), then g = the first present term's value and
-            // g = g + next, rounded once each, in the order quadratic, waypoint, pair-distance.  An absent kind contributes no
-            // operation; velocity components see the quadratic term only.  Table indices are bounded as in the three originals, by
-            // design_begin's rows == Ltot, width and batch == B checks of every kind taken.
+            // the sum of the armed table objectives: g = the first present term's value and g = g + next, rounded once each, in the
+            // order quadratic, waypoint, pair-distance.  An absent kind contributes no operation; velocity components see the quadratic
+            // term only.  Table indices are bounded as in the three single instantiations, by design_begin's rows == Ltot, width and
+            // batch == B checks of every kind taken.
             const int fl = sum->flags;
             bool have = false;
-            if (fl & kSumQuad) {
-                const int64_t bS = (fl & kSumQuadSPerDesign) ? b : 0, bh = (fl & kSumQuadHPerDesign) ? b : 0;
-                const int64_t srow = (bS * a.Ltot + lx) * a.F + f;
-                const float4* sp = reinterpret_cast<const float4*>(sum->quad_S + srow * a.F);
-                const float4* xp = reinterpret_cast<const float4*>(a.x + (i - f));
-                float acc = 0.f;
-                for (int k = 0; k < (a.F >> 2); ++k) {
-                    const float4 sv = sp[k], xq = xp[k];
-                    acc = __fadd_rn(acc, __fmul_rn(sv.x, xq.x)); acc = __fadd_rn(acc, __fmul_rn(sv.y, xq.y));
-                    acc = __fadd_rn(acc, __fmul_rn(sv.z, xq.z)); acc = __fadd_rn(acc, __fmul_rn(sv.w, xq.w));
-                }
-                g = __fsub_rn(acc, sum->quad_h[(bh * a.Ltot + lx) * a.F + f]);
-                have = true;
-            }
-            if (comp < 2 && (fl & kSumWay)) {
-                const int64_t bs = (fl & kSumWayScalePerDesign) ? b : 0, bt = (fl & kSumWayTargetPerDesign) ? b : 0;
-                const float s = sum->way_scale[(bs * a.Ltot + lx) * a.nb + body];
-                float gw = 0.f;
-                if (s != 0.f) {
-                    const float* tp = sum->way_target + ((bt * a.Ltot + lx) * a.nb + body) * 2;
-                    const float d = xv - tp[comp];
-                    if (fl & kSumWayL2) {
-                        const float dother = a.x[i ^ 1] - tp[comp ^ 1];
-                        gw = s * d / sqrtf(d * d + dother * dother);
-                    } else {
-                        gw = s * 2.0f * d;
-                    }
-                }
-                g = have ? __fadd_rn(g, gw) : gw;
-                have = true;
-            }
-            if (comp < 2 && (fl & kSumPair)) {
-                const int64_t bb = (fl & kSumPairBandPerDesign) ? b : 0, bw = (fl & kSumPairWeightPerDesign) ? b : 0;
-                const float* xr = a.x + (i - f);
-                const float* wp = sum->pair_weight + (bw * a.Ltot + lx) * P;
-                const float* bp = sum->pair_band + (bb * a.Ltot + lx) * P * 2;
-                const float xw = a.x[i ^ 1];
-                float gp = 0.f;
-                for (int o = 0; o < a.nb; ++o) {
-                    if (o == body) continue;
-                    const int p = pair_index(min(body, o), max(body, o), a.nb);
-                    const float w = wp[p];
-                    float term = 0.f;
-                    if (w != 0.f) {
-                        const float lo = bp[2 * p], hi = bp[2 * p + 1];
-                        const float d = __fsub_rn(xv, xr[4 * o + comp]), dw = __fsub_rn(xw, xr[4 * o + (comp ^ 1)]);
-                        const float r = sqrtf(__fadd_rn(__fmul_rn(d, d), __fmul_rn(dw, dw)));
-                        if (r != 0.f && (r < lo || r > hi))
-                            term = __fmul_rn(__fmul_rn(__fmul_rn(w, 2.0f), __fsub_rn(r, r < lo ? lo : hi)), d) / r;
-                    }
-                    gp = __fadd_rn(gp, term);
-                }
-                g = have ? __fadd_rn(g, gp) : gp;
-            }
+            auto add = [&](float next) { g = have ? __fadd_rn(g, next) : next; have = true; };
+            if (fl & kSumQuad) add(grad_quad(sum->quad_S, sum->quad_h, fl & kSumQuadSPerDesign, fl & kSumQuadHPerDesign));
+            if (comp < 2 && (fl & kSumWay))
+                add(grad_way(sum->way_target, sum->way_scale, fl & kSumWayTargetPerDesign, fl & kSumWayScalePerDesign, fl & kSumWayL2));
+            if (comp < 2 && (fl & kSumPair)) add(grad_pair(sum->pair_band, sum->pair_weight, fl & kSumPairBandPerDesign, fl & kSumPairWeightPerDesign));
         }
         if (comp < 2) {
-            if constexpr (kObj == kObjQuad || kObj == kObjSum) {
-                // (the position objectives of modes 1 - 4 are not part of these instantiations; the time-consistency term below is)
-            } else if constexpr (kObj == kObjPair) {
-                // pair-distance objective: g = sum over the other bodies o, ascending, from 0.f, of the pair {body, o}'s term
-                //   w * 2 * (r - lo) * d / r  where r < lo,   w * 2 * (r - hi) * d / r  where r > hi,   0.f otherwise and where w == 0 or r == 0,
-                // d = x[body, comp] - x[o, comp], r = sqrt(dx dx + dy dy): every product, sum, square root and quotient rounded once, in
-                // the order ((((w * 2) * (r - bound)) * d) / r).  Every state load is in the thread's own row of x (F floats at i - f);
-                // the tables' indices are bounded by pdt_begin's rows == Ltot, n_bodies == nb, batch == B.
-                const int64_t bb = (a.dz_mode & kDzTargetPerDesign) ? b : 0, bw = (a.dz_mode & kDzScalePerDesign) ? b : 0;
-                const float* xr = a.x + (i - f);
-                const float* wp = a.dz_weight + (bw * a.Ltot + lx) * P;
-                const float* bp = a.dz_band + (bb * a.Ltot + lx) * P * 2;
-                const float xw = a.x[i ^ 1];
-                for (int o = 0; o < a.nb; ++o) {
-                    if (o == body) continue;
-                    const int p = pair_index(min(body, o), max(body, o), a.nb);
-                    const float w = wp[p];
-                    float term = 0.f;
-                    if (w != 0.f) {
-                        const float lo = bp[2 * p], hi = bp[2 * p + 1];
-                        const float d = __fsub_rn(xv, xr[4 * o + comp]), dw = __fsub_rn(xw, xr[4 * o + (comp ^ 1)]);
-                        const float r = sqrtf(__fadd_rn(__fmul_rn(d, d), __fmul_rn(dw, dw)));
-                        if (r != 0.f && (r < lo || r > hi))
-                            term = __fmul_rn(__fmul_rn(__fmul_rn(w, 2.0f), __fsub_rn(r, r < lo ? lo : hi)), d) / r;
-                    }
-                    g = __fadd_rn(g, term);
-                }
-            } else if (dzm >= 3) {
-                // table objective: the point branch's expressions with the scale and the target read per (design | all, row, body)
-                const int64_t bs = (a.dz_mode & kDzScalePerDesign) ? b : 0, bt = (a.dz_mode & kDzTargetPerDesign) ? b : 0;
-                const float s = a.dz_scale[(bs * a.Ltot + lx) * a.nb + body];
-                if (s != 0.f) {
-                    const float* tp = a.dz_target + ((bt * a.Ltot + lx) * a.nb + body) * 2;
-                    const float d = xv - tp[comp];
-                    if (dzm == 3) {
-                        const float dother = a.x[i ^ 1] - tp[comp ^ 1];
-                        g = s * d / sqrtf(d * d + dother * dother);
+            // (the position objectives of modes 1 - 4 are part of kObjPosition only; the time-consistency term below is part of all)
+            if constexpr (kObj == kObjPair) {
+                g = grad_pair(a.dz_band, a.dz_weight, a.dz_mode & kDzTargetPerDesign, a.dz_mode & kDzScalePerDesign);
+            } else if constexpr (kObj == kObjPosition) {
+                if (dzm >= 3) {
+                    g = grad_way(a.dz_target, a.dz_scale, a.dz_mode & kDzTargetPerDesign, a.dz_mode & kDzScalePerDesign, dzm == 3);
+                } else if (lx >= a.Ltot - a.dz_last_n) {
+                    const float d = xv - (comp == 0 ? a.dz_tx : a.dz_ty);
+                    const float scale = a.dz_coef / (float)a.dz_last_n;
+                    if (a.dz_mode == 1) {
+                        const float dother = a.x[i ^ 1] - (comp == 0 ? a.dz_ty : a.dz_tx);
+                        g = scale * d / sqrtf(d * d + dother * dother);
                     } else {
-                        g = s * 2.0f * d;
+                        g = scale * 2.0f * d;
                     }
-                }
-            } else if (lx >= a.Ltot - a.dz_last_n) {
-                const float d = xv - (comp == 0 ? a.dz_tx : a.dz_ty);
-                const float scale = a.dz_coef / (float)a.dz_last_n;
-                if (a.dz_mode == 1) {
-                    const float dother = a.x[i ^ 1] - (comp == 0 ? a.dz_ty : a.dz_tx);
-                    g = scale * d / sqrtf(d * d + dother * dother);
-                } else {
-                    g = scale * 2.0f * d;
                 }
             }
             if (a.dz_tc > 0.f && a.Ltot > 1) {
@@ -3838,7 +3825,6 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
         if (a.dz_alpha) g *= a.betas[t] / sqrtf(a.acp[t]);
         float pred = mean - g;
         if (a.iso && lx < a.iso_steps) pred = a.iso[((size_t)b * a.iso_steps + lx) * a.F + f];
-        const uint32_t el = (uint32_t)(lx * a.F + f);
         float v;
         if (a.relax) {
             const float ratio = a.ac[t] / a.acp[t];
@@ -3848,81 +3834,17 @@ __device__ __forceinline__ void compose_update_body(const ComposeArgs& a, int64_
             v = sqrtf(ratio) * pred + sqrtf(1.0f - ratio) * z;
         } else if (a.ddim_tab) {
             // guided DDIM (ddim_sample :1772-1793 on p_sample_compose_inside's DDIM return :1375-1376): the last iteration hands
-            // (eps + g, x_start) to the DDIM update; its own pred / relaxed state is never used.  Roundings as the unguided branch below.
-            const int tn = a.ddim_tnext[sidx];
-            v = x0;
-            if (tn >= 0) {
-                const float epsd = __fadd_rn(eps, g);
-                const float san = a.ddim_tab[4 * sidx], cc = a.ddim_tab[4 * sidx + 1], sg = a.ddim_tab[4 * sidx + 2];
-                const float z = a.noise ? a.noise[(size_t)sidx * a.noise_t_stride + i]
-                                : (sg != 0.f ? counter_normal(dseed, (uint64_t)(dsoff + b), (uint32_t)t, el) : 0.f);
-                v = __fadd_rn(__fadd_rn(__fmul_rn(x0, san), __fmul_rn(cc, epsd)), __fmul_rn(sg, z));
-                if constexpr (kMulti) {
-                    const float kap = a.ddim_tab[4 * sidx + 3];
-                    if (kap != 0.f) v = __fadd_rn(v, __fmul_rn(kap, __fsub_rn(x0, hist[i])));
-                }
-                if (a.inp_cond && lx < a.inp_steps) {      // inpainting overwrite with q_sample(cond, time) (:1790-1793)
-                    const size_t ci = ((size_t)b * a.inp_steps + lx) * a.F + f;
-                    const float z2 = a.inp_noise ? a.inp_noise[(size_t)sidx * a.inp_noise_t_stride + ci]
-                                                 : counter_normal(dseed ^ 0x5bd1e995u, (uint64_t)(dsoff + b), (uint32_t)t, el);
-                    v = a.sqrt_ac[t] * a.inp_cond[ci] + a.sqrt_1mac[t] * z2;
-                }
-            }
-            if constexpr (kMulti) hist[i] = x0;
+            // (eps + g, x_start) to the DDIM update; its own pred / relaxed state is never used
+            v = ddim_tail(__fadd_rn(eps, g));
         } else {
-            v = pred;
-            if (a.add_noise && t > 0) {
-                const float z = a.noise ? a.noise[(size_t)t * a.noise_t_stride + i]
-                                        : counter_normal(dseed, (uint64_t)(dsoff + b), (uint32_t)t, el);
-                v += expf(0.5f * a.logvar[t]) * z;
-            }
-            if (a.inp_cond && lx < a.inp_steps) {
-                const size_t ci = ((size_t)b * a.inp_steps + lx) * a.F + f;
-                const float z = a.inp_noise ? a.inp_noise[(size_t)t * a.inp_noise_t_stride + ci]
-                                            : counter_normal(dseed ^ 0x5bd1e995u, (uint64_t)(dsoff + b), (uint32_t)t, el);
-                v = a.sqrt_ac[t] * a.inp_cond[ci] + a.sqrt_1mac[t] * z;
-            }
+            v = ddpm_tail(pred);
         }
         a.x_out[i] = v;
     } else if (a.x_out && a.ddim_tab) {
-        // x_{next} = x0 * sqrt(alpha_next) + c * eps + sigma * z (:1781-1783); the last step returns x0 (:1784-1789)
-        const int tn = a.ddim_tnext[sidx];
-        const uint32_t el = (uint32_t)(lx * a.F + f);
-        float v = x0;
-        if (tn >= 0) {
-            const float san = a.ddim_tab[4 * sidx], cc = a.ddim_tab[4 * sidx + 1], sg = a.ddim_tab[4 * sidx + 2];
-            const float z = a.noise ? a.noise[(size_t)sidx * a.noise_t_stride + i]
-                            : (sg != 0.f ? counter_normal(dseed, (uint64_t)(dsoff + b), (uint32_t)t, el) : 0.f);
-            if constexpr (kClampedEps) { if (a.objective != 0 && a.clip) eps = (ra * xv - x0) / rb; }
-            v = __fadd_rn(__fadd_rn(__fmul_rn(x0, san), __fmul_rn(cc, eps)), __fmul_rn(sg, z));
-            if constexpr (kMulti) {
-                const float kap = a.ddim_tab[4 * sidx + 3];
-                if (kap != 0.f) v = __fadd_rn(v, __fmul_rn(kap, __fsub_rn(x0, hist[i])));
-            }
-            if (a.inp_cond && lx < a.inp_steps) {      // inpainting overwrite with q_sample(cond, time) (:1790-1793)
-                const size_t ci = ((size_t)b * a.inp_steps + lx) * a.F + f;
-                const float z2 = a.inp_noise ? a.inp_noise[(size_t)sidx * a.inp_noise_t_stride + ci]
-                                             : counter_normal(dseed ^ 0x5bd1e995u, (uint64_t)(dsoff + b), (uint32_t)t, el);
-                v = a.sqrt_ac[t] * a.inp_cond[ci] + a.sqrt_1mac[t] * z2;
-            }
-        }
-        if constexpr (kMulti) hist[i] = x0;
-        a.x_out[i] = v;
+        if constexpr (kClampedEps) { if (a.objective != 0 && a.clip) eps = (ra * xv - x0) / rb; }
+        a.x_out[i] = ddim_tail(eps);
     } else if (a.x_out) {
-        float v = mean;
-        const uint32_t el = (uint32_t)(lx * a.F + f);
-        if (a.add_noise && t > 0) {
-            const float z = a.noise ? a.noise[(size_t)t * a.noise_t_stride + i]
-                                    : counter_normal(dseed, (uint64_t)(dsoff + b), (uint32_t)t, el);
-            v += expf(0.5f * a.logvar[t]) * z;
-        }
-        if (a.inp_cond && lx < a.inp_steps) {      // inpainting overwrite (:1715-1718)
-            const size_t ci = ((size_t)b * a.inp_steps + lx) * a.F + f;
-            const float z = a.inp_noise ? a.inp_noise[(size_t)t * a.inp_noise_t_stride + ci]
-                                        : counter_normal(dseed ^ 0x5bd1e995u, (uint64_t)(dsoff + b), (uint32_t)t, el);
-            v = a.sqrt_ac[t] * a.inp_cond[ci] + a.sqrt_1mac[t] * z;
-        }
-        a.x_out[i] = v;
+        a.x_out[i] = ddpm_tail(mean);
     }
     }
 }
