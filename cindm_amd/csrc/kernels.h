@@ -3887,8 +3887,9 @@ __global__ void compose_update_ms_quad_kernel(const ComposeArgs a, float* hist) 
 // n_seg * B rows of x [n_seg * B, Ltot, F], segment-major (row = k B + b); at the top of every step segment k + 1 is conditioned on
 // the last Lc rows of segment k's CURRENT (noisy) state (:1827-1829).  c is the step's ComposeArgs with c.B = n_seg * B rows and
 // c.cond = cond_buf, plain (mode 0) or multibody (mode 5) prediction.
-//   timecompose_update_kernel   the DDIM update of compose_update_element (same expressions, each product and sum rounded once, the
-//                               noise not re-derived) with the step noise of row (k, b) keyed (seeds[k], sample_off + b, t, element);
+//   timecompose_update_kernel   the unguided DDIM update of ddim_sample (same expressions, each product and sum rounded once; under
+//                               pred_x0 / pred_v the noise re-derived from the clamped x_start, as compose_update_clamped_kernel
+//                               does) with the step noise of row (k, b) keyed (seeds[k], sample_off + b, t, element);
 //                               a thread that writes a tail row (>= Ltot - Lc) of a segment k < n_seg - 1 also writes the value into
 //                               cond_buf of row (k + 1, b): the hand-over the NEXT step reads.  The step's gather has read cond_buf
 //                               before this launch starts and nothing after it in the step reads it: no hazard inside the step.
@@ -3959,8 +3960,10 @@ __global__ __launch_bounds__(256) void timecompose_update_kernel(const TimeCompo
         if (a.objective == 0) p = __fsub_rn(__fmul_rn(ra, xv[j]), __fmul_rn(rb, o[j]));
         else if (a.objective == 1) p = o[j];
         else p = __fsub_rn(__fmul_rn(a.sqrt_ac[t], xv[j]), __fmul_rn(a.sqrt_1mac[t], o[j]));
-        const float eps = (a.objective == 0) ? o[j] : (ra * xv[j] - p) / rb;
+        // model_predictions(clip_x_start = clip_denoised) (:1838): under pred_x0 / pred_v pred_noise is re-derived from the CLAMPED
+        // x_start (:1018-1027), compose_update_body's kClampedEps expression -- segment 0 stays ddim_sample bit for bit
         if (a.clip) p = clamp_pm1(p);
+        const float eps = (a.objective == 0) ? o[j] : (ra * xv[j] - p) / rb;
         x0[j] = p;
         // x_{next} = x0 * sqrt(alpha_next) + c * eps + sigma * z (:1844-1846); the last step returns x0 (:1840-1842)
         v[j] = tn >= 0 ? __fadd_rn(__fadd_rn(__fmul_rn(p, san), __fmul_rn(cc, eps)), __fmul_rn(sg, z[j])) : p;

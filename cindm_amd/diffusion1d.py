@@ -893,6 +893,10 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         """:2048-2073: ``num_samples_per_step`` Langevin iterations at timestep ts[0] on the whole state x [B, Lc + R, 16]:
         x <- x + gradient(x, t, n_bodies, scalar_for_gradient) * ss_t + randn_like(x) * std_t with ss = betas_inference * 0.035,
         std = (2 ss) ** .5.  Returns the new state (x is not modified).  The one-timestep form of the library's Langevin chain.
+        gradient() scales the composed eps by -scalar_for_gradient[t] for t > 400 only (:1923-1926); at t <= 400 it returns eps
+        itself, so the update ADDS eps * ss_t.  The library's update always multiplies by the negated table entry: for t <= 400 it
+        is handed -1.0 in place of scalar_for_gradient[t], the factor is +1 and the product exact.  (The chain of
+        ``sample_compose_multibodies`` stops at t = 401 and never takes this branch.)
         Build-only keywords: ``noise`` [num_samples_per_step, B, Lc + R, 16] explicit draws, ``seed`` / ``sample_offset``
         (counter-based draws keyed by (seed, sample_offset + b, t, l)), ``use_graph``."""
         t = self._t_int(ts)
@@ -906,7 +910,10 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
             seed = self._draw_seed()
         out = self._f32(x).clone()
         tape = None if noise is None else noise.reshape((1,) + tuple(noise.shape))
-        return self._run_ula(out, t, t, L, scalar=scalar_for_gradient, tape=tape, seed=0 if seed is None else int(seed),
+        scalar = torch.as_tensor(scalar_for_gradient).detach().to("cpu", torch.float32)
+        if t <= 400:                                    # :1923-1926: the unscaled eps; -(-1.0) * eps is eps bit for bit
+            scalar = torch.full_like(scalar, -1.0)
+        return self._run_ula(out, t, t, L, scalar=scalar, tape=tape, seed=0 if seed is None else int(seed),
                              sample_offset=sample_offset, use_graph=use_graph)
 
     @torch.no_grad()
@@ -1172,7 +1179,8 @@ class GaussianDiffusion1D(DiffusionHandle, nn.Module):
         K = n_composed + 1 segments are denoised side by side by ONE unguided DDIM chain on K * B rows: at the top of every
         step segment k + 1 takes the last conditioned_steps rows of segment k's current, still noisy state as its condition
         (segment 0 keeps ``cond``); prediction and update per step are ``ddim_sample(design_fn=None)``'s (:1838-1846;
-        clip_x_start = ``clip_denoised``, eta = ddim_sampling_eta).  S sequential steps where ``autoregress_time_compose_sample``
+        clip_x_start = ``clip_denoised``, eta = ddim_sampling_eta; under pred_x0 / pred_v with the clamp on pred_noise is
+        re-derived from the CLAMPED x_start, :1018-1027, as in ``ddim_sample``).  S sequential steps where ``autoregress_time_compose_sample``
         takes K * S -- and another algorithm: the later segments never see a finished condition.
         ``shape`` = (B, image_size, F) with B = cond.shape[0].  Returns (img [B, R, F], img_infered [B, n_composed * min(20, R), F]):
         segment 0, and the last min(20, R) rows of segments 1 .. K - 1 in order (the reference's literal ``-20:``).

@@ -821,3 +821,104 @@ def compose_repredict_f64(tab, desc, x, A_x, n_x, t, pair_eps):
     assert torch.equal(x0u, x0) and torch.equal(m, mean)
     A = {"mean": c1 * A_x0 + c2 * A_x, "x_start": A_x0, "pred_noise": A_out}
     return mean, x0, eps, A, {"mean": torch.maximum(n_x0, n_x) + 3, "x_start": n_x0, "pred_noise": n_out}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The parallel time composition and the Langevin update: one step of each on GIVEN U-Net outputs, in float64, with magnitudes
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Written from the reference (model/diffusion_1d.py:1823-1846 the loop of composing_time_sample, :1018-1027 the re-derived noise,
+# :1923-1926 gradient()'s two branches, :1998-1999 scalar_for_gradient, :2048-2059 sample_step_ULA) and from the restatements in
+# tests/test_time_compose_host.py and tests/test_ula_host.py.  Nothing new is counted for the time composition: compose_roundings
+# for the prediction, the DDIM row of the table above for the update.
+#
+#   re-derived eps     (ra x - x_start) / rb on the clamped x_start: product, difference, quotient                 -> n_x0 + 3
+#   Langevin update    (-scalar) eps (1; the negation is exact), its product with ss (1), x + that (1); z std (1); the sum (1).
+#                      The longer path is the score's                                                              -> max(n_x, n_eps + 2) + 2
+#                      t <= 400 (:1926): eps itself, one product fewer                                              -> max(n_x, n_eps + 1) + 2
+#   (n_x: the count of the state, 0 for a given one; n_eps = compose_roundings("multibody") = nb - 1 + 2.)
+
+
+def rederive_eps_f64(tab, t, x, x0, A_x0, n_x0):
+    """(pred_noise, A, n) re-derived from a (clamped) x_start as model_predictions does under pred_x0 / pred_v (:1018-1027):
+    (sqrt_recip_alphas_cumprod[t] x - x_start) / sqrt_recipm1_alphas_cumprod[t]."""
+    ra, rb = (float(tab[k][t].double()) for k in ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod"))
+    x = x.double()
+    return (ra * x - x0) / rb, (ra * x.abs() + A_x0) / rb, n_x0 + 3
+
+
+def timecompose_handover(x, cond, Lc, _mut=None, x_older=None):
+    """The conditions of the K * B rows at the top of a step (:1827-1829): rows 0 .. B the caller's ``cond`` [B, Lc, F], row (k + 1, b)
+    the last Lc rows of row (k, b) of the state ``x`` [K, B, R, F] BEFORE the step -> [K * B, Lc, F].
+    ``_mut``: ``handover_older`` from ``x_older`` (the state one step older), ``handover_same`` to segment k instead of k + 1,
+    ``handover_first`` the first Lc rows."""
+    mut = _mut or ()
+    K, B = x.shape[0], x.shape[1]
+    src = (x_older if "handover_older" in mut else x).double()
+    tails = src[:, :, :Lc] if "handover_first" in mut else src[:, :, src.shape[2] - Lc:]
+    c = torch.zeros((K, B, Lc, x.shape[3]), dtype=torch.float64)
+    c[0] = cond.double()
+    c[1:] = tails[1:] if "handover_same" in mut else tails[:-1]
+    return c.reshape(K * B, Lc, x.shape[3])
+
+
+def timecompose_step_f64(tab, desc, x, cond, t, time_next, row, z, pair_eps, single_eps=None, _mut=None, x_older=None):
+    """One step of composing_time_sample on all K * B rows -> {"state": (value, A, n_e), "x_start": (value, A, n_e)}, each
+    [K, B, R, F] float64.  ``desc``: ``plain`` or ``multibody`` with cond_steps = Lc and window = Lc + R; ``x`` [K, B, R, F] the
+    state before the step; ``row`` the fp32 (sqrt(alpha_next), c, sigma) of ``ddim_schedule()``; ``z`` [K, B, R, F] the step's draw;
+    ``pair_eps`` / ``single_eps`` the U-Net outputs on ``compose_rows(desc, x.reshape(K * B, R, F), timecompose_handover(..))``.
+    The prediction is model_predictions(clip_x_start = desc.clip): under pred_x0 / pred_v pred_noise is re-derived from the CLAMPED
+    x_start.  ``_mut``: timecompose_handover's and compose_predict_f64's mutations, and ``eps_unclamped`` (pred_noise of the unclamped
+    x_start), ``noise_neighbour`` (the draw of segment k + 1), ``san_c_swap``, ``last_not_x0``, ``coef_1`` (uncond_coef 1.0)."""
+    mut = _mut or ()
+    K, B, Rr, F = x.shape
+    Lc = desc.cond_steps
+    assert desc.mode in ("plain", "multibody") and desc.state_len == Rr
+    if "coef_1" in mut:
+        desc = desc.replace(uncond_coef=1.0)
+    rows = x.double().reshape(K * B, Rr, F)
+    c = timecompose_handover(x, cond, Lc, mut, x_older)
+    n = compose_roundings(desc.mode, desc.n_bodies, compose_cover(desc)[Lc:].double().view(1, -1, 1), desc.objective)
+    _, x0, eps, A = compose_predict_f64(tab, desc, rows, c, t, pair_eps, single_eps, _mut=mut)
+    e, Ae, ne = eps, A["pred_noise"], n["pred_noise"]
+    if desc.objective != "pred_noise" and "eps_unclamped" not in mut:
+        e, Ae, ne = rederive_eps_f64(tab, t, rows, x0, A["x_start"], n["x_start"])
+    zz = z.double().reshape(K * B, Rr, F)
+    if "noise_neighbour" in mut:
+        zz = torch.roll(z.double(), -1, dims=0).reshape(K * B, Rr, F)
+    r3 = row[:3]
+    if "san_c_swap" in mut:
+        r3 = torch.stack([row[1], row[0], row[2]])
+    st = step1d_update_f64("ddim", x0, A["x_start"], n["x_start"], tab=tab, t=t, eps=e, A_eps=Ae, n_eps=ne, row=r3, z=zz,
+                           last=(time_next < 0 and "last_not_x0" not in mut), time_next=time_next)
+    shape = (K, B, Rr, F)
+    n0 = torch.as_tensor(n["x_start"], dtype=torch.float64) + torch.zeros_like(x0)
+    return {"state": tuple(v.reshape(shape) for v in st), "x_start": (x0.reshape(shape), A["x_start"].reshape(shape), n0.reshape(shape))}
+
+
+def ula_rows_f64(betas_inference):
+    """(scalar, ss, std) of the Langevin phase in float64, indexed by the timestep (:1998-1999, :2050, :2054)."""
+    b = torch.as_tensor(betas_inference).detach().double()
+    ss = b * 0.035
+    return torch.sqrt(1 / (1 - torch.cumprod(1. - b, dim=0))), ss, (2 * ss) ** .5
+
+
+def ula_update_f64(x, eps, A_eps, n_eps, scalar, ss, std, z, *, A_x=None, n_x=0, _mut=None):
+    """One Langevin iteration in float64 -> (state, A, n_e): x + ((-scalar) eps) ss + z std (:1924, :2056, :2059), every operation
+    rounded once on the fp32 side.  ``eps`` (with ``A_eps``, ``n_eps``) is the ``multibody`` composition of compose_predict_f64;
+    ``scalar``, ``ss``, ``std`` the fp32 table entries at the timestep (cast exactly); ``scalar`` None: t <= 400, where gradient()
+    returns eps itself (:1926) and the update adds eps ss.  ``A_x``, ``n_x``: magnitude and count of a state that is itself computed
+    (the second iteration); a given state has |x| and 0.
+    ``_mut``: ``score_sign``, ``ss_std_swap`` (the host test's mutations; the others are made on the arguments)."""
+    mut = _mut or ()
+    x, e, Ae, zz = x.double(), eps.double(), A_eps.double(), z.double()
+    A_x = x.abs() if A_x is None else A_x.double()
+    f = lambda v: float(torch.as_tensor(v).double())
+    s, d = f(ss), f(std)
+    if "ss_std_swap" in mut:
+        s, d = d, s
+    k = 1.0 if scalar is None else -f(scalar)
+    if "score_sign" in mut:
+        k = -k
+    n_g = torch.as_tensor(n_eps, dtype=torch.float64) + (1 if scalar is None else 2)
+    n = torch.maximum(torch.as_tensor(n_x, dtype=torch.float64) + torch.zeros_like(x), n_g + torch.zeros_like(x)) + 2
+    return x + (k * e) * s + zz * d, A_x + abs(k) * Ae * abs(s) + zz.abs() * abs(d), n

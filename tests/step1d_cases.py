@@ -291,8 +291,7 @@ def statement(case, d, E, tab, row=None, mut=None):
     else:
         e, Ae, ne = eps, A["pred_noise"], n["pred_noise"]
         if kind is None and case.objective != "pred_noise":
-            ra, rb = (float(tab[k][t].double()) for k in ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod"))
-            e, Ae, ne = (ra * d["x"].double() - x0) / rb, (ra * d["x"].double().abs() + A["x_start"]) / rb, n["x_start"] + 3
+            e, Ae, ne = R.rederive_eps_f64(tab, t, d["x"], x0, A["x_start"], n["x_start"])
         st = R.step1d_update_f64("ddim", x0, A["x_start"], n["x_start"], tab=tab, t=t, eps=e, A_eps=Ae, n_eps=ne, g=g, A_g=Ag, n_g=ng,
                                  alpha=case.alpha, row=row, z=d["z"], last=tn < 0, hist=d["hist"], cond=d["cond"], z_cond=d["zc"], time_next=tn,
                                  _mut=mut)

@@ -33,9 +33,9 @@ def _diffusion(hz=24, Lc=4, R=20, **kw):
     return cindm_amd.GaussianDiffusion1D(m, image_size=R, conditioned_steps=Lc, timesteps=1000, loss_type="l1", **kw)
 
 
-def restated_loop(od, cond, init, step, S, eta):
+def restated_loop(od, cond, init, step, S, eta, clip=True, x_starts=None):
     """:1823-1846: per step the hand-over from the current state, one prediction on all K * B rows, the DDIM update.
-    Returns the state after every step [S, K, B, R, F]."""
+    Returns the state after every step [S, K, B, R, F]; ``x_starts``: a list that receives every step's x_start."""
     K, Bn = init.shape[0], init.shape[1]
     x = init.reshape((K * Bn,) + tuple(init.shape[2:])).clone()
     c = torch.zeros((K * Bn,) + tuple(cond.shape[1:]))
@@ -43,10 +43,12 @@ def restated_loop(od, cond, init, step, S, eta):
     states = []
     for i, (time, time_next) in enumerate(O.ddim_time_pairs(od.num_timesteps, S)):
         c[Bn:] = x[:(K - 1) * Bn, -od.conditioned_steps:]
-        pred_noise, x_start = O.model_predictions(od, x, c, time, clip_x_start=True)
+        pred_noise, x_start = O.model_predictions(od, x, c, time, clip_x_start=clip)
         san, cc, sigma = O.ddim_coefs(od, time, time_next, eta)
         x = x_start if time_next < 0 else x_start * san + cc * pred_noise + sigma * step[i].reshape(x.shape)
         states.append(x.reshape(init.shape).clone())
+        if x_starts is not None:
+            x_starts.append(x_start.reshape(init.shape).clone())
     return torch.stack(states)
 
 
